@@ -1,23 +1,28 @@
 #!/usr/bin/env python3
 """bench.py — instances/sec through transform + cull + compact (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step is one frame: ONE pass of the hot path over the resident instance arrays, outputs written to
-HBM-resident buffers, every step ordered behind the previous one (one frame in flight).
+HBM-resident buffers, every step ordered behind the previous one (one frame in flight). Exactly K steps
+are timed, after at least W untimed ones; they are split into samples of >= 20 back-to-back steps (one
+sample of K when K < 40), and `ms_per_step` is the median over samples of a sample's time / its steps.
 
   N = 1   BASELINE configs[2]: the mixed 64-mesh scene, 1 M instances ("HBM-bound regime"), the largest
           single-GPU configuration. `value` is SURVEY.md §8(d)'s metric: one mip_run, device-resident in and
-          out, bracketed by HIP events on the stream it is launched on — the MEDIAN over >= 50 samples after
-          warm-up, where a sample is `--steps` back-to-back frames (so --steps only sets the batch per sample).
+          out, bracketed by HIP events on the stream it is launched on: N / ms_per_step.
   N > 1   BASELINE configs[3]: the same generator at 10 M instances, STRONG scaling — rank r owns the
           contiguous draw_index range of ceil(10 M / N) instances; every step is shard kernel -> ONE RCCL
           all-gather of the compacted draw lists -> merge, all inside the timed region (barrier +
           synchronize on both sides, MAX over ranks per sample, median over samples).
 
-Prints ONE JSON line on rank 0. Everything else (other configurations, frames in flight, launch graphs,
-the next-tier rows) is reported under "extra" and never as `value`.
+Prints ONE JSON line on rank 0. A plain run measures the headline and nothing else. --full adds the CPU
+baseline, the per-leg breakdown of the N > 1 step and the secondary legs (other configurations, frames in
+flight, launch graphs, the next-tier rows), reported under "extra" and never as `value`.
+
+--dump-outputs DIR writes what the last timed step computed, as DIR/<name>.npy (float32 / float64; integer
+outputs are stored exactly as float64), under 64 MB in all: see OUTPUT_ROW_LIMITS.
 """
 import argparse
 import hashlib
@@ -33,7 +38,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s is the measured copy ceiling
-MIN_SAMPLES = 50
+MIN_SAMPLES = 50  # samples of the secondary event-timed legs (--full)
+STEPS_PER_SAMPLE = 20  # least back-to-back steps in one headline sample: the batch the headline was always timed in
 MIN_WARMUP_SECONDS = 0.05  # untimed launches before the timed samples of an event-timed leg, in batches of 200
 PARITY = "oracle (unpinned: the reference holds no tests, fixtures or golden vectors; SURVEY.md §8c)"
 
@@ -46,15 +52,20 @@ def algorithmic_bytes_per_instance(v):
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20, help="frames per timed sample")
+    ap.add_argument("--steps", type=int, default=1000, help="timed frames in all")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--samples", type=int, default=MIN_SAMPLES, help=f"timed samples (at least {MIN_SAMPLES} at N=1)")
+    ap.add_argument("--samples", type=int, default=MIN_SAMPLES,
+                    help=f"at most this many timed samples, each of at least {STEPS_PER_SAMPLE} of the --steps frames")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, the N>1 step's legs one by one and the secondary legs under 'extra'")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--config", type=int, default=None,
                     help="override the workload: 1 Box 1k | 2 DamagedHelmet 100k | 3 mixed 1M (N=1 default) | 4 mixed 10M (N>1 default)")
     ap.add_argument("--instances", type=int, default=None, help="override the TOTAL instance count")
     ap.add_argument("--all-visible", action="store_true", help="every instance inside the frustum (worst-case writes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary legs reported under 'extra'")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the secondary legs reported under 'extra'")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--sharded-extras", action="store_true",
                     help="N>1 only: also time the exchange with two frames in flight (two contexts on two streams). Off by default: a "
@@ -81,10 +92,17 @@ class DeviceOutputs:
                     draw_index_total=self.scalars.data_ptr() + 4)
 
 
-def event_samples(torch, step, steps, warmup, samples):
-    """`samples` samples of `steps` back-to-back steps between two HIP events recorded on torch's current stream
-    — the stream the context launches on. Returns the per-step times in ms (one per sample) and the wall-clock
-    per-step times of the same samples (host launch + synchronize included)."""
+def split_steps(steps, samples):
+    """The headline's `steps` timed steps as consecutive samples: at most `samples` of them, each of at least
+    STEPS_PER_SAMPLE steps (one sample of all the steps when there are fewer than two samples' worth)."""
+    k = max(1, min(samples, steps // STEPS_PER_SAMPLE))
+    return [steps // k + (1 if i < steps % k else 0) for i in range(k)]
+
+
+def event_samples(torch, step, batches, warmup):
+    """One sample per entry of `batches`: that many back-to-back steps between two HIP events recorded on torch's
+    current stream — the stream the context launches on. Returns the per-step times in ms (one per sample) and the
+    wall-clock per-step times of the same samples (host launch + synchronize included)."""
     # untimed warm-up: the W steps the caller asked for, and in any case about 50 ms of launches for the
     # GPU's clocks to settle — the first hundred samples after an idle period carry a slow tail otherwise
     # (p90 19.1 us against 18.6 once warm, same median: profiles/r02_sizes_final.txt)
@@ -95,7 +113,7 @@ def event_samples(torch, step, steps, warmup, samples):
         done += 200
         torch.cuda.synchronize()
     ev_ms, wall_ms = [], []
-    for _ in range(samples):
+    for steps in batches:
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
@@ -110,14 +128,14 @@ def event_samples(torch, step, steps, warmup, samples):
     return np.array(ev_ms), np.array(wall_ms)
 
 
-def barrier_samples(torch, dist, step, steps, warmup, samples, distributed):
-    """The contract's timed region, `samples` times: barrier + synchronize, EXACTLY `steps` steps, synchronize
-    (+ barrier); per sample the MAX over ranks. Returns per-step ms, one per sample."""
+def barrier_samples(torch, dist, step, batches, warmup, distributed):
+    """The contract's timed region, once per entry of `batches`: barrier + synchronize, EXACTLY that many steps,
+    synchronize (+ barrier); per sample the MAX over ranks. Returns per-step ms, one per sample."""
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
     local = []
-    for _ in range(samples):
+    for steps in batches:
         if distributed:
             dist.barrier()
         torch.cuda.synchronize()
@@ -131,12 +149,58 @@ def barrier_samples(torch, dist, step, steps, warmup, samples, distributed):
     t = torch.tensor(local, dtype=torch.float64, device="cuda")
     if distributed:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    return t.cpu().numpy() * 1e3 / steps
+    return t.cpu().numpy() * 1e3 / np.array(batches, dtype=np.float64)
 
 
 def stats(ms):
     return {"median": float(np.median(ms)), "mean": float(ms.mean()), "min": float(ms.min()), "p90": float(np.percentile(ms, 90)),
             "samples": int(len(ms))}
+
+
+# --dump-outputs: an output with more rows than its limit is written as a fixed seeded sample of its rows, beside the
+# row indices (<name>_rows.npy). At 1 M instances the model matrices alone are 64 MB; with these limits the files
+# stay under 47 MB at any size.
+OUTPUT_ROW_LIMITS = {"model": 1 << 16, "visible_bitmap": 1 << 20, "draw_cmds": 1 << 19}
+OUTPUT_BYTES_MAX = 64 * 10**6
+
+
+def sample_rows(n, limit):
+    """Sorted row indices of a seeded sample of `limit` of `n` rows; None when all rows fit."""
+    if n <= limit:
+        return None
+    return np.sort(np.random.default_rng(n).choice(n, limit, replace=False))
+
+
+def write_outputs(out_dir, outputs):
+    """outputs: name -> numpy array as the caller receives it. Floats are written as float32, integers exactly as
+    float64; rows beyond OUTPUT_ROW_LIMITS[name] are sampled (sample_rows)."""
+    files = {}
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype.kind in "iub" else np.float32)
+        rows = sample_rows(len(a), OUTPUT_ROW_LIMITS.get(name, len(a)))
+        if rows is not None:
+            a = a[rows]
+            files[name + "_rows"] = rows.astype(np.float64)
+        files[name] = a
+    total = sum(a.nbytes for a in files.values())
+    if total > OUTPUT_BYTES_MAX:
+        raise SystemExit(f"bench.py: the outputs are {total} bytes, more than {OUTPUT_BYTES_MAX}; nothing written")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def device_outputs(o, n, count, index_total, cmds=None):
+    """What a caller of the frame receives from DeviceOutputs `o` (n instances), on the host; `cmds` (count x 5)
+    stands in for o's command stream (the merged list of the N > 1 step)."""
+    return {
+        "model": o.model[:n].cpu().numpy(),
+        "visible_bitmap": o.bitmap[: (n + 31) // 32].cpu().numpy().view(np.uint32),
+        "draw_cmds": o.cmds[:count].cpu().numpy().view(np.uint32) if cmds is None else cmds,
+        "draw_count": np.array([count], np.uint32),
+        "draw_index_total": np.array([index_total], np.uint32),
+    }
 
 
 def kernel_source_sha():
@@ -248,19 +312,21 @@ def make_pipe(renderer_amd, s, local_rank, stream=None, frames=1, ordered_tiles=
     return p
 
 
-def serialized_leg(torch, renderer_amd, make_frame, s, device, local_rank, stream, steps, warmup, samples, ordered_tiles=False):
-    """SURVEY.md §8(d) on scene `s`: one frame in flight on `stream`, HIP-event samples."""
+def serialized_leg(torch, renderer_amd, make_frame, s, device, local_rank, stream, batches, warmup, ordered_tiles=False, dump_dir=None):
+    """SURVEY.md §8(d) on scene `s`: one frame in flight on `stream`, HIP-event samples (event_samples)."""
     n = s["n"]
     p = make_pipe(renderer_amd, s, local_rank, stream=stream, ordered_tiles=ordered_tiles)
     o = DeviceOutputs(torch, n, device)
     torch.cuda.synchronize()
     prepared = p.prepare_outputs(**o.kwargs())
     fref = p.frame_ref(make_frame(s["planes"], s["cam_pos"]))
-    ev, wall = event_samples(torch, lambda: p.run_prepared(fref, prepared), steps, warmup, samples)
+    ev, wall = event_samples(torch, lambda: p.run_prepared(fref, prepared), batches, warmup)
     p.wait()
-    count = int(o.scalars[0].item())
+    count, index_total = (int(x) & 0xFFFFFFFF for x in o.scalars[:2].cpu().tolist())
     bitmap = o.bitmap[: (n + 31) // 32].cpu().numpy().view(np.uint32)
     visible = int(np.unpackbits(bitmap.view(np.uint8)).sum())
+    if dump_dir is not None:
+        write_outputs(dump_dir, device_outputs(o, n, count, index_total))
     p.close()
     return {"n": n, "count": count, "visible": visible, "event_ms": ev, "wall_ms": wall}
 
@@ -365,7 +431,7 @@ def views_leg(torch, renderer_amd, scene, make_frame, s, device, local_rank, str
         outs.append(p.prepare_outputs(draw_cmds=cmds.data_ptr(), draw_count=scal.data_ptr(), draw_index_total=scal.data_ptr() + 4,
                                       visible_bitmap=bitmap.data_ptr()))
     torch.cuda.synchronize()
-    ev, wall = event_samples(torch, lambda: p.run_views(frames, outs), 20, 20, 30)
+    ev, wall = event_samples(torch, lambda: p.run_views(frames, outs), [20] * 30, 20)
     p.wait()
     counts = [int(k[1][0].item()) for k in keep]
     p.close()
@@ -682,7 +748,7 @@ def main():
     # come out: a watchdog prints it with what is there and ends the process with a NON-ZERO code (a process that
     # has given up on a GPU stall must not look like a clean run).
     watchdog = None
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         import threading
 
         def bail():
@@ -700,9 +766,9 @@ def main():
         watchdog.daemon = True
         watchdog.start()
 
-    if not args.no_extra and not distributed and args.config is None and args.instances is None and not args.all_visible:
+    if args.full and not args.no_extra and not distributed and args.config is None and args.instances is None and not args.all_visible:
         secondary_single(args, torch, renderer_amd, scene, make_frame, device, local_rank, stream, extra)
-    if not args.no_extra and distributed and args.config is None and args.instances is None and (args.sharded_extras or args.native_rccl_leg or world == 1):
+    if args.full and not args.no_extra and distributed and args.config is None and args.instances is None and (args.sharded_extras or args.native_rccl_leg or world == 1):
         secondary_sharded(args, torch, dist, renderer_amd, scene, make_frame, device, local_rank, rank, world, stream, extra)
 
     if extra:
@@ -722,8 +788,8 @@ def run_single(args, torch, renderer_amd, scene, make_frame, device, local_rank,
     cfg = scene.CONFIGS[config]
     n = args.instances if args.instances is not None else cfg["n"]
     s = scene.make_scene(config, n=n, all_visible=args.all_visible)
-    samples = max(args.samples, MIN_SAMPLES)
-    r = serialized_leg(torch, renderer_amd, make_frame, s, device, local_rank, stream, args.steps, args.warmup, samples)
+    r = serialized_leg(torch, renderer_amd, make_frame, s, device, local_rank, stream, split_steps(args.steps, args.samples), args.warmup,
+                       dump_dir=args.dump_outputs)
     ms = float(np.median(r["event_ms"]))
     v_emit = r["count"] / max(n, 1)
     result.update({
@@ -743,8 +809,9 @@ def run_single(args, torch, renderer_amd, scene, make_frame, device, local_rank,
             "host_loop": "python: one mip_run per step (direct launches on one stream, each ordered behind the previous one)",
             "outputs": "model[N] mat4 + visibility bitmap + compacted VkDrawIndexedIndirectCommand stream, HBM-resident",
         },
-        "timing": dict(stats(r["event_ms"]), method=f"HIP events on the launch stream around {args.steps} back-to-back steps per sample; "
-                                                      f"value = N / median sample", wall_clock_ms_per_step=stats(r["wall_ms"])),
+        "timing": dict(stats(r["event_ms"]), method=f"HIP events on the launch stream around each sample of back-to-back steps, "
+                                                      f"{args.steps} steps in all; ms_per_step = median over samples of a sample's time / "
+                                                      f"its steps; value = N / ms_per_step", wall_clock_ms_per_step=stats(r["wall_ms"])),
     })
     bytes_per_launch = n * algorithmic_bytes_per_instance(v_emit)
     achieved = bytes_per_launch / (ms * 1e-3) / 1e9
@@ -768,7 +835,7 @@ def run_single(args, torch, renderer_amd, scene, make_frame, device, local_rank,
         "note": "one launch = one step: kernel_ms is the median per-step time of the timed samples themselves; "
                 "profiles/ holds the rocprofv3 --kernel-trace --stats summary of the same command",
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(s, args.cpu_seconds)
 
 
@@ -783,13 +850,13 @@ def secondary_single(args, torch, renderer_amd, scene, make_frame, device, local
     s2 = scene.make_scene(2)
     guarded("frames_in_flight_2_1m", lambda: frames_in_flight_leg(torch, renderer_amd, make_frame, s3, device, local_rank, 2, 256))
     guarded("damaged_helmet_100k_serialized", lambda: leg_summary(serialized_leg(
-        torch, renderer_amd, make_frame, s2, device, local_rank, stream, args.steps, args.warmup, MIN_SAMPLES)))
+        torch, renderer_amd, make_frame, s2, device, local_rank, stream, [STEPS_PER_SAMPLE] * MIN_SAMPLES, args.warmup)))
     guarded("damaged_helmet_100k_frames_in_flight_2", lambda: frames_in_flight_leg(torch, renderer_amd, make_frame, s2, device, local_rank, 2, 1024))
     guarded("mixed_1m_all_visible_serialized", lambda: leg_summary(serialized_leg(
-        torch, renderer_amd, make_frame, scene.make_scene(3, all_visible=True), device, local_rank, stream, args.steps, args.warmup, MIN_SAMPLES)))
+        torch, renderer_amd, make_frame, scene.make_scene(3, all_visible=True), device, local_rank, stream, [STEPS_PER_SAMPLE] * MIN_SAMPLES, args.warmup)))
     def ten_million():
         # the honest HBM figure (the 1 M frame's 105 MB are helped by the memory-side cache): with the PMC traffic of the same kernel source at 10 M
-        row = leg_summary(serialized_leg(torch, renderer_amd, make_frame, scene.make_scene(4), device, local_rank, stream, 5, 5, 20))
+        row = leg_summary(serialized_leg(torch, renderer_amd, make_frame, scene.make_scene(4), device, local_rank, stream, [5] * 20, 5))
         pmc4, stale4 = pmc_traffic(4, scene.CONFIGS[4]["n"])
         row["algorithmic_bytes_per_launch"] = row["instances"] * algorithmic_bytes_per_instance(row["emitted_fraction"])
         row["traffic"] = pmc4["hbm_bytes_per_launch"] if pmc4 else None
@@ -802,11 +869,11 @@ def secondary_single(args, torch, renderer_amd, scene, make_frame, device, local
     # measure the one kernel there is, on a context created with the (now ignored) flag — so they can be read against round 3's
     # 25.45 / 7.55 us and against the default legs above.
     guarded("mixed_1m_ordered_tiles_serialized", lambda: dict(leg_summary(serialized_leg(
-        torch, renderer_amd, make_frame, s3, device, local_rank, stream, args.steps, args.warmup, MIN_SAMPLES, ordered_tiles=True)),
+        torch, renderer_amd, make_frame, s3, device, local_rank, stream, [STEPS_PER_SAMPLE] * MIN_SAMPLES, args.warmup, ordered_tiles=True)),
         note="MIP_CFG_ORDERED_TILES is accepted and ignored: this is the default kernel, which no longer depends on dispatch order "
              "(decoupled look-back with a fallback; round 3: three wait-free launches, 25.45 us)"))
     guarded("damaged_helmet_100k_ordered_tiles_serialized", lambda: dict(leg_summary(serialized_leg(
-        torch, renderer_amd, make_frame, s2, device, local_rank, stream, args.steps, args.warmup, MIN_SAMPLES, ordered_tiles=True)),
+        torch, renderer_amd, make_frame, s2, device, local_rank, stream, [STEPS_PER_SAMPLE] * MIN_SAMPLES, args.warmup, ordered_tiles=True)),
         note="as above (round 3: two launches, 7.55 us)"))
     guarded("mixed_1m_scrambled_dispatch", lambda: scrambled_dispatch_leg())
     guarded("zero_copy_semaphore_frame", lambda: semaphore_leg())
@@ -915,7 +982,7 @@ def merge_leg(torch, renderer_amd, scene, make_frame, device, local_rank, stream
         def step():
             p.merge_wire_lists(recv.data_ptr(), ranks, stride, merged.data_ptr(), oc.data_ptr(), chunk_capacity=cap, packed=(form == "packed"), async_=True)
 
-        ev, _ = event_samples(torch, step, 20, 20, 20)
+        ev, _ = event_samples(torch, step, [20] * 20, 20)
         p.wait()
         ms = float(np.median(ev))
         nbytes = ranks * count * per_cmd
@@ -945,7 +1012,7 @@ def run_sharded(args, torch, dist, renderer_amd, scene, make_frame, device, loca
     wire_env = os.environ.get("MIP_BENCH_WIRE", "2")
     ex = DrawListExchange(pipe, n_local, world, rank, device, wire={"0": False, "1": 1}.get(wire_env, True))
     def timed():
-        out = barrier_samples(torch, dist, lambda: ex.step(frame, outs), args.steps, args.warmup, samples, True)
+        out = barrier_samples(torch, dist, lambda: ex.step(frame, outs), split_steps(args.steps, samples), args.warmup, True)
         ex.complete()
         return out
 
@@ -961,6 +1028,9 @@ def run_sharded(args, torch, dist, renderer_amd, scene, make_frame, device, loca
     counts, _ = ex.counts()
     samples = max(10, min(args.samples, 30))
     ms = timed()
+    if args.dump_outputs and rank == 0:
+        cmds, total, index_total = ex.merged_draw_list()
+        write_outputs(args.dump_outputs, device_outputs(outs, n_local, total, index_total, cmds=cmds.view(np.uint32).reshape(-1, 5)))
     helps = torch.tensor([pipe.timings()["prefix_helps"]], dtype=torch.int64, device="cuda")
     dist.all_reduce(helps, op=dist.ReduceOp.MAX)
     med = float(np.median(ms))
@@ -990,20 +1060,21 @@ def run_sharded(args, torch, dist, renderer_amd, scene, make_frame, device, loca
             "host_loop": "python: kernel -> all_gather_into_tensor -> merge per step on one stream",
             "outputs": "per rank: its shard's model[] + bitmap; every rank: the merged global draw list",
         },
-        "timing": dict(stats(ms), method=f"barrier + synchronize around EXACTLY {args.steps} steps per sample, MAX over ranks per sample, "
-                                         f"value = N_total / median sample"),
+        "timing": dict(stats(ms), method=f"barrier + synchronize around each sample of back-to-back steps, {args.steps} steps in all, MAX "
+                                         f"over ranks per sample; ms_per_step = median over samples of a sample's time / its steps; "
+                                         f"value = N_total / ms_per_step"),
     })
 
-    if True:  # collective legs: every rank takes part, rank 0 reports
+    if args.full:  # collective legs: every rank takes part, rank 0 reports
         kw = outs.kwargs()
-        k_ms = barrier_samples(torch, dist, lambda: pipe.run_device(frame, async_=True, **kw), args.steps, args.warmup, 10, True)
+        k_ms = barrier_samples(torch, dist, lambda: pipe.run_device(frame, async_=True, **kw), [STEPS_PER_SAMPLE] * 10, args.warmup, True)
         pipe.wait()
-        g_ms = barrier_samples(torch, dist, lambda: dist.all_gather_into_tensor(ex.recv, ex.send), args.steps, 3, 10, True)
+        g_ms = barrier_samples(torch, dist, lambda: dist.all_gather_into_tensor(ex.recv, ex.send), [STEPS_PER_SAMPLE] * 10, 3, True)
         merge_fn = pipe.merge_wire_lists if ex.form else pipe.merge_draw_lists
         merge_kw = {"packed": True} if ex.form == 2 else {}
         m_ms = barrier_samples(torch, dist, lambda: merge_fn(ex.recv.data_ptr(), world, ex.stride, ex.merged.data_ptr(),
                                                              ex.merged_count.data_ptr(), async_=True, chunk_capacity=ex.capacity, **merge_kw),
-                               args.steps, 3, 10, True)
+                               [STEPS_PER_SAMPLE] * 10, 3, True)
         pipe.wait()
         result["breakdown_ms_per_step"] = {
             "shard_kernel_only": float(np.median(k_ms)), "all_gather_only": float(np.median(g_ms)), "merge_only": float(np.median(m_ms)),
@@ -1024,23 +1095,23 @@ def run_sharded(args, torch, dist, renderer_amd, scene, make_frame, device, loca
             "note": "the shard kernel of rank 0 alone (wall clock incl. host launch); the step as a whole is bound by the all-gather over xGMI",
         }
     # the same 10 M scene on ONE GPU (rank 0), so that a reader can compute the strong-scaling speed-up
-    if not args.no_extra and args.instances is None:
+    if args.full and not args.no_extra and args.instances is None:
         dist.barrier()
         if rank == 0:
             try:
                 one = leg_summary(serialized_leg(torch, renderer_amd, make_frame, scene.make_scene(config, n=n_total), device, local_rank,
-                                                 stream, 5, 5, 20))
+                                                 stream, [5] * 20, 5))
                 extra["single_gpu_same_workload"] = one
             except Exception as e:  # noqa: BLE001
                 extra["single_gpu_same_workload"] = {"error": f"{type(e).__name__}: {e}"}
         dist.barrier()
     # the CPU restatement beside the GPU number on EVERY line (round 4 carried it at N = 1 only): rank 0 times a bounded sample of its
     # own shard's scene outside the timed region while the other ranks wait at the barrier
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(s, args.cpu_seconds)
         if world > 1:
             result["cpu_baseline"]["sample"] = f"rank 0's shard of the {n_total}-instance scene; " + str(result["cpu_baseline"].get("sample", ""))
-    elif rank == 0:
+    elif rank == 0 and args.full:
         result["cpu_baseline"] = None  # --no-cpu-baseline
     if world > 1:
         dist.barrier()
@@ -1068,7 +1139,7 @@ def secondary_sharded(args, torch, dist, renderer_amd, scene, make_frame, device
             px.step(f4, o4s)
         px.wait()
         px.tighten()
-        ms = barrier_samples(torch, dist, lambda: px.step(f4, o4s), max(args.steps, 4), 4, 10, True)
+        ms = barrier_samples(torch, dist, lambda: px.step(f4, o4s), [STEPS_PER_SAMPLE] * 10, 4, True)
         px.wait()
         row = {"frames_in_flight_2": {"instances_per_s": n_total / (float(np.median(ms)) * 1e-3), "ms_per_step": float(np.median(ms)),
                                       "note": "two contexts on two streams: frame k+1's kernel runs under frame k's all-gather"}}
@@ -1087,7 +1158,7 @@ def secondary_sharded(args, torch, dist, renderer_amd, scene, make_frame, device
                 pn.run_sharded(f4, merged.data_ptr(), mcount.data_ptr(), model=o4s[0].model.data_ptr(),
                                visible_bitmap=o4s[0].bitmap.data_ptr(), chunk_capacity=cap, async_=True)
 
-            ms = barrier_samples(torch, dist, native_step, max(args.steps, 4), 4, 10, True)
+            ms = barrier_samples(torch, dist, native_step, [STEPS_PER_SAMPLE] * 10, 4, True)
             pn.wait()
             row["native_rccl"] = {"instances_per_s": n_total / (float(np.median(ms)) * 1e-3), "ms_per_step": float(np.median(ms)),
                                   "commands_total": int(mcount[0].item())}

@@ -4,6 +4,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,6 +49,43 @@ def test_committed_bench_line_carries_the_contract_fields():
     r = line["roofline"]
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     assert line["cpu_baseline"]["kind"] == "port" and "unpinned" in line["parity"]
+
+
+def test_steps_sets_the_number_of_timed_steps():
+    for steps in (1, 5, 19, 20, 39, 40, 41, 999, 1000, 1001, 20_000):
+        batches = bench.split_steps(steps, 50)
+        assert sum(batches) == steps and 1 <= len(batches) <= 50
+        assert min(batches) >= min(steps, bench.STEPS_PER_SAMPLE) and max(batches) - min(batches) <= 1
+    assert bench.split_steps(1000, 50) == [20] * 50  # the batches the headline was always timed in
+
+
+def test_a_plain_run_measures_the_headline_only(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "10", "--warmup", "2"])
+    args = bench.parse_args()
+    assert not args.full and args.dump_outputs is None and args.steps == 10
+
+
+def test_dumped_outputs_are_exact_bounded_and_repeatable(tmp_path):
+    """--dump-outputs at the headline's size: float32 / float64 files only, integers exact, under 64 MB, and the model
+    rows sampled the same way on every run."""
+    n, count = 1_000_000, 268_553
+    rng = np.random.default_rng(1)
+    cmds = rng.integers(0, 2**32, size=(count, 5), dtype=np.uint32)
+    outs = {"model": rng.standard_normal((n, 16)).astype(np.float32), "visible_bitmap": rng.integers(0, 2**32, (n + 31) // 32, dtype=np.uint32),
+            "draw_cmds": cmds, "draw_count": np.array([count], np.uint32), "draw_index_total": np.array([2**32 - 1], np.uint32)}
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), outs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.OUTPUT_BYTES_MAX
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f))
+        assert got[f[:-4]].dtype in (np.float32, np.float64), f
+    assert np.array_equal(got["draw_cmds"], cmds.astype(np.float64)) and got["draw_index_total"][0] == 2**32 - 1
+    rows = got["model_rows"].astype(np.int64)
+    assert len(rows) == bench.OUTPUT_ROW_LIMITS["model"] and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["model"], outs["model"][rows])
 
 
 def _run_bench(argv, env_extra, drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "MIP_BENCH_FORCE_DIST")):
