@@ -374,6 +374,71 @@ int32_t mip_run_skinned(MipContext* ctx, const MipFrame* frame, const MipOutputs
 #define MIP_MAX_VIEWS 16
 int32_t mip_run_views(MipContext* ctx, const MipFrame* frames, const MipOutputs* outs, uint32_t n_views);
 
+/* ---- Extension: occlusion culling against a depth pyramid (Hi-Z), one and two phases -----------------
+ * NOT a reference behaviour: farnoy/renderer renders a depth prepass (DepthRT: D16_UNORM, cleared to 1.0,
+ * compare LESS_OR_EQUAL, viewport flipped to y = H, height = -H; src/renderer/systems/depth_pass.rs) but
+ * culls nothing against it. Specified here and checked against this repository's own restatement
+ * (tests/occlusion_restatement.py) only.
+ *
+ * PYRAMID (mip_build_depth_pyramid): f32, row-major, levels one after another, level 0 first. Level 0 is
+ * ceil(W/2) x ceil(H/2); level k+1 is ceil of half of level k, down to 1 x 1. Texel (x, y) of level k is
+ * the max of the depth pixels (px, py) with px >> (k+1) == x and py >> (k+1) == y. A u16 value v counts
+ * as (float)v / 65535.0f (correctly rounded), a NaN f32 pixel as 1.0f, and a zero texel is +0.0f: max is
+ * exact, so the pyramid is bit-exact whatever the reduction order. mip_depth_pyramid_bytes gives its size.
+ * `depth` and `pyramid` are DEVICE pointers of the context's GPU; row_pitch_bytes is a multiple of the
+ * element size and at least W of them. The build is enqueued on the stream of the frame slot the context's
+ * next mip_run / mip_run_occluded will use, so that run is ordered after it without a wait. async == 0:
+ * returns when the pyramid is complete.
+ *
+ * OCCLUSION TEST (evaluated with contraction off). An instance is OCCLUDED when it passes the frustum
+ * test, is a candidate (its bit in `candidates` is set, or clear under MIP_OCC_CANDIDATES_INVERTED; every
+ * instance when `candidates` is NULL, which INVERTED does not go with) and fails this test:
+ *   1. corner c (0..7) of its world AABB (what world_aabb receives) takes max on x if c&1, on y if c&2, on z if c&4;
+ *   2. clip = ((m0*x + m4*y) + m8*z) + m12 per row, m = pv;
+ *   3. any clip coordinate non-finite, or any w <= 0: NOT occluded;
+ *   4. r = 1.0f / w (correctly rounded), ndc = clip.xyz * r;
+ *   5. u = (ndc.x*0.5f + 0.5f) * W, v = (0.5f - ndc.y*0.5f) * H   (the flipped viewport);
+ *   6. x0..x1 = floor(min u), floor(max u) over the corners clamped to [0, W-1], y0..y1 the same on v, H;
+ *   7. k = the smallest level with (x1>>(k+1)) - (x0>>(k+1)) <= 1 and the same for y;
+ *   8. d = max of the (at most 4) level-k texels covering the rectangle;
+ *   9. occluded iff d < 1.0f and min over corners of ndc.z > d (a texel at 1.0 — cleared — never occludes).
+ *
+ * mip_run_occluded: every output of MipOutputs is exactly what mip_run gives for the same scene in which
+ * every non-candidate and every occluded instance had been frustum-culled — visible_bitmap, draw_cmds /
+ * draw_count / draw_index_total (firstIndex sums what is emitted), culled_index_buffer (the per-triangle
+ * stage runs over the emitted list); model, world_aabb and tlas_instances are written for every instance.
+ * occluded_bitmap (optional) bit i is set iff instance i passed the frustum test, was a candidate and is
+ * occluded. `candidates` and `occluded_bitmap` need MIP_OUT_DEVICE. Not with MIP_OUT_WIRE; skinned
+ * instances, views, shards and mip_run_many are out of scope.
+ *
+ * TWO PHASES, composed by the caller:
+ *   phase 1  candidates = last frame's visible_bitmap, pyramid = last frame's; draw; rebuild the pyramid
+ *            from the new depth (mip_build_depth_pyramid);
+ *   phase 2  candidates = phase 1's visible_bitmap with MIP_OCC_CANDIDATES_INVERTED, the new pyramid; draw
+ *            with its own draw list and its own culled-index region.
+ * The union of the two phases' bitmaps is the next frame's phase-1 candidate set. */
+#define MIP_DEPTH_UNORM16 0u /* D16_UNORM, the reference's DepthRT */
+#define MIP_DEPTH_FLOAT32 1u /* D32_SFLOAT */
+#define MIP_MAX_DEPTH_EXTENT 16384u
+#define MIP_OCC_CANDIDATES_INVERTED 0x1u
+
+/* Bytes of the pyramid of a W x H depth image (pure, no device); 0 if a side is 0 or above MIP_MAX_DEPTH_EXTENT. */
+uint64_t mip_depth_pyramid_bytes(uint32_t width, uint32_t height);
+int32_t mip_build_depth_pyramid(MipContext* ctx, const void* depth, uint32_t width, uint32_t height,
+                                uint32_t row_pitch_bytes, uint32_t format, void* pyramid, int32_t async);
+
+typedef struct MipOcclusion {
+  uint32_t struct_size;         /* = sizeof(MipOcclusion) */
+  uint32_t width, height;       /* of the depth image the pyramid was built from */
+  uint32_t flags;               /* MIP_OCC_* */
+  const void* pyramid;          /* DEVICE, built by mip_build_depth_pyramid */
+  const uint32_t* candidates;   /* optional DEVICE bitmap, ceil(N/32) words; NULL = every instance */
+  uint32_t* occluded_bitmap;    /* optional DEVICE output, ceil(N/32) words */
+  float pv[16];                 /* projection * view the depth was rendered with, column-major */
+} MipOcclusion;                 /* 104 B */
+
+int32_t mip_run_occluded(MipContext* ctx, const MipFrame* frame, const MipOcclusion* occ, const MipOutputs* out);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every

@@ -127,6 +127,7 @@ void free_all(MipContext* ctx) {
     (void)hipFree(sl.d_chunk_first);
     (void)hipFree(sl.d_chunk_status);
     (void)hipFree(sl.d_skin_box);
+    (void)hipFree(sl.d_pyramid_counter);
     (void)hipFree(sl.d_frame_ring);
     if (sl.h_frame_stage) (void)hipHostFree(sl.h_frame_stage);
     for (auto& e : sl.stage_free)

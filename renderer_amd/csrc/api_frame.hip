@@ -218,7 +218,7 @@ void drop_graphs(MipContext* ctx) {
 
 // One frame on the next frame slot. Every decision is in `plan` (frame_plan.hpp); what is left here is the order of
 // the launches and the bookkeeping of the slot's prefix state.
-int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out, bool skinned, void* palette) {
+int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out, bool skinned, void* palette, const MipOcclusion* occ) {
   mip::LaunchPlan plan;
   if (int32_t rc = plan_for(ctx, frame, out, skinned, &plan)) return rc;
   if (int32_t rc = bind_device(ctx)) return rc;
@@ -240,7 +240,7 @@ int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out,
   mip::KernelArgs a{};
   fill_kernel_args(ctx, sl, frame, out, device_out, a);
   a.group_shift = plan.group_shift;
-  if (plan.uses_prefix_state) a.first_mover_rule = first_mover_rule_now(ctx);
+  if (plan.uses_prefix_state && !occ) a.first_mover_rule = first_mover_rule_now(ctx);  // (the occluded kernel does not follow the rule)
   if (plan.need_tri_scratch) {
     // the instance kernel emits into the slot's scratch list; the triangle stage rewrites
     // indexCount there and the final compaction lands in the caller's buffers
@@ -295,7 +295,10 @@ int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out,
       mip::launch_skinned_bounds(plan.skin_blocks, stream, k);
       MIP_HIP(ctx, hipGetLastError());
     }
-    {
+    if (occ) {
+      if (plan.general) ctx->timings.general_launches += 1;
+      if (int32_t rc = launch_occluded_frame(ctx, occ, a, plan, stream)) return rc;
+    } else {
       mip::FrameKernelParams params(a);
       if (plan.general) ctx->timings.general_launches += 1;
       MIP_HIP(ctx, hipLaunchKernel((const void*)frame_kernel_of(plan, a.first_mover_rule == 1u), dim3(plan.n_tiles), dim3(mip::kTile), params.p, ctx->lds_pad, stream));

@@ -3,6 +3,7 @@
 //   api_frame.hip     one frame: plan (frame_plan.hpp) -> launches; recorded launch graphs; views; light lists; mip_wait
 //   api_sharded.hip   shard merges, the collective-library seam, mip_run_sharded and its collective repair
 //   api_interop.hip   external memory and external semaphores (row f-2)
+//   api_occlusion.hip the occlusion-culling extension: depth pyramid builds, mip_run_occluded (occlusion_kernel.hpp)
 // (round 3 had all of it in one 2 224-line mip_api.hip)
 #pragma once
 
@@ -58,6 +59,7 @@ struct MipContext {
     uint32_t* d_tri_order = nullptr;         // large frames: command numbers by descending size class
     uint32_t* d_tri_sort = nullptr;          //               kSortWords words: histogram, positions, tickets (triangle_kernels.hpp)
     float* d_skin_box = nullptr;             // skinned frames: per instance posed mesh-space box {min xyz, -, max xyz, -}
+    uint32_t* d_pyramid_counter = nullptr;   // depth pyramid builds on this slot's stream: workgroups done (the last one resets it)
     // recorded launches (mip_run_many): the frames of one replay, read by the kernels (KernelArgs.frame_ring),
     // refreshed before every replay from one of two pinned staging halves
     uint32_t* d_frame_ring = nullptr;
@@ -232,6 +234,9 @@ int32_t repair_sharded_overflow(MipContext* ctx);     // api_sharded.hip
 void comm_release(MipContext* ctx);                   // api_sharded.hip: communicator + buffers, for mip_destroy
 void interop_release(MipContext* ctx);                // api_interop.hip: imported memory and semaphores, for mip_destroy
 int32_t interop_drain(MipContext* ctx);                // api_interop.hip: every queued signal of an external semaphore has been performed (mip_wait)
-int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out, bool skinned, void* palette);  // api_frame.hip
+// occ != null: the occluded frame kernel (api_occlusion.hip, launch_occluded_frame) takes the frame kernel's place
+int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out, bool skinned, void* palette,
+                  const MipOcclusion* occ = nullptr);  // api_frame.hip
+int32_t launch_occluded_frame(MipContext* ctx, const MipOcclusion* occ, mip::KernelArgs& a, const mip::LaunchPlan& plan, hipStream_t stream);  // api_occlusion.hip
 
 }  // namespace mip_host

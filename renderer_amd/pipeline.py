@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import MipConfig, MipError, MipFrame, MipOutputs, MipShardedOutputs, MipTimings
+from ._lib import MipConfig, MipError, MipFrame, MipOcclusion, MipOutputs, MipShardedOutputs, MipTimings
 
 MESH_DTYPE = np.dtype(
     [
@@ -52,6 +52,41 @@ def wire_body_bytes(capacity, packed=False):
     per = _lib.MIP_WIRE_PACKED_BLOCK_COMMANDS if packed else _lib.MIP_WIRE_BLOCK_COMMANDS
     blocks = (int(capacity) + per - 1) // per
     return blocks * (_lib.MIP_WIRE_PACKED_BLOCK_BYTES if packed else _lib.MIP_WIRE_BLOCK_BYTES)
+
+
+def depth_pyramid_layout(width, height):
+    """mip_depth_pyramid_bytes as a pure mirror (the occlusion-culling extension): the pyramid of a W x H depth image is f32,
+    row-major, level 0 = ceil(W/2) x ceil(H/2), each next level ceil of half the last, down to 1 x 1, stored level 0 first.
+    Returns {"sizes": [(w, h), ...], "offsets": [float offset of each level], "bytes": total}; bytes = 0 (no levels) when a
+    side is 0 or above MIP_MAX_DEPTH_EXTENT."""
+    width, height = int(width), int(height)
+    if not (1 <= width <= _lib.MIP_MAX_DEPTH_EXTENT and 1 <= height <= _lib.MIP_MAX_DEPTH_EXTENT):
+        return {"sizes": [], "offsets": [], "bytes": 0}
+    sizes, offsets, floats = [], [], 0
+    k = 0
+    while True:
+        w, h = ((width - 1) >> (k + 1)) + 1, ((height - 1) >> (k + 1)) + 1
+        sizes.append((w, h))
+        offsets.append(floats)
+        floats += w * h
+        if w == 1 and h == 1:
+            break
+        k += 1
+    return {"sizes": sizes, "offsets": offsets, "bytes": floats * 4}
+
+
+def make_occlusion(width, height, pyramid_ptr, pv, candidates=0, occluded_bitmap=0, inverted=False):
+    """A MipOcclusion: the pyramid (device pointer) of a width x height depth image rendered with `pv` (column-major 16 floats);
+    optional device bitmaps of candidates and of the occluded instances."""
+    o = MipOcclusion()
+    o.struct_size = C.sizeof(MipOcclusion)
+    o.width, o.height = int(width), int(height)
+    o.flags = _lib.MIP_OCC_CANDIDATES_INVERTED if inverted else 0
+    o.pyramid = pyramid_ptr or None
+    o.candidates = candidates or None
+    o.occluded_bitmap = occluded_bitmap or None
+    o.pv[:] = np.ascontiguousarray(pv, dtype=np.float32).reshape(16).tolist()
+    return o
 
 
 def make_frame(planes, cam_pos, first_instance_base=0, first_index_base=0, pv=None):
@@ -386,6 +421,22 @@ class InstancePipeline:
         lights = np.ascontiguousarray(light_pos_xyz, dtype=np.float32).reshape(-1, 3)
         self._check(self._lib.mip_light_draw_lists(self._ctx, lights.ctypes.data, len(lights), int(first_instance_base),
                                                    out_cmds_ptr, 1 if async_ else 0))
+
+    # -- occlusion culling (extension) --
+    def build_depth_pyramid(self, depth_ptr, width, height, pyramid_ptr, row_pitch_bytes=None, format=_lib.MIP_DEPTH_UNORM16,
+                            async_=False):
+        """The max pyramid of a device depth image (D16_UNORM or D32_SFLOAT) into device memory of
+        depth_pyramid_layout(width, height)["bytes"], on the stream the next run / run_occluded will use."""
+        if row_pitch_bytes is None:
+            row_pitch_bytes = int(width) * (2 if format == _lib.MIP_DEPTH_UNORM16 else 4)
+        self._check(self._lib.mip_build_depth_pyramid(self._ctx, depth_ptr or None, int(width), int(height), int(row_pitch_bytes),
+                                                      int(format), pyramid_ptr or None, 1 if async_ else 0))
+
+    def run_occluded(self, frame, occlusion, outputs):
+        """mip_run_occluded: `frame` from make_frame, `occlusion` from make_occlusion, `outputs` a MipOutputs (prepare_outputs, or
+        one built by hand): every output as mip_run gives it for the scene in which the non-candidates and the occluded instances
+        had been frustum-culled."""
+        self._check(self._lib.mip_run_occluded(self._ctx, C.addressof(frame), C.addressof(occlusion), C.addressof(outputs)))
 
     # -- diagnostics --
     def timings(self):
