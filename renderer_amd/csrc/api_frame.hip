@@ -122,10 +122,6 @@ void fill_kernel_args(MipContext* ctx, MipContext::FrameSlot& sl, const MipFrame
   std::memcpy(a.planes, frame->planes, sizeof a.planes);
   std::memcpy(a.cam, frame->cam_pos, sizeof a.cam);
   a.n_tiles = tiles_for(n);
-#ifdef MIP_EXP_FAKE_DELAY
-  a.delay_first = std::getenv("MIP_TUNE_DELAY_FIRST") ? (uint32_t)std::atoi(std::getenv("MIP_TUNE_DELAY_FIRST")) : 0u;
-  a.delay_last = std::getenv("MIP_TUNE_DELAY_LAST") ? (uint32_t)std::atoi(std::getenv("MIP_TUNE_DELAY_LAST")) : 0xffffffffu;
-#endif
   a.group_shift = a.n_tiles <= 512 ? 4u : (a.n_tiles <= 2048 ? 5u : 6u);
 #ifdef MIP_DEBUG_STAMPS
   a.stamps = ctx->d_stamps;

@@ -64,6 +64,17 @@ struct alignas(16) MeshEntry {
   uint32_t len1;
 };
 
+// A mesh entry from its two 16-B halves, and its gather from the mesh table.
+__device__ __forceinline__ MeshEntry mesh_entry(float4 mb0, float4 mb1) {
+  MeshEntry mb;
+  mb.min_x = mb0.x; mb.min_y = mb0.y; mb.min_z = mb0.z; mb.len0 = __float_as_uint(mb0.w);
+  mb.max_x = mb1.x; mb.max_y = mb1.y; mb.max_z = mb1.z; mb.len1 = __float_as_uint(mb1.w);
+  return mb;
+}
+__device__ __forceinline__ MeshEntry load_mesh_entry(const MeshEntry* meshes, uint32_t mesh) {
+  return mesh_entry(*reinterpret_cast<const float4*>(&meshes[mesh].min_x), *reinterpret_cast<const float4*>(&meshes[mesh].max_x));
+}
+
 // Per-mesh draw data, one 16-B gather for the lanes that emit a command.
 struct alignas(16) MeshDraw {
   int32_t vertex_offset;  // ConsolidatedMeshBuffers.vertex_offsets[mesh]
@@ -128,9 +139,6 @@ struct KernelArgs {
   uint32_t* help_counter;       // DEVICE memory: tile aggregates that waiting tiles computed themselves (MipTimings.prefix_helps), kHelpShards words
   uint32_t* helps_seen;         // DEVICE memory, one word beside the prefix state: the help count the last launch that looked saw
   uint32_t* help_hint;          // host-mapped word (or null: nobody is told): note_helps_for_the_host
-#ifdef MIP_EXP_FAKE_DELAY
-  uint32_t delay_first, delay_last;  // tuning builds: tiles in [first, last) idle in place of the look-up
-#endif
 #ifdef MIP_DEBUG_STAMPS
   unsigned long long* stamps;  // diagnostic build only: 8 realtime stamps per tile
   uint32_t debug_skip_publish_tile;  // diagnostic build only: tile index + 1 that never publishes (0 = off)
@@ -924,6 +932,113 @@ __device__ __forceinline__ void wire_packed_copy_out(uint32_t* body, const uint3
   }
 }
 
+// ---- the tile's tail, shared by the frame kernel's two orders and the occluded frame kernel (occlusion_kernel.hpp). They take
+//      the argument block by reference and read its fields where the kernel's own code did: a field passed by value is read
+//      earlier, and that moved instructions of the frame kernel. (The wave offsets, the matrix staging and the prefix look-up
+//      stay written out in each kernel: as helpers they changed the frame kernel's gfx950 instruction mix.) ----
+
+// One command, staged at `c` in LDS (kCmdLdsWords; firstIndex still relative to the tile).
+template <int kWire, class A>
+__device__ __forceinline__ void stage_command(const A& a, uint32_t* c, uint32_t len, uint32_t first_index, int32_t vertex_offset,
+                                              uint32_t first_instance, uint32_t mesh, bool far_lod) {
+  c[0] = len;                                               // indexCount
+  c[1] = 1u;                                                // instanceCount, generate_work.comp:63
+  c[2] = first_index;                                       // firstIndex (tile-relative)
+  c[3] = (uint32_t)vertex_offset;                           // vertexOffset, :66
+  c[4] = first_instance;                                    // firstInstance = draw_index, :64
+  if constexpr (kWire) c[5] = mesh | (far_lod ? 0x80000000u : 0u);  // wire form: the record's second word
+  else if (a.src_index_offset)                              // push constant indexOffset, cull_pipeline.rs:552 (per-triangle stage only)
+    c[5] = far_lod ? a.mesh_draw[mesh].src_offset1 : a.mesh_draw[mesh].src_offset0;
+}
+
+// Where the tile's 16 KiB of matrices (and TLAS rows) go: descriptors bounded at the last instance.
+struct PieceStores { __amdgpu_buffer_rsrc_t model, tlas; };
+template <class A>
+__device__ __forceinline__ PieceStores piece_stores(const A& a, uint32_t tile_first) {
+  const uint32_t tile_bytes = (a.n - tile_first < kTile ? a.n - tile_first : kTile) * 64u;
+  return {stream_descriptor(a.model ? a.model + (size_t)tile_first * 4 : nullptr, a.model ? tile_bytes : 0u),
+          stream_descriptor(a.tlas_instances ? a.tlas_instances + (size_t)tile_first * 4 : nullptr, a.tlas_instances ? tile_bytes : 0u)};
+}
+
+// One 1-KiB piece = 16 staged matrices (s_mat: rows 0..2, 48-B pitch; s_row3: NaN bits of row 3 + mesh id) -> one store
+// instruction of a wave (64 B per matrix, lane-contiguous 16-B stores). Piece p of the tile covers instances tile_first + 16 p ...
+template <bool kGeneral, class A>
+__device__ __forceinline__ void store_piece(const A& a, const PieceStores& d, const float* s_mat, const uint32_t* s_row3, uint32_t tile_first,
+                                            uint32_t first_instance_base, uint32_t lane, uint32_t p) {
+  const uint32_t local = 16u * p + (lane >> 2);  // matrix within the tile
+  const uint32_t col = lane & 3u;
+  const float* src = &s_mat[local * 12u];
+  const bool in_range = tile_first + local < a.n;
+  if (a.model) {
+    float w = (col == 3u) ? 1.0f : 0.0f;
+    if constexpr (kGeneral) {
+      const uint32_t bits = s_row3[local] & 15u;
+      if ((bits >> col) & 1u) w = __uint_as_float(0x7fc00000u);
+    }
+    store_stream16(d.model, (64u * p + lane) * 16u, make_float4(src[3u * col], src[3u * col + 1u], src[3u * col + 2u], w));
+  }
+  // optional TLAS instance rows (acceleration_strucures.rs:419-451), same transposed store:
+  // VkAccelerationStructureInstanceKHR = { 3x4 row-major transform = rows 0..2 of M,
+  //   instanceCustomIndex:24 = draw_index | mask:8 = 0xFF, sbtOffset:24 = 0 | flags:8 =
+  //   TRIANGLE_FACING_CULL_DISABLE, BLAS device address }, for EVERY instance (visible or not).
+  if (a.tlas_instances) {
+    const uint32_t draw = tile_first + local;
+    uint4 v;
+    if (col < 3u) {  // row `col`: one element of each staged column
+      v = make_uint4(__float_as_uint(src[col]), __float_as_uint(src[col + 3u]), __float_as_uint(src[col + 6u]), __float_as_uint(src[col + 9u]));
+    } else {
+      const uint32_t mesh_of = s_row3[local] >> 4;
+      const unsigned long long blas = (in_range && a.blas_address) ? a.blas_address[mesh_of] : 0ull;
+      v = make_uint4(((first_instance_base + draw) & 0xffffffu) | 0xff000000u, 0x01000000u,
+                     (uint32_t)blas, (uint32_t)(blas >> 32));
+    }
+    store_stream16(d.tlas, (64u * p + lane) * 16u, make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)));
+  }
+}
+
+// optional world AABB (mins, maxs) of instance i as the ECS component holds it: 24 B per lane
+template <class A>
+__device__ __forceinline__ void store_world_aabb(const A& a, uint32_t i, bool active, const Instance& inst) {
+  if (a.world_aabb && active) {
+    float2* o2 = reinterpret_cast<float2*>(a.world_aabb + (size_t)i * 6);
+    o2[0] = make_float2(inst.mins[0], inst.mins[1]);
+    o2[1] = make_float2(inst.mins[2], inst.maxs[0]);
+    o2[2] = make_float2(inst.maxs[1], inst.maxs[2]);
+  }
+}
+
+// a bitmap's words of the tile (one per 32 instances, from the waves' ballots in LDS), one store instruction
+__device__ __forceinline__ void store_tile_bitmap(uint32_t* bitmap, uint32_t bitmap_words, const unsigned long long* s_masks,
+                                                  uint32_t tile_first, uint32_t lane) {
+  if (bitmap && lane < 2u * kWaves) {
+    const uint32_t word = (tile_first >> 5) + lane;
+    if (word < bitmap_words) bitmap[word] = (uint32_t)(s_masks[lane >> 1] >> (32u * (lane & 1u)));
+  }
+}
+
+// Coalesced copy-out of the tile's staged commands at list position base_count: 20-byte commands (and the per-triangle
+// stage's source offsets), or a wire form (kWire, as the frame kernel's template parameter). Run by one wave.
+template <int kWire, class A>
+__device__ __forceinline__ void copy_out_tile(const A& a, const uint32_t* s_cmd, uint32_t lane, uint32_t base_count, uint32_t first_index_add,
+                                              uint32_t tile_count, uint32_t first_instance_base) {
+  if constexpr (kWire == 2) {
+    wire_packed_copy_out(a.cmds, s_cmd, lane, base_count, first_index_add, tile_count, first_instance_base, a.wire_index_bits);
+  } else if constexpr (kWire == 1) {
+    wire_copy_out(a.cmds, s_cmd, lane, base_count, first_index_add, tile_count);
+  } else {
+    uint32_t* out = a.cmds + (size_t)base_count * kCmdWords;
+    const uint32_t words = tile_count * kCmdWords;
+    for (uint32_t j = lane; j < words; j += 64u) {
+      const uint32_t k = j / kCmdWords, f = j - k * kCmdWords;
+      uint32_t v = s_cmd[k * kCmdLdsWords + f];
+      if (f == 2u) v += first_index_add;
+      out[j] = v;
+    }
+    if (a.src_index_offset)
+      for (uint32_t k = lane; k < tile_count; k += 64u) a.src_index_offset[base_count + k] = s_cmd[k * kCmdLdsWords + 5u];
+  }
+}
+
 // Model matrix + world box of one instance in the arithmetic tier its WAVE takes (kGeneral) or the separable fold
 // (census-selected launches). Shared by the owner of a tile and by a wave that computes the tile's aggregate in its
 // place (help_tile_aggregate): same loads, same functions, same tier decision per 64 consecutive instances.
@@ -1020,11 +1135,7 @@ __device__ __forceinline__ unsigned long long help_tile_aggregate(uint32_t u, ui
     const float4 q = rot[jl];
     const float sc = scale[jl];
     const uint32_t mesh = mesh_id[jl];
-    const float4 mb0 = *reinterpret_cast<const float4*>(&meshes[mesh].min_x);
-    const float4 mb1 = *reinterpret_cast<const float4*>(&meshes[mesh].max_x);
-    MeshEntry mb;
-    mb.min_x = mb0.x; mb.min_y = mb0.y; mb.min_z = mb0.z; mb.len0 = __float_as_uint(mb0.w);
-    mb.max_x = mb1.x; mb.max_y = mb1.y; mb.max_z = mb1.z; mb.len1 = __float_as_uint(mb1.w);
+    MeshEntry mb = load_mesh_entry(meshes, mesh);
     float r[3][3];
     quat_to_rotation(q.x, q.y, q.z, q.w, r);
     Instance inst;
@@ -1173,9 +1284,7 @@ __global__ __launch_bounds__(kTile, kGeneral ? MIP_MIN_WAVES_PER_SIMD : 8) void 
   const bool marks = first_mover_rule && want_cmds && tid == 63u && !skip_publish;  // (a lane that publishes for wave 0)
   if constexpr (first_mover_rule)
     if (want_cmds) granule_before = mark_tile_started_issue(a, tile, marks);
-  MeshEntry mb;
-  mb.min_x = mb0.x; mb.min_y = mb0.y; mb.min_z = mb0.z; mb.len0 = __float_as_uint(mb0.w);
-  mb.max_x = mb1.x; mb.max_y = mb1.y; mb.max_z = mb1.z; mb.len1 = __float_as_uint(mb1.w);
+  MeshEntry mb = mesh_entry(mb0, mb1);
 
   // ---- model matrix + world AABB ----
   float r[3][3];
@@ -1219,69 +1328,19 @@ __global__ __launch_bounds__(kTile, kGeneral ? MIP_MIN_WAVES_PER_SIMD : 8) void 
     bool publish = ((uint32_t)all >> kAggArrivalShift) == kWaves && !skip_publish;
     if (publish) publish_aggregate(a, tile, (uint32_t)all & 0xffffu, (uint32_t)(all >> 32), !((uint32_t)all & kAggHelpedFirst));
   }
-  // ---- stage the matrix rows for the transposed store (three conflict-free ds_write_b128, 48-B pitch) ----
   if (a.model || a.tlas_instances) {
     float4* dst = reinterpret_cast<float4*>(&s_mat[tid * 12]);
     dst[0] = make_float4(inst.m[0], inst.m[1], inst.m[2], inst.m[3]);
     dst[1] = make_float4(inst.m[4], inst.m[5], inst.m[6], inst.m[7]);
     dst[2] = make_float4(inst.m[8], inst.m[9], inst.m[10], inst.m[11]);
-    s_row3[tid] = inst.row3 | (mesh << 4);  // NaN bits of row 3 + the mesh id (for the TLAS rows)
+    s_row3[tid] = inst.row3 | (mesh << 4);
   }
   if (lane == 0u) s_vis[wave] = vis_mask;
 
-  // One 1-KiB piece = 16 staged matrices -> one store instruction of a wave (64 B per matrix,
-  // lane-contiguous 16-B stores). Piece p of the tile covers instances tile_first + 16 p ...
-  // descriptors of this tile's 16 KiB of matrices (and TLAS rows): bounded at the last instance
-  const uint32_t tile_bytes = (a.n - tile_first < kTile ? a.n - tile_first : kTile) * 64u;
-  const __amdgpu_buffer_rsrc_t d_model = stream_descriptor(a.model ? a.model + (size_t)tile_first * 4 : nullptr, a.model ? tile_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t d_tlas = stream_descriptor(a.tlas_instances ? a.tlas_instances + (size_t)tile_first * 4 : nullptr, a.tlas_instances ? tile_bytes : 0u);
-  auto store_piece = [&](uint32_t p) {
-    const uint32_t local = 16u * p + (lane >> 2);  // matrix within the tile
-    const uint32_t col = lane & 3u;
-    const float* src = &s_mat[local * 12u];
-    const bool in_range = tile_first + local < a.n;
-    if (a.model) {
-      float w = (col == 3u) ? 1.0f : 0.0f;
-      if constexpr (kGeneral) {
-        const uint32_t bits = s_row3[local] & 15u;
-        if ((bits >> col) & 1u) w = __uint_as_float(0x7fc00000u);
-      }
-      store_stream16(d_model, (64u * p + lane) * 16u, make_float4(src[3u * col], src[3u * col + 1u], src[3u * col + 2u], w));
-    }
-    // optional TLAS instance rows (acceleration_strucures.rs:419-451), same transposed store:
-    // VkAccelerationStructureInstanceKHR = { 3x4 row-major transform = rows 0..2 of M,
-    //   instanceCustomIndex:24 = draw_index | mask:8 = 0xFF, sbtOffset:24 = 0 | flags:8 =
-    //   TRIANGLE_FACING_CULL_DISABLE, BLAS device address }, for EVERY instance (visible or not).
-    if (a.tlas_instances) {
-      const uint32_t draw = tile_first + local;
-      uint4 v;
-      if (col < 3u) {  // row `col`: one element of each staged column
-        v = make_uint4(__float_as_uint(src[col]), __float_as_uint(src[col + 3u]), __float_as_uint(src[col + 6u]), __float_as_uint(src[col + 9u]));
-      } else {
-        const uint32_t mesh_of = s_row3[local] >> 4;
-        const unsigned long long blas = (in_range && a.blas_address) ? a.blas_address[mesh_of] : 0ull;
-        v = make_uint4(((first_instance_base + draw) & 0xffffffu) | 0xff000000u, 0x01000000u,
-                       (uint32_t)blas, (uint32_t)(blas >> 32));
-      }
-      store_stream16(d_tlas, (64u * p + lane) * 16u, make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)));
-    }
-  };
-  // optional world AABB (mins, maxs) as the ECS component holds it: 24 B per lane
-  auto store_aabb = [&]() {
-    if (a.world_aabb && active) {
-      float2* o2 = reinterpret_cast<float2*>(a.world_aabb + (size_t)i * 6);
-      o2[0] = make_float2(inst.mins[0], inst.mins[1]);
-      o2[1] = make_float2(inst.mins[2], inst.maxs[0]);
-      o2[2] = make_float2(inst.maxs[1], inst.maxs[2]);
-    }
-  };
-  // visibility bitmap: the tile's eight words, one store instruction
-  auto store_bitmap = [&]() {
-    if (a.bitmap && lane < 2u * kWaves) {
-      const uint32_t word = (tile_first >> 5) + lane;
-      if (word < a.bitmap_words) a.bitmap[word] = (uint32_t)(s_vis[lane >> 1] >> (32u * (lane & 1u)));
-    }
-  };
+  const PieceStores d = piece_stores(a, tile_first);
+  auto store_piece = [&](uint32_t p) { mip::store_piece<kGeneral>(a, d, s_mat, s_row3, tile_first, first_instance_base, lane, p); };
+  auto store_aabb = [&]() { store_world_aabb(a, i, active, inst); };
+  auto store_bitmap = [&]() { store_tile_bitmap(a.bitmap, a.bitmap_words, s_vis, tile_first, lane); };
 
   if constexpr (kOrder == 1) {
     auto own_stores = [&]() {
@@ -1312,11 +1371,9 @@ __global__ __launch_bounds__(kTile, kGeneral ? MIP_MIN_WAVES_PER_SIMD : 8) void 
     }
     __syncthreads();  // waves 1-3 have read their staged matrices: their area is free for the commands
     if (keep) {
-      uint32_t* c = &s_cmd[(wave_off_count + rank_in_wave) * kCmdLdsWords];
       vertex_offset_of_mesh = a.mesh_draw[mesh].vertex_offset;  // stores-first order: gathered by the emitting lanes only
-      c[0] = len; c[1] = 1u; c[2] = wave_off_sum + (incl_sum - len_vis); c[3] = (uint32_t)vertex_offset_of_mesh; c[4] = first_instance_base + i;
-      if constexpr (kWire) c[5] = mesh | (far_lod ? 0x80000000u : 0u);
-      else if (a.src_index_offset) c[5] = far_lod ? a.mesh_draw[mesh].src_offset1 : a.mesh_draw[mesh].src_offset0;
+      stage_command<kWire>(a, &s_cmd[(wave_off_count + rank_in_wave) * kCmdLdsWords], len, wave_off_sum + (incl_sum - len_vis),
+                           vertex_offset_of_mesh, first_instance_base + i, mesh, far_lod);
     }
     __syncthreads();
     MIP_STAMP(3);
@@ -1330,23 +1387,7 @@ __global__ __launch_bounds__(kTile, kGeneral ? MIP_MIN_WAVES_PER_SIMD : 8) void 
       if (a.index_total) *a.index_total = base_sum + tile_sum;
     }
     MIP_STAMP(4);
-    const uint32_t first_index_add = base_sum + first_index_base;
-    if constexpr (kWire) {
-      if constexpr (kWire == 2) wire_packed_copy_out(a.cmds, s_cmd, lane, base_count, first_index_add, tile_count, first_instance_base, a.wire_index_bits);
-      else wire_copy_out(a.cmds, s_cmd, lane, base_count, first_index_add, tile_count);
-      MIP_STAMP(5);
-      return;
-    }
-    uint32_t* out = a.cmds + (size_t)base_count * kCmdWords;
-    const uint32_t words = tile_count * kCmdWords;
-    for (uint32_t j = lane; j < words; j += 64u) {
-      const uint32_t k = j / kCmdWords, f = j - k * kCmdWords;
-      uint32_t v = s_cmd[k * kCmdLdsWords + f];
-      if (f == 2u) v += first_index_add;
-      out[j] = v;
-    }
-    if (a.src_index_offset)
-      for (uint32_t k = lane; k < tile_count; k += 64u) a.src_index_offset[base_count + k] = s_cmd[k * kCmdLdsWords + 5u];
+    copy_out_tile<kWire>(a, s_cmd, lane, base_count, base_sum + first_index_base, tile_count, first_instance_base);
     MIP_STAMP(5);
     return;
   }
@@ -1371,17 +1412,9 @@ __global__ __launch_bounds__(kTile, kGeneral ? MIP_MIN_WAVES_PER_SIMD : 8) void 
   }
 
   // ---- tile-local command assembly in LDS (firstIndex still relative to the tile) ----
-  if (keep) {
-    uint32_t* c = &s_cmd[(wave_off_count + rank_in_wave) * kCmdLdsWords];
-    c[0] = len;                                               // indexCount
-    c[1] = 1u;                                                // instanceCount, generate_work.comp:63
-    c[2] = wave_off_sum + (incl_sum - len_vis);               // firstIndex (tile-relative)
-    c[3] = (uint32_t)vertex_offset_of_mesh;                   // vertexOffset, :66
-    c[4] = first_instance_base + i;                         // firstInstance = draw_index, :64
-    if constexpr (kWire) c[5] = mesh | (far_lod ? 0x80000000u : 0u);  // wire form: the record's second word
-    else if (a.src_index_offset)                              // push constant indexOffset, cull_pipeline.rs:552 (per-triangle stage only)
-      c[5] = far_lod ? a.mesh_draw[mesh].src_offset1 : a.mesh_draw[mesh].src_offset0;
-  }
+  if (keep)
+    stage_command<kWire>(a, &s_cmd[(wave_off_count + rank_in_wave) * kCmdLdsWords], len, wave_off_sum + (incl_sum - len_vis),
+                         vertex_offset_of_mesh, first_instance_base + i, mesh, far_lod);
   __syncthreads();  // commands, staged matrices and visibility words of every wave are in LDS
   MIP_STAMP(3);
 
@@ -1398,45 +1431,17 @@ __global__ __launch_bounds__(kTile, kGeneral ? MIP_MIN_WAVES_PER_SIMD : 8) void 
     return;
   }
 
-  // ---- exclusive prefix over the earlier tiles ----
+  // ---- exclusive prefix over the earlier tiles, then the coalesced copy-out of the tile's commands ----
   store_aabb();  // (optional output) before the look-up: nothing of the instance lives across it
   uint32_t base_count = 0, base_sum = 0;
-#ifndef MIP_EXP_NO_HOP  // tuning builds only: what the kernel costs without the cross-tile look-up (results are wrong)
   if (tile > 0) resolve_prefix(a, tile, lane, base_count, base_sum, help, first_mover_rule);
   else note_helps_for_the_host(a, lane);
-#else
-  base_count = tile * 64u;
-#ifdef MIP_EXP_FAKE_DELAY  // idle for the time a look-up takes, without its memory traffic
-  if (tile >= a.delay_first && tile < a.delay_last) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (__builtin_amdgcn_s_memrealtime() - t0 < MIP_EXP_FAKE_DELAY) __builtin_amdgcn_s_sleep(8);
-  }
-#endif
-#endif
   if (lane == 0 && tile == a.n_tiles - 1u) {
     *a.draw_count = base_count + tile_count;
     if (a.index_total) *a.index_total = base_sum + tile_sum;
   }
   MIP_STAMP(4);
-
-  // ---- coalesced copy-out of the tile's commands ----
-  const uint32_t first_index_add = base_sum + first_index_base;
-  if constexpr (kWire) {
-    if constexpr (kWire == 2) wire_packed_copy_out(a.cmds, s_cmd, lane, base_count, first_index_add, tile_count, first_instance_base, a.wire_index_bits);
-    else wire_copy_out(a.cmds, s_cmd, lane, base_count, first_index_add, tile_count);
-    MIP_STAMP(5);
-    return;
-  }
-  uint32_t* out = a.cmds + (size_t)base_count * kCmdWords;
-  const uint32_t words = tile_count * kCmdWords;
-  for (uint32_t j = lane; j < words; j += 64u) {
-    const uint32_t k = j / kCmdWords, f = j - k * kCmdWords;
-    uint32_t v = s_cmd[k * kCmdLdsWords + f];
-    if (f == 2u) v += first_index_add;
-    out[j] = v;
-  }
-  if (a.src_index_offset)
-    for (uint32_t k = lane; k < tile_count; k += 64u) a.src_index_offset[base_count + k] = s_cmd[k * kCmdLdsWords + 5u];
+  copy_out_tile<kWire>(a, s_cmd, lane, base_count, base_sum + first_index_base, tile_count, first_instance_base);
   MIP_STAMP(5);
 }
 

@@ -1,7 +1,8 @@
 // occlusion_kernel.hpp — EXTENSION (not reference behaviour): occlusion culling against a depth pyramid (Hi-Z), gfx950.
 //   mip_depth_pyramid_kernel    the max pyramid of a D16_UNORM / D32_SFLOAT depth image in ONE launch
-//   mip_occluded_frame_kernel   the frame kernel's path (instance_kernel.hpp) with one more keep predicate: a frustum-visible
-//                               candidate is dropped when its projected world box lies behind the pyramid's depth
+//   mip_occluded_frame_kernel   the commands-first frame kernel with one more keep predicate, built on its tile-tail helpers
+//                               (instance_kernel.hpp): a frustum-visible candidate is dropped when its projected world box lies
+//                               behind the pyramid's depth
 // The test and the pyramid are specified in include/mi_instance_pipeline.h (MipOcclusion) and restated in numpy by
 // tests/occlusion_restatement.py; instantiated in api_occlusion.hip only.
 #pragma once
@@ -292,11 +293,7 @@ __device__ __forceinline__ unsigned long long help_occluded_aggregate(uint32_t u
     const float sc = ka->scale[jl];
     const uint32_t mesh = ka->mesh_id[jl];
     const uint32_t cand_word = oa->candidates ? oa->candidates[jl >> 5] ^ oa->candidates_xor : ~0u;
-    const float4 mb0 = *reinterpret_cast<const float4*>(&ka->meshes[mesh].min_x);
-    const float4 mb1 = *reinterpret_cast<const float4*>(&ka->meshes[mesh].max_x);
-    MeshEntry mb;
-    mb.min_x = mb0.x; mb.min_y = mb0.y; mb.min_z = mb0.z; mb.len0 = __float_as_uint(mb0.w);
-    mb.max_x = mb1.x; mb.max_y = mb1.y; mb.max_z = mb1.z; mb.len1 = __float_as_uint(mb1.w);
+    MeshEntry mb = load_mesh_entry(ka->meshes, mesh);
     float r[3][3];
     quat_to_rotation(q.x, q.y, q.z, q.w, r);
     Instance inst;
@@ -311,11 +308,12 @@ __device__ __forceinline__ unsigned long long help_occluded_aggregate(uint32_t u
   return ((unsigned long long)sum << 32) | cnt;
 }
 
-// One tile of 256 instances per workgroup, as mip_instance_pipeline_kernel<false, kGeneral, 3> (the commands-first order): model
-// matrix, world box, frustum test and LOD by the same device functions; then, for the frustum-visible candidates only, the
-// projection of the world box and a gather of at most four pyramid texels. The kept instances are compacted with the same
-// one-hop prefix (publish / resolve / help) — the help applies the same predicate. Matrices, boxes and TLAS rows are written
-// for every instance, as mip_run writes them.
+// One tile of 256 instances per workgroup: the commands-first order of mip_instance_pipeline_kernel<false, kGeneral, 3> with
+// its tile tail (instance_kernel.hpp: staging, the one-hop prefix, the copy-out, the matrix / TLAS / box stores). Model matrix,
+// world box, frustum test and LOD by the same device functions; then, for the frustum-visible candidates only, the projection
+// of the world box and a gather of at most four pyramid texels. The kept instances are compacted with the same prefix
+// (publish / resolve / help) — the help applies the same predicate. Matrices, boxes and TLAS rows are written for every
+// instance, as mip_run writes them; a second bitmap records the occluded candidates.
 // Register bounds: 6 waves per SIMD (80 VGPRs) for the census-selected kernel and 4 for the one with the fall-back tiers — the
 // tightest bounds at which neither spills to scratch (the help path, which projects and gathers too, sets the high-water mark).
 #ifndef MIP_OCC_WAVES_PER_SIMD
@@ -363,11 +361,7 @@ __global__ __launch_bounds__(kTile, kGeneral ? 4 : MIP_OCC_WAVES_PER_SIMD) void 
     if (tid == 0) s_tile_agg = 0ull;
     __syncthreads();
   }
-  const float4 mb0 = *reinterpret_cast<const float4*>(&a.meshes[mesh].min_x);
-  const float4 mb1 = *reinterpret_cast<const float4*>(&a.meshes[mesh].max_x);
-  MeshEntry mb;
-  mb.min_x = mb0.x; mb.min_y = mb0.y; mb.min_z = mb0.z; mb.len0 = __float_as_uint(mb0.w);
-  mb.max_x = mb1.x; mb.max_y = mb1.y; mb.max_z = mb1.z; mb.len1 = __float_as_uint(mb1.w);
+  MeshEntry mb = load_mesh_entry(a.meshes, mesh);
 
   float r[3][3];
   quat_to_rotation(q.x, q.y, q.z, q.w, r);
@@ -386,12 +380,7 @@ __global__ __launch_bounds__(kTile, kGeneral ? 4 : MIP_OCC_WAVES_PER_SIMD) void 
     dst[2] = make_float4(inst.m[8], inst.m[9], inst.m[10], inst.m[11]);
     s_row3[tid] = inst.row3 | (mesh << 4);
   }
-  if (a.world_aabb && active) {
-    float2* o2 = reinterpret_cast<float2*>(a.world_aabb + (size_t)i * 6);
-    o2[0] = make_float2(inst.mins[0], inst.mins[1]);
-    o2[1] = make_float2(inst.mins[2], inst.maxs[0]);
-    o2[2] = make_float2(inst.maxs[1], inst.maxs[2]);
-  }
+  store_world_aabb(a, i, active, inst);
   bool occluded = false;
   if (candidate) occluded = box_occluded(inst.mins, inst.maxs, oa.pv, oa.pyramid, oa.width, oa.height);  // only these lanes project and gather
   const bool visible = candidate && !occluded;
@@ -418,36 +407,9 @@ __global__ __launch_bounds__(kTile, kGeneral ? 4 : MIP_OCC_WAVES_PER_SIMD) void 
     s_occ[wave] = occ_mask;
   }
 
-  const uint32_t tile_bytes = (n - tile_first < kTile ? n - tile_first : kTile) * 64u;
-  const __amdgpu_buffer_rsrc_t d_model = stream_descriptor(a.model ? a.model + (size_t)tile_first * 4 : nullptr, a.model ? tile_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t d_tlas = stream_descriptor(a.tlas_instances ? a.tlas_instances + (size_t)tile_first * 4 : nullptr, a.tlas_instances ? tile_bytes : 0u);
-  auto store_piece = [&](uint32_t p) {  // as the frame kernel's: 16 staged matrices -> one 1-KiB store instruction
-    const uint32_t local = 16u * p + (lane >> 2);
-    const uint32_t col = lane & 3u;
-    const float* src = &s_mat[local * 12u];
-    const bool in_range = tile_first + local < n;
-    if (a.model) {
-      float w = (col == 3u) ? 1.0f : 0.0f;
-      if constexpr (kGeneral) {
-        const uint32_t bits = s_row3[local] & 15u;
-        if ((bits >> col) & 1u) w = __uint_as_float(0x7fc00000u);
-      }
-      store_stream16(d_model, (64u * p + lane) * 16u, make_float4(src[3u * col], src[3u * col + 1u], src[3u * col + 2u], w));
-    }
-    if (a.tlas_instances) {
-      const uint32_t draw = tile_first + local;
-      uint4 v;
-      if (col < 3u) {
-        v = make_uint4(__float_as_uint(src[col]), __float_as_uint(src[col + 3u]), __float_as_uint(src[col + 6u]), __float_as_uint(src[col + 9u]));
-      } else {
-        const uint32_t mesh_of = s_row3[local] >> 4;
-        const unsigned long long blas = (in_range && a.blas_address) ? a.blas_address[mesh_of] : 0ull;
-        v = make_uint4(((first_instance_base + draw) & 0xffffffu) | 0xff000000u, 0x01000000u, (uint32_t)blas, (uint32_t)(blas >> 32));
-      }
-      store_stream16(d_tlas, (64u * p + lane) * 16u, make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)));
-    }
-  };
-  auto store_bitmaps = [&]() {  // the tile's eight words of each bitmap
+  const PieceStores d = piece_stores(a, tile_first);
+  auto store_piece = [&](uint32_t p) { mip::store_piece<kGeneral>(a, d, s_mat, s_row3, tile_first, first_instance_base, lane, p); };
+  auto store_bitmaps = [&]() {
     if (lane < 2u * kWaves) {
       const uint32_t word = (tile_first >> 5) + lane;
       if (word < a.bitmap_words) {
@@ -472,15 +434,9 @@ __global__ __launch_bounds__(kTile, kGeneral ? 4 : MIP_OCC_WAVES_PER_SIMD) void 
     tile_count += wc;
     tile_sum += ws;
   }
-  if (keep) {
-    uint32_t* c = &s_cmd[(wave_off_count + rank_in_wave) * kCmdLdsWords];
-    c[0] = len;
-    c[1] = 1u;
-    c[2] = wave_off_sum + (incl_sum - len_vis);
-    c[3] = (uint32_t)vertex_offset_of_mesh;
-    c[4] = first_instance_base + i;
-    if (a.src_index_offset) c[5] = far_lod ? a.mesh_draw[mesh].src_offset1 : a.mesh_draw[mesh].src_offset0;
-  }
+  if (keep)
+    stage_command<0>(a, &s_cmd[(wave_off_count + rank_in_wave) * kCmdLdsWords], len, wave_off_sum + (incl_sum - len_vis),
+                     vertex_offset_of_mesh, first_instance_base + i, mesh, far_lod);
   __syncthreads();
   if (wave != 0) {  // waves 1-3: the bulk stores of the whole tile
     const uint32_t p0 = store_run_first(wave), p1 = store_run_first(wave + 1u);
@@ -496,17 +452,7 @@ __global__ __launch_bounds__(kTile, kGeneral ? 4 : MIP_OCC_WAVES_PER_SIMD) void 
     *a.draw_count = base_count + tile_count;
     if (a.index_total) *a.index_total = base_sum + tile_sum;
   }
-  const uint32_t first_index_add = base_sum + first_index_base;
-  uint32_t* out = a.cmds + (size_t)base_count * kCmdWords;
-  const uint32_t words = tile_count * kCmdWords;
-  for (uint32_t j = lane; j < words; j += 64u) {
-    const uint32_t k = j / kCmdWords, f = j - k * kCmdWords;
-    uint32_t v = s_cmd[k * kCmdLdsWords + f];
-    if (f == 2u) v += first_index_add;
-    out[j] = v;
-  }
-  if (a.src_index_offset)
-    for (uint32_t k = lane; k < tile_count; k += 64u) a.src_index_offset[base_count + k] = s_cmd[k * kCmdLdsWords + 5u];
+  copy_out_tile<0>(a, s_cmd, lane, base_count, base_sum + first_index_base, tile_count, first_instance_base);
 }
 
 }  // namespace mip

@@ -66,11 +66,7 @@ __device__ __forceinline__ unsigned long long help_view_aggregate(uint32_t v, ui
     const float4 q = rot[jl];
     const float sc = scale[jl];
     const uint32_t mesh = mesh_id[jl];
-    const float4 mb0 = *reinterpret_cast<const float4*>(&meshes[mesh].min_x);
-    const float4 mb1 = *reinterpret_cast<const float4*>(&meshes[mesh].max_x);
-    MeshEntry mb;
-    mb.min_x = mb0.x; mb.min_y = mb0.y; mb.min_z = mb0.z; mb.len0 = __float_as_uint(mb0.w);
-    mb.max_x = mb1.x; mb.max_y = mb1.y; mb.max_z = mb1.z; mb.len1 = __float_as_uint(mb1.w);
+    MeshEntry mb = load_mesh_entry(meshes, mesh);
     float r[3][3];
     quat_to_rotation(q.x, q.y, q.z, q.w, r);
     Instance inst;
@@ -123,11 +119,7 @@ __global__ __launch_bounds__(kTile, kGeneral ? 4 : MIP_VIEWS_WAVES_PER_SIMD) voi
   const float4 q = a.rot[il];
   const float sc = a.scale[il];
   const uint32_t mesh = a.mesh_id[il];
-  const float4 mb0 = *reinterpret_cast<const float4*>(&a.meshes[mesh].min_x);
-  const float4 mb1 = *reinterpret_cast<const float4*>(&a.meshes[mesh].max_x);
-  MeshEntry mb;
-  mb.min_x = mb0.x; mb.min_y = mb0.y; mb.min_z = mb0.z; mb.len0 = __float_as_uint(mb0.w);
-  mb.max_x = mb1.x; mb.max_y = mb1.y; mb.max_z = mb1.z; mb.len1 = __float_as_uint(mb1.w);
+  MeshEntry mb = load_mesh_entry(a.meshes, mesh);
   const int32_t vertex_offset = a.mesh_draw[mesh].vertex_offset;
   float r[3][3];
   quat_to_rotation(q.x, q.y, q.z, q.w, r);
