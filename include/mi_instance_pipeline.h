@@ -167,7 +167,18 @@ typedef struct MipOutputs {
    * generate_work). firstIndex keeps the reference's layout: the running sum of the full
    * index_len of the earlier commands. */
   void* culled_index_buffer;
-  uint64_t culled_index_capacity; /* in indices (u32); a command that would not fit raises MIP_ERR_CAPACITY */
+  /* Size of culled_index_buffer in indices (u32). Any value is legal, 0 included. When the range
+   * [firstIndex, firstIndex + indexCount) of an emitted command (its FULL index count, before the
+   * per-triangle test) does not fit:
+   *  - the call (mip_wait, for an asynchronous frame) returns MIP_ERR_CAPACITY;
+   *  - no word at or behind culled_index_capacity is written;
+   *  - the commands that fit keep their bytes and their part of the stream, as if the buffer were
+   *    large enough;
+   *  - a command that does not fit writes nothing, not even in front of the capacity, and is
+   *    absent from the compacted list ("its triangles were dropped"); draw_count counts the
+   *    commands that are there, draw_index_total keeps the frame's value;
+   *  - the context stays usable: the next frame with a buffer that fits is complete. */
+  uint64_t culled_index_capacity;
   /* Optional (needs MIP_OUT_DEVICE): N x VkAccelerationStructureInstanceKHR (64 B), one per
    * instance in draw_index order, as build_acceleration_structures fills them
    * (src/renderer/systems/acceleration_strucures.rs:419-451): transform = rows 0..2 of the model

@@ -111,6 +111,103 @@ def dump_wire(name, golden_name):
     print(f"ext/{name}: {len(cmds)} commands -> {body.nbytes} wire bytes ({body.nbytes / max(len(cmds), 1):.2f} B per command)")
 
 
+def dump_triangles(name, s, vertices, indices, pv, first_instance_base=0, first_index_base=0):
+    """Extension fixtures for row f-1 (the per-triangle stage): the frame's inputs with geometry and pv, the frame's command
+    list, the source index offsets, and the oracle's final commands and WHOLE culled stream (untouched slots = 0xFFFFFFFF)."""
+    r = oracle.run(s["pos"], s["rot"], s["scale"], s["mesh_id"], s["meshes"], s["planes"], s["cam_pos"],
+                   first_instance_base=first_instance_base, first_index_base=first_index_base)
+    capacity = first_index_base + r["draw_index_total"] + 3
+    final, stream, src = oracle.cull_all_triangles(r, s["pos"], s["mesh_id"], s["meshes"], s["cam_pos"], pv, vertices, indices,
+                                                   first_instance_base=first_instance_base, out_capacity=capacity, threads=1)
+    path = os.path.join(OUT, "ext", name + ".npz")
+    np.savez_compressed(
+        path, pos=s["pos"], rot=s["rot"], scale=s["scale"], mesh_id=s["mesh_id"], meshes=s["meshes"], planes=s["planes"], cam_pos=s["cam_pos"],
+        pv=np.asarray(pv, np.float32), first_instance_base=np.uint32(first_instance_base), first_index_base=np.uint32(first_index_base),
+        vertices=np.asarray(vertices, np.float32), indices=np.asarray(indices, np.uint32),
+        draw_cmds=r["draw_cmds"], draw_count=np.uint32(r["draw_count"]), draw_index_total=np.uint32(r["draw_index_total"]),
+        src_index_offset=src, final_cmds=final, final_count=np.uint32(len(final)), culled_stream=stream,
+    )
+    print(f"ext/{name}: n={s['n']} cmds={r['draw_count']} -> {len(final)}, indices {int(r['draw_cmds']['indexCount'].sum())} -> "
+          f"{int(final['indexCount'].sum())}, {os.path.getsize(path)} bytes")
+
+
+def small_mesh_table(m=8, max_len0=600):
+    """The first m meshes of the mixed table with their LOD chains rebuilt from at most max_len0 indices and the offsets
+    repacked: the same boxes and LOD structure over geometry of a few thousand indices."""
+    t = scene.mixed_mesh_table()[:m].copy()
+    index_off = vertex_off = 0
+    for k in range(m):
+        len0 = min(int(t["index_len"][k, 0]), max_len0 - 30 * k) // 3 * 3
+        lens = scene._lod_chain(len0)[: int(t["n_lods"][k])]
+        t["n_lods"][k] = len(lens)
+        t["index_len"][k] = 0
+        t["index_offset"][k] = 0
+        for j, l in enumerate(lens):
+            t["index_len"][k, j] = l
+            t["index_offset"][k, j] = index_off
+            index_off += l
+        t["vertex_offset"][k] = vertex_off
+        vertex_off += max(len0 // 3, 9)
+    return t
+
+
+def triangle_scenes():
+    """(name, scene, vertices, indices, pv, bases) of the three committed row f-1 fixtures."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import triangle_cases as tc
+
+    pv = scene.default_pv()
+    out = []
+    # a mixed scene over a reduced mesh table
+    s = scene.make_scene(3, n=300)
+    s["meshes"] = small_mesh_table()
+    s["mesh_id"] = (s["mesh_id"] % len(s["meshes"])).astype(np.uint32)
+    out.append(("triangles_mixed_300", s, *scene.make_geometry(s["meshes"]), pv, {}))
+    # the known-answer triangles as mesh 0 (identity instance 0, mirrored instance 1) + special instances of a small mesh
+    s = scene.make_scene(3, n=24, all_visible=True)
+    table = small_mesh_table(2, 300)
+    kv, ki = tc.case_mesh(tc.CASES + tc.MIRROR_CASES)
+    finite = kv[np.isfinite(kv).all(axis=1)]
+    table["aabb_min"][0], table["aabb_max"][0] = finite.min(axis=0), finite.max(axis=0)
+    table["n_lods"][0] = 1
+    table["index_len"][0], table["index_offset"][0] = 0, 0
+    table["index_len"][0, 0] = len(ki)
+    alone = table[1:2].copy()                         # mesh 1's torus on its own, then placed behind the case mesh
+    n1 = int(alone["n_lods"][0])
+    alone["index_offset"][0, :n1] -= alone["index_offset"][0, 0]
+    alone["vertex_offset"][0] = 0
+    gv, gi = scene.make_geometry(alone)
+    table["vertex_offset"][1] = len(kv)
+    table["index_offset"][1, :n1] = alone["index_offset"][0, :n1] + len(ki)
+    vertices = np.concatenate([kv, gv])
+    indices = np.concatenate([ki, gi])
+    s["meshes"] = table
+    s["mesh_id"][:] = 1
+    s["mesh_id"][:2] = 0
+    s["pos"][0], s["rot"][0], s["scale"][0] = (0, 0, 0), (0, 0, 0, 1), 1.0
+    s["pos"][1], s["rot"][1], s["scale"][1] = tc.MIRROR_INSTANCE["pos"], tc.MIRROR_INSTANCE["rot"], tc.MIRROR_INSTANCE["scale"]
+    s["pos"][5, 0] = np.nan
+    s["scale"][7] = 0.0
+    s["scale"][9] = -1.0
+    s["rot"][11] = (0, 0, 0, 3.0)
+    s["scale"][13] = np.inf
+    out.append(("triangles_special_24", s, vertices, indices, pv, {}))
+    # bases != 0, index counts of 3k+1, 3k+2, 2 and 1
+    s = scene.make_scene(3, n=200, all_visible=True)
+    s["meshes"] = small_mesh_table()
+    s["mesh_id"] = (s["mesh_id"] % len(s["meshes"])).astype(np.uint32)
+    vertices, indices = scene.make_geometry(s["meshes"])
+    m = s["meshes"]
+    for k in range(len(m)):
+        for lod in range(int(m["n_lods"][k])):
+            if (k + lod) % 3 == 1 and m["index_len"][k][lod] > 4:
+                m["index_len"][k][lod] -= 1 + (k % 2)
+    m["index_len"][5][: int(m["n_lods"][5])] = 2
+    m["index_len"][6][: int(m["n_lods"][6])] = 1
+    out.append(("triangles_bases_200", s, vertices, indices, pv, dict(first_instance_base=1000, first_index_base=5)))
+    return out
+
+
 def main():
     os.makedirs(os.path.join(OUT, "ext"), exist_ok=True)
     oracle.build()
@@ -130,6 +227,8 @@ def main():
     dump("special_513", special_scene())
     np.save(os.path.join(OUT, "default_planes.npy"), scene.default_planes())
     dump_wire("wire_4097_bases", "mixed_4097_bases")
+    for name, s, vertices, indices, pv, bases in triangle_scenes():
+        dump_triangles(name, s, vertices, indices, pv, **bases)
 
 
 if __name__ == "__main__":

@@ -345,8 +345,9 @@ __device__ __forceinline__ void triangle_waves_body(const TriangleArgs& a, uint3
                                  : affine ? chunk_walk<true, true>(a, m, model, pv, 0u, m.n_tris, fits, (size_t)m.first_index / 3u, nullptr, lane)
                                           : chunk_walk<false, true>(a, m, model, pv, 0u, m.n_tris, fits, (size_t)m.first_index / 3u, nullptr, lane);
       // the command's final indexCount: beside the command when the re-compaction is told to look there (it must, when another
-      // grid may have taken the frame instead), else into it
-      if (lane == 0) (a.final_index_count ? a.final_index_count[c] : a.cmds[c * kCmdWords + 0]) = survivors * 3u;
+      // grid may have taken the frame instead), else into it. A command that does not fit the index buffer has written nothing:
+      // it ends with no indices and leaves the compacted list (MIP_ERR_CAPACITY, "its triangles were dropped")
+      if (lane == 0) (a.final_index_count ? a.final_index_count[c] : a.cmds[c * kCmdWords + 0]) = fits ? survivors * 3u : 0u;
 #ifdef MIP_EXP_RANGE_TIMES
       if (lane == 0u && exp_cmds == 0u) exp_at[4] = (uint32_t)__builtin_amdgcn_s_memrealtime();
       exp_cmds += 1u; exp_tris += m.n_tris;
@@ -754,7 +755,7 @@ __global__ __launch_bounds__(kTriBlock) void mip_triangle_cull_block_kernel(cons
       }
       survivors += total;
     }
-    if (tid == 0) a.cmds[c * kCmdWords + 0] = survivors * 3u;
+    if (tid == 0) a.cmds[c * kCmdWords + 0] = fits ? survivors * 3u : 0u;  // (a command that does not fit wrote nothing: dropped)
   }
 }
 
@@ -925,7 +926,8 @@ __global__ __launch_bounds__(256, 4) void mip_triangle_cull_parts_kernel(const T
     }
     // the command's final indexCount — beside the command, never into it: a part of this command that has not started yet (its
     // successors have helped themselves past it) still needs the ORIGINAL indexCount to find its triangles
-    if (part == kTriParts - 1u && tid == 0) a.final_index_count[c] = (prefix + total) * 3u;
+    // (a command that does not fit the index buffer wrote nothing: it ends with no indices)
+    if (part == kTriParts - 1u && tid == 0) a.final_index_count[c] = fits ? (prefix + total) * 3u : 0u;
   }
 }
 
@@ -990,8 +992,11 @@ __global__ __launch_bounds__(256) void mip_triangle_prepare_kernel(const Triangl
   const uint32_t n_tris = index_count / 3u;
   const uint32_t end = (first_index - base) / 3u + n_tris;
   const uint32_t prev_end = c ? (a.cmds[(c - 1u) * kCmdWords + 2] - base) / 3u + a.cmds[(c - 1u) * kCmdWords + 0] / 3u : 0u;
-  if ((unsigned long long)first_index + index_count > a.capacity) raise_error(a.error_flag, kErrIndexOverflow);
-  if (n_tris == 0u) a.final_index_count[c] = 0u;  // (an indexCount of 1 or 2: no range ever visits it)
+  // A command that does not fit the index buffer is reported and ends with no indices, here: the ranges behind ranges_cap are
+  // never walked, and what an earlier frame of the slot left in final_index_count[c] must not reach the compacted list.
+  const bool fits = (unsigned long long)first_index + index_count <= a.capacity;
+  if (!fits) raise_error(a.error_flag, kErrIndexOverflow);
+  if (n_tris == 0u || !fits) a.final_index_count[c] = 0u;  // (an indexCount of 1 or 2: no range ever visits it)
   uint32_t b = (prev_end + S - 1u) / S;
   uint32_t b_end = (end + S - 1u) / S;
   if (b_end > ca.ranges_cap) b_end = ca.ranges_cap;  // (only commands that do not fit the index buffer reach past it: reported above)
@@ -1190,7 +1195,7 @@ __device__ __forceinline__ void triangle_ranges_body(const TriangleChunkArgs& ca
           } else {             // the command starts here: its survivors' position is known
             survivors = affine ? chunk_walk<true, true>(a, m, model, pv, t_begin, t_end, fits, dst_tri, nullptr, lane)
                                : chunk_walk<false, true>(a, m, model, pv, t_begin, t_end, fits, dst_tri, nullptr, lane);
-            if (ends_here && lane == 0u) a.final_index_count[c] = survivors * 3u;
+            if (ends_here && lane == 0u) a.final_index_count[c] = fits ? survivors * 3u : 0u;  // (does not fit: nothing written, dropped)
           }
           last_survivors = survivors;
         }
@@ -1206,7 +1211,7 @@ __device__ __forceinline__ void triangle_ranges_body(const TriangleChunkArgs& ca
     if (pend.valid) {
       const uint32_t prefix = chunk_lookback(ca, S, pv, pend, lane);
       chunk_write_deferred(a, base, pv, pend, s_masks[wave][buf ^ 1u], prefix, lane);
-      if (pend.ends && lane == 0u) a.final_index_count[pend.c] = (prefix + pend.survivors) * 3u;
+      if (pend.ends && lane == 0u) a.final_index_count[pend.c] = pend.fits ? (prefix + pend.survivors) * 3u : 0u;
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // those masks have been read before a later range writes its own there
       __builtin_amdgcn_wave_barrier();
     }

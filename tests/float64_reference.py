@@ -33,3 +33,47 @@ def run(s):
     decided = (np.abs(margin) > 1e-4 * scale).all(axis=1)
     model_colmajor = M.transpose(0, 2, 1).reshape(n, 16)
     return dict(model=model_colmajor, mins=lo, maxs=hi, culled=culled, decided=decided)
+
+
+# ---- row f-1: the per-triangle decision (generate_work.comp:137-166) ------------------------------------------------
+#
+# The forward error bound of the float32 chain, in units of u = 2^-24, against the ABSOLUTE-VALUE evaluation of the same
+# expression (every product and sum taken over |pv|, |model|, |v|: cancellation inside the transform is covered).
+#   * world = model * vec4(v, 1): a dot product of four terms, 4 multiplications and 3 additions, at most 4 roundings on any
+#     term's path: |error| <= 4u |model||v|.
+#   * clip = pv * world: the same again over inputs that already carry 4u: (4 + 4)u |pv||model||v| =: 8u A, to first order.
+#   * det: a sum of six products of three clip values: 3 x 8u from the factors, 2u from the two multiplications, and at most
+#     3u from the subtraction inside the cofactor and the two outer additions: 29u x the permanent-like sum of |.| products.
+#   * the bound tests compare x / w with +-1: 8u A_x + 8u A_w from the operands, 1u |w| from the division: <= 9u (A_x + A_w).
+# K is the larger of the two, rounded up to a power of two. It is derived, not tuned: a test that fails with it has found
+# something.
+TRIANGLE_K = 32
+
+
+def triangle_decisions(model, pv, v, k=TRIANGLE_K):
+    """model, pv: float32[16] column-major; v: (t, 3 corners, 3) float32 positions. Returns (culled, decided): the shader's
+    decision evaluated in float64 from those float32 inputs, and whether every quantity the decision hangs on is further
+    from its threshold than the float32 chain's forward error bound (k u x magnitudes)."""
+    u = 2.0 ** -24
+    M = np.asarray(model, np.float64).reshape(4, 4).T    # row-major 4x4
+    P = np.asarray(pv, np.float64).reshape(4, 4).T
+    vh = np.concatenate([np.asarray(v, np.float64), np.ones(v.shape[:2] + (1,))], axis=-1)   # (t, 3, 4)
+    with np.errstate(all="ignore"):
+        clip = vh @ (P @ M).T                                     # (t, 3, 4)
+        mag = np.abs(vh) @ (np.abs(P) @ np.abs(M)).T              # |pv| |model| |v|
+        c, a = clip[..., [0, 1, 3]], mag[..., [0, 1, 3]]          # xyw of the three corners: (t, corner, 3)
+        det = (c[:, 0, 0] * (c[:, 1, 1] * c[:, 2, 2] - c[:, 2, 1] * c[:, 1, 2]) - c[:, 1, 0] * (c[:, 0, 1] * c[:, 2, 2] - c[:, 2, 1] * c[:, 0, 2])
+               + c[:, 2, 0] * (c[:, 0, 1] * c[:, 1, 2] - c[:, 1, 1] * c[:, 0, 2]))
+        det_mag = (a[:, 0, 0] * (a[:, 1, 1] * a[:, 2, 2] + a[:, 2, 1] * a[:, 1, 2]) + a[:, 1, 0] * (a[:, 0, 1] * a[:, 2, 2] + a[:, 2, 1] * a[:, 0, 2])
+                   + a[:, 2, 0] * (a[:, 0, 1] * a[:, 1, 2] + a[:, 1, 1] * a[:, 0, 2]))
+        w = clip[..., 3]
+        ndc = clip[..., :2] / w[..., None]                         # (t, corner, 2)
+        outside = (ndc < -1.0).all(axis=1).any(axis=1) | (ndc > 1.0).all(axis=1).any(axis=1)
+        culled = (det > 0.0) | outside
+        sgn = np.where(w < 0.0, -1.0, 1.0)
+        margin = np.abs(np.abs(clip[..., :2] * sgn[..., None]) - np.abs(w)[..., None])   # |x sgn w| - |w|: 0 on a bound
+        decided = (np.abs(det) > k * u * det_mag) \
+            & (margin > k * u * (mag[..., :2] + mag[..., 3:4])).all(axis=(1, 2)) \
+            & (np.abs(w) > k * u * mag[..., 3]).all(axis=1) \
+            & np.isfinite(clip).all(axis=(1, 2))
+    return culled, decided

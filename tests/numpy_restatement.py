@@ -133,3 +133,70 @@ def run(s, first_instance_base=0, first_index_base=0):
     culled = coarse_culled(mins, maxs, s["planes"])
     cmds = draw_commands(s["pos"], s["mesh_id"], culled, s["meshes"], s["cam_pos"], first_instance_base, first_index_base)
     return dict(model=model, world_aabb=np.concatenate([mins, maxs], axis=1), coarse_culled=culled, cmds=cmds)
+
+
+# ---- row f-1: per-triangle cull + index append (generate_work.comp:68-200) -------------------
+
+def src_index_offsets(pos, mesh_id, culled, meshes, cam_pos):
+    """`indexOffset` of every emitted command: the index range of the LOD the frame picked for the instance, for the
+    instances that are visible and whose LOD is not empty, in instance order (the order of the command list)."""
+    with np.errstate(all="ignore"):
+        d = np.asarray(cam_pos).astype(F)[None, :] - pos.astype(F)
+        sq = F(0.0) + ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        far = np.sqrt(sq) > F(10.0)
+    lod = (far & (meshes["n_lods"][mesh_id] > 1)).astype(np.int64)
+    keep = ~np.asarray(culled).astype(bool) & (meshes["index_len"][mesh_id, lod] > 0)
+    return meshes["index_offset"][mesh_id, lod][keep].astype(np.uint32)
+
+
+def _mat4_vec4(m, x, y, z, w):
+    """GLSL mat4 * vec4 as the column combination, left to right: m holds 16 scalars or arrays (column-major)."""
+    return [((m[0 * 4 + r] * x + m[1 * 4 + r] * y) + m[2 * 4 + r] * z) + m[3 * 4 + r] * w for r in range(4)]
+
+
+def triangle_culled(model, pv, v):
+    """generate_work.comp:137-166 for the triangles v (t, 3 corners, 3) of one instance: True where the shader ends
+    with cull == true. float32, one rounding per written operation; `xyz / w` are divisions."""
+    m = [F(x) for x in np.asarray(model, F).reshape(16)]
+    p = [F(x) for x in np.asarray(pv, F).reshape(16)]
+    one = F(1.0)
+    with np.errstate(all="ignore"):
+        clip = []
+        for k in range(3):
+            world = _mat4_vec4(m, v[:, k, 0], v[:, k, 1], v[:, k, 2], one)        # model_mat * vec4(v, 1.0)
+            clip.append(_mat4_vec4(p, world[0], world[1], world[2], world[3]))    # pv * (...)
+        # determinant(mat3(vertex0.xyw, vertex1.xyw, vertex2.xyw)): column k is (x, y, w) of corner k; the cofactor
+        # expansion along the first row of columns, m[0][0] * (m[1][1] * m[2][2] - m[2][1] * m[1][2]) - ...
+        c = [[clip[k][0], clip[k][1], clip[k][3]] for k in range(3)]
+        det = (c[0][0] * (c[1][1] * c[2][2] - c[2][1] * c[1][2]) - c[1][0] * (c[0][1] * c[2][2] - c[2][1] * c[0][2])) \
+            + c[2][0] * (c[0][1] * c[1][2] - c[1][1] * c[0][2])
+        cull = det > F(0.0)
+        ndc_x = [clip[k][0] / clip[k][3] for k in range(3)]
+        ndc_y = [clip[k][1] / clip[k][3] for k in range(3)]
+        outside = ((ndc_x[0] < -one) & (ndc_x[1] < -one) & (ndc_x[2] < -one)) | ((ndc_x[0] > one) & (ndc_x[1] > one) & (ndc_x[2] > one)) \
+            | ((ndc_y[0] < -one) & (ndc_y[1] < -one) & (ndc_y[2] < -one)) | ((ndc_y[0] > one) & (ndc_y[1] > one) & (ndc_y[2] > one))
+    return cull | outside    # (the degenerate-triangle test ends in `cull = false`, :166: it decides nothing)
+
+
+def cull_all_triangles(cmds, src, model, first_instance_base, pv, vertices, indices, out_capacity):
+    """The frame's commands through generate_work.comp and compact_draw_stream.comp: for every command the triangles
+    index_buffer[indexOffset / 3 + id], id < indexCount / 3, of vertex_buffer[vertexOffset + ix]; the survivors in order
+    at out_index_buffer[firstIndex / 3 + k]; indexCount = 3 x survivors; commands without survivors dropped. Returns
+    (final commands, the whole output buffer: slots nothing was written to hold 0xFFFFFFFF)."""
+    vertices = np.asarray(vertices, F).reshape(-1, 3)
+    indices = np.asarray(indices, np.uint32)
+    model = np.asarray(model, F).reshape(-1, 16)
+    out = np.full(int(out_capacity), 0xFFFFFFFF, np.uint32)
+    final = np.array(cmds, copy=True)
+    for k in range(len(final)):
+        n_tris = int(final["indexCount"][k]) // 3
+        s0 = int(src[k]) // 3 * 3
+        ix = indices[s0 : s0 + n_tris * 3].reshape(n_tris, 3)
+        v = vertices[ix.astype(np.int64) + int(final["vertexOffset"][k])]
+        instance = (int(final["firstInstance"][k]) - int(first_instance_base)) & 0xFFFFFFFF
+        kept = ix[~triangle_culled(model[instance], pv, v)] if n_tris else ix
+        d0 = int(final["firstIndex"][k]) // 3 * 3
+        assert d0 + kept.size <= len(out), "the restatement does not model a short output buffer"
+        out[d0 : d0 + kept.size] = kept.reshape(-1)
+        final["indexCount"][k] = kept.size
+    return final[final["indexCount"] != 0], out

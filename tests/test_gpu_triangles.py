@@ -67,15 +67,8 @@ def test_triangle_cull_matches_oracle(ra, oracle_mod, config, n, allvis):
     assert 0 < survivors < int(r["draw_cmds"]["indexCount"].astype(np.int64).sum())  # something was culled, something survived
 
 
-@pytest.mark.parametrize("mode", ["ranges", "ranges_ticketed", "ranges_or_sorted_waves", "sorted_waves", "ranges_of_a_large_frame", "recompact_three_launches",
-                                  "wave", "wave_only", "tickets", "tickets_x4", "block256", "block512", "block1024", "parts"])
-def test_every_triangle_kernel_variant(ra, oracle_mod, monkeypatch, mode):
-    """Round 5: the stage is the range kernel (equal ranges of the triangle stream, one per wave, or — long streams — ranges
-    of MIP_TUNE_TRI_RANGE_SLOTS pulled from a counter) and, above 65 536 instances, the range kernel or the wave-per-command
-    kernel over commands sorted by size class, chosen on the device. The round-4 kernels stay selectable
-    (MIP_TUNE_TRI_CHUNKS_FROM=4294967295): sixteen parts per command, a 256/512/1024-thread workgroup per command (dealt by
-    a stride, or pulling tickets — one or four commands each), one wave per command in list order. Each variant is forced
-    (tuning variables, read by mip_create and at launch) onto the same mixed scene."""
+def _force_variant(monkeypatch, mode):
+    """Forces one decomposition of the stage (tuning variables, read by mip_create and at launch)."""
     if mode == "ranges":
         pass                                                     # the default at this size: one range per wave
     elif mode == "ranges_ticketed":
@@ -108,6 +101,18 @@ def test_every_triangle_kernel_variant(ra, oracle_mod, monkeypatch, mode):
     else:
         monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_MAX", "100000000")
         monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_THREADS", mode[5:])
+
+
+@pytest.mark.parametrize("mode", ["ranges", "ranges_ticketed", "ranges_or_sorted_waves", "sorted_waves", "ranges_of_a_large_frame", "recompact_three_launches",
+                                  "wave", "wave_only", "tickets", "tickets_x4", "block256", "block512", "block1024", "parts"])
+def test_every_triangle_kernel_variant(ra, oracle_mod, monkeypatch, mode):
+    """Round 5: the stage is the range kernel (equal ranges of the triangle stream, one per wave, or — long streams — ranges
+    of MIP_TUNE_TRI_RANGE_SLOTS pulled from a counter) and, above 65 536 instances, the range kernel or the wave-per-command
+    kernel over commands sorted by size class, chosen on the device. The round-4 kernels stay selectable
+    (MIP_TUNE_TRI_CHUNKS_FROM=4294967295): sixteen parts per command, a 256/512/1024-thread workgroup per command (dealt by
+    a stride, or pulling tickets — one or four commands each), one wave per command in list order. Each variant is forced
+    (tuning variables, read by mip_create and at launch) onto the same mixed scene."""
+    _force_variant(monkeypatch, mode)
     s = ra.scene.make_scene(3, n=7000)
     s["pos"][11, 1] = np.nan  # one command takes the literal (non-affine) path
     vertices, indices = ra.scene.make_geometry(s["meshes"])
@@ -401,3 +406,289 @@ print("PARTS OK")
 '''
     out = subprocess.run([sys.executable, "-c", code, root, fault], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "PARTS OK" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+
+
+# ---- committed fixtures, the overflow contract, degenerate frames ---------------------------------------------------
+
+SENTINEL = 0xFFFFFFFF
+
+
+class _Stage:
+    """One context over a scene and its geometry, with outputs the test owns: the index buffer is allocated at `alloc` words
+    whatever capacity a frame is given, so a kernel that ignored the capacity would write into the test's own memory."""
+
+    def __init__(self, ra, s, vertices, indices, alloc, frames_in_flight=1, n_slots=1):
+        import torch
+
+        self.ra, self.torch, self.s = ra, torch, s
+        n = max(s["n"], 1)
+        dev = torch.device("cuda", 0)
+        self.p = ra.InstancePipeline(max_instances=n, max_meshes=len(s["meshes"]), frames_in_flight=frames_in_flight)
+        self.p.set_mesh_table(s["meshes"])
+        self.p.set_geometry(vertices, indices)
+        self.p.set_instances(s["pos"], s["rot"], s["scale"], s["mesh_id"])
+        self.bufs = [dict(model=torch.zeros((n, 16), dtype=torch.float32, device=dev), cmds=torch.zeros((n, 5), dtype=torch.int32, device=dev),
+                          scal=torch.zeros(8, dtype=torch.int32, device=dev), out=torch.full((alloc,), -1, dtype=torch.int32, device=dev))
+                     for _ in range(n_slots)]
+
+    def close(self):
+        self.p.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def enqueue(self, frame, capacity, slot=0, async_=False):
+        b = self.bufs[slot]
+        self.p.run_device(frame, model=b["model"].data_ptr(), draw_cmds=b["cmds"].data_ptr(), draw_count=b["scal"].data_ptr(),
+                          draw_index_total=b["scal"].data_ptr() + 4, culled_index_buffer=b["out"].data_ptr(), culled_index_capacity=capacity,
+                          async_=async_)
+
+    def read(self, slot=0):
+        b = self.bufs[slot]
+        count, total = (int(x) & 0xFFFFFFFF for x in b["scal"][:2].cpu().tolist())
+        cmds = b["cmds"][:count].cpu().numpy().view(np.uint32).reshape(-1).view(self.ra.DRAW_CMD_DTYPE)
+        return cmds, count, total, b["out"].cpu().numpy().view(np.uint32)
+
+    def run(self, frame, capacity, slot=0):
+        """One synchronous frame into a freshly sentinel-filled buffer. Returns (status, commands, count, total, whole buffer)."""
+        self.bufs[slot]["out"].fill_(-1)
+        self.bufs[slot]["cmds"].fill_(0x5A5A5A5A)
+        self.torch.cuda.synchronize()
+        status = 0
+        try:
+            self.enqueue(frame, capacity, slot)
+        except self.ra.MipError as e:
+            status = e.code
+        return (status,) + self.read(slot)
+
+
+def _assert_frame(got, want_cmds, want_total, want_stream, what, status=0):
+    g_status, g_cmds, g_count, g_total, g_out = got
+    assert g_status == status, (what, g_status)
+    assert g_count == len(want_cmds) and g_total == want_total, (what, g_count, len(want_cmds), g_total, want_total)
+    assert g_cmds.tobytes() == want_cmds.tobytes(), (what, "commands")
+    assert len(g_out) >= len(want_stream)
+    assert np.array_equal(g_out[: len(want_stream)], want_stream), (what, "stream", int((g_out[: len(want_stream)] != want_stream).sum()))
+    assert (g_out[len(want_stream):] == SENTINEL).all(), (what, "words behind the capacity were written")
+
+
+@pytest.mark.parametrize("large_frame_path", [False, True])
+@pytest.mark.parametrize("name", ["triangles_mixed_300", "triangles_special_24", "triangles_bases_200"])
+def test_committed_triangle_fixtures(ra, monkeypatch, name, large_frame_path):
+    """tests/golden/ext/triangles_*.npz through mip_run: final commands, count, total and the whole culled stream are the
+    committed bytes (which the oracle and the numpy restatement both reproduce: tests/test_oracle.py)."""
+    import os
+
+    from renderer_amd.pipeline import make_frame
+
+    if large_frame_path:
+        monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_MAX", "0")
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ext", name + ".npz"))
+    s = dict(n=len(g["pos"]), pos=g["pos"], rot=g["rot"], scale=g["scale"], mesh_id=g["mesh_id"], meshes=g["meshes"])
+    capacity = len(g["culled_stream"])
+    frame = make_frame(g["planes"], g["cam_pos"], first_instance_base=int(g["first_instance_base"]), first_index_base=int(g["first_index_base"]), pv=g["pv"])
+    with _Stage(ra, s, g["vertices"], g["indices"], capacity + 64) as st:
+        for rep in range(2):
+            _assert_frame(st.run(frame, capacity), g["final_cmds"], int(g["draw_index_total"]), g["culled_stream"], (name, rep))
+
+
+_OVERFLOW_SCENE = {}
+
+
+def _overflow_scene(ra, oracle_mod):
+    """The scene of test_every_triangle_kernel_variant, its oracle frame and the three short capacities (computed once)."""
+    if not _OVERFLOW_SCENE:
+        s = ra.scene.make_scene(3, n=7000)
+        s["pos"][11, 1] = np.nan
+        vertices, indices = ra.scene.make_geometry(s["meshes"])
+        pv = ra.scene.default_pv()
+        r0 = oracle_mod.run(s["pos"], s["rot"], s["scale"], s["mesh_id"], s["meshes"], s["planes"], s["cam_pos"], want=("draw_cmds",))
+        full = r0["draw_index_total"] + 3
+        r, want_cmds, want_out = _oracle(oracle_mod, s, vertices, indices, pv, full, first_instance_base=17)
+        frame_cmds = r["draw_cmds"]
+        ends = frame_cmds["firstIndex"].astype(np.int64) + frame_cmds["indexCount"].astype(np.int64)
+        k = int(np.searchsorted(ends, 0.4 * full))
+        assert frame_cmds["indexCount"][k] > 6 and 0 < k < len(frame_cmds) - 1
+        caps = {"inside_a_command": int(frame_cmds["firstIndex"][k]) + int(frame_cmds["indexCount"][k]) // 2, "at_a_command_boundary": int(ends[k]), "zero": 0}
+        _OVERFLOW_SCENE.update(s=s, vertices=vertices, indices=indices, pv=pv, full=full, r=r, want_cmds=want_cmds, want_out=want_out, ends=ends, caps=caps)
+    return _OVERFLOW_SCENE
+
+
+def _expected_short_frame(o, capacity, alloc):
+    """What the contract (include/mi_instance_pipeline.h, culled_index_capacity) leaves of the oracle's frame: the final
+    commands whose FRAME range [firstIndex, firstIndex + indexCount) fits, their part of the stream, the sentinel elsewhere."""
+    frame_cmds = o["r"]["draw_cmds"]
+    fits = o["ends"] <= capacity
+    n_fit = int(fits.sum())
+    assert fits[:n_fit].all()                                   # the commands ascend in firstIndex: the ones that fit are a prefix
+    fitting = set(frame_cmds["firstInstance"][:n_fit].tolist())
+    keep = np.array([int(f) in fitting for f in o["want_cmds"]["firstInstance"]], bool)
+    cut = int(o["ends"][n_fit - 1]) if n_fit else 0
+    stream = np.full(alloc, SENTINEL, np.uint32)
+    stream[:cut] = o["want_out"][:cut]
+    return o["want_cmds"][keep], stream
+
+
+@pytest.mark.parametrize("mode", ["ranges", "ranges_ticketed", "ranges_of_a_large_frame", "ranges_or_sorted_waves", "sorted_waves", "recompact_three_launches",
+                                  "parts", "block256", "tickets", "wave"])
+def test_triangle_overflow_contract(ra, oracle_mod, monkeypatch, mode):
+    """culled_index_capacity shorter than the frame needs (include/mi_instance_pipeline.h), on every decomposition: the call
+    returns MIP_ERR_CAPACITY; no word at or behind the capacity is written; the commands that fit keep their oracle bytes and
+    their part of the stream; the commands that do not fit are absent from the compacted list and write nothing; draw_count
+    counts what is there, draw_index_total keeps the frame's value; the context stays usable. The buffer is allocated at the
+    full size plus a guard tail throughout, a full-capacity frame runs first (so the slot's scratch holds real counts that
+    must not resurface), and a fresh context takes a short frame as its FIRST (so nothing the scratch was allocated with
+    resurfaces either)."""
+    from renderer_amd.pipeline import make_frame
+
+    _force_variant(monkeypatch, mode)
+    o = _overflow_scene(ra, oracle_mod)
+    s, full = o["s"], o["full"]
+    alloc = full + 4096
+    total = o["r"]["draw_index_total"]
+    frame = make_frame(s["planes"], s["cam_pos"], first_instance_base=17, pv=o["pv"])
+    full_stream = np.concatenate([o["want_out"], np.full(alloc - full, SENTINEL, np.uint32)])
+    with _Stage(ra, s, o["vertices"], o["indices"], alloc) as st:
+        _assert_frame(st.run(frame, full), o["want_cmds"], total, full_stream, (mode, "full capacity, first"))
+        for what, capacity in o["caps"].items():
+            want_cmds, want_stream = _expected_short_frame(o, capacity, alloc)
+            assert len(want_cmds) < len(o["want_cmds"])
+            _assert_frame(st.run(frame, capacity), want_cmds, total, want_stream, (mode, what, capacity), status=-4)
+            _assert_frame(st.run(frame, full), o["want_cmds"], total, full_stream, (mode, "full capacity after", what))
+    with _Stage(ra, s, o["vertices"], o["indices"], alloc) as st:
+        for what in ("zero", "inside_a_command"):
+            want_cmds, want_stream = _expected_short_frame(o, o["caps"][what], alloc)
+            _assert_frame(st.run(frame, o["caps"][what]), want_cmds, total, want_stream, (mode, "fresh context", what), status=-4)
+        _assert_frame(st.run(frame, full), o["want_cmds"], total, full_stream, (mode, "fresh context, full capacity"))
+
+
+@pytest.mark.parametrize("large_frame_path", [False, True])
+def test_triangle_overflow_of_a_frame_in_flight_is_reported_by_wait(ra, oracle_mod, monkeypatch, large_frame_path):
+    """Two slots, two asynchronous frames in flight: slot 0's at full capacity, slot 1's with a short buffer. mip_wait returns
+    MIP_ERR_CAPACITY; slot 0's frame is the oracle's, slot 1's is what the contract leaves; the next wait is clean."""
+    from renderer_amd.pipeline import make_frame
+
+    if large_frame_path:
+        monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_MAX", "0")
+    o = _overflow_scene(ra, oracle_mod)
+    s, full = o["s"], o["full"]
+    alloc = full + 4096
+    total = o["r"]["draw_index_total"]
+    frame = make_frame(s["planes"], s["cam_pos"], first_instance_base=17, pv=o["pv"])
+    full_stream = np.concatenate([o["want_out"], np.full(alloc - full, SENTINEL, np.uint32)])
+    capacity = o["caps"]["inside_a_command"]
+    want_cmds, want_stream = _expected_short_frame(o, capacity, alloc)
+    with _Stage(ra, s, o["vertices"], o["indices"], alloc, frames_in_flight=2, n_slots=2) as st:
+        for rep in range(2):   # the second round sees the first one's scratch in both slots
+            for b in st.bufs:
+                b["out"].fill_(-1)
+            st.torch.cuda.synchronize()
+            st.enqueue(frame, full, slot=0, async_=True)
+            st.enqueue(frame, capacity, slot=1, async_=True)
+            with pytest.raises(ra.MipError) as e:
+                st.p.wait()
+            assert e.value.code == -4
+            _assert_frame((0,) + st.read(0), o["want_cmds"], total, full_stream, (rep, "the other slot's frame"))
+            _assert_frame((0,) + st.read(1), want_cmds, total, want_stream, (rep, "the short frame"))
+            st.p.wait()            # reported once
+        st.enqueue(frame, full, slot=0, async_=True)
+        st.enqueue(frame, full, slot=1, async_=True)
+        st.p.wait()
+        for k in range(2):
+            _assert_frame((0,) + st.read(k), o["want_cmds"], total, full_stream, ("both at full capacity", k))
+
+
+def _oracle_and_restatement(oracle_mod, s, vertices, indices, pv, capacity):
+    """The oracle's frame and final (commands, stream), checked against the numpy restatement's."""
+    import numpy_restatement as npr
+
+    r, want_cmds, want_out = _oracle(oracle_mod, s, vertices, indices, pv, capacity)
+    src = npr.src_index_offsets(s["pos"], s["mesh_id"], r["coarse_culled"], s["meshes"], s["cam_pos"])
+    cmds2, out2 = npr.cull_all_triangles(r["draw_cmds"], src, r["model"], 0, pv, vertices, indices, capacity)
+    assert cmds2.tobytes() == want_cmds.tobytes() and np.array_equal(out2, want_out)
+    return r, want_cmds, want_out
+
+
+def _one_triangle_scene(ra, corners):
+    """One instance (identity, at the origin) of one mesh of exactly one triangle."""
+    meshes = np.zeros(1, ra.MESH_DTYPE)
+    c = np.array(corners, np.float32)
+    meshes["aabb_min"], meshes["aabb_max"] = c.min(axis=0), c.max(axis=0) + np.float32(0.01)
+    meshes["n_lods"] = 1
+    meshes["index_len"][0, 0] = 3
+    s = dict(n=1, pos=np.zeros((1, 3), np.float32), rot=np.array([[0, 0, 0, 1]], np.float32), scale=np.ones(1, np.float32),
+             mesh_id=np.zeros(1, np.uint32), meshes=meshes, planes=ra.scene.default_planes(), cam_pos=np.array([0, 1, 2], np.float32))
+    return s, c, np.arange(3, dtype=np.uint32)
+
+
+@pytest.mark.parametrize("large_frame_path", [False, True])
+def test_degenerate_frames_through_the_triangle_stage(ra, oracle_mod, monkeypatch, large_frame_path):
+    """Frames that end early in the stage, each twice (the second sees the first one's scratch), each followed by a normal
+    frame in the same context, each against the oracle AND the numpy restatement: no instance passes the frustum (no
+    command: the stage kernels return on count == 0); commands are emitted but every triangle dies (draw_count 0 after the
+    re-compaction, draw_index_total keeps the frame's value); the stream is untouched both times."""
+    from renderer_amd.pipeline import make_frame
+
+    if large_frame_path:
+        monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_MAX", "0")
+    s = ra.scene.make_scene(3, n=3000)
+    vertices, indices = ra.scene.make_geometry(s["meshes"])
+    pv = ra.scene.default_pv()
+    r0 = oracle_mod.run(s["pos"], s["rot"], s["scale"], s["mesh_id"], s["meshes"], s["planes"], s["cam_pos"], want=("draw_cmds",))
+    capacity = r0["draw_index_total"] + 3
+    alloc = capacity + 64
+    r, want_cmds, want_out = _oracle_and_restatement(oracle_mod, s, vertices, indices, pv, capacity)
+    normal = make_frame(s["planes"], s["cam_pos"], pv=pv)
+    pad = np.full(alloc - capacity, SENTINEL, np.uint32)
+    untouched = np.full(alloc, SENTINEL, np.uint32)
+    none = np.zeros(0, ra.DRAW_CMD_DTYPE)
+    # a camera that looks away from everything: the same frustum 10 000 units up
+    away_cam = np.array([0, 10_000, 2], np.float32)
+    away_planes = oracle_mod.project_camera(away_cam, (0.0, 0.0, 0.0, 1.0))
+    s_away = dict(s, planes=away_planes, cam_pos=away_cam)
+    ra_, aw_cmds, aw_out = _oracle_and_restatement(oracle_mod, s_away, vertices, indices, pv, capacity)
+    assert ra_["draw_count"] == 0 and len(aw_cmds) == 0 and (aw_out == SENTINEL).all()
+    # a pv whose x row is 3 w: clip.x = 3 clip.w for every vertex, NDC.x = 3 > 1 (or NaN): every triangle is culled
+    pv_dead = pv.copy().reshape(4, 4)
+    pv_dead[:, 0] = 3.0 * pv_dead[:, 3]
+    pv_dead = pv_dead.reshape(16)
+    rd, dead_cmds, dead_out = _oracle_and_restatement(oracle_mod, s, vertices, indices, pv_dead, capacity)
+    assert rd["draw_count"] > 100 and len(dead_cmds) == 0 and (dead_out == SENTINEL).all()
+    with _Stage(ra, s, vertices, indices, alloc) as st:
+        _assert_frame(st.run(normal, capacity), want_cmds, r["draw_index_total"], np.concatenate([want_out, pad]), "normal, first")
+        for rep in range(2):
+            _assert_frame(st.run(make_frame(away_planes, away_cam, pv=pv), capacity), none, 0, untouched, ("no instance visible", rep))
+        _assert_frame(st.run(normal, capacity), want_cmds, r["draw_index_total"], np.concatenate([want_out, pad]), "normal after an empty frame")
+        for rep in range(2):
+            _assert_frame(st.run(make_frame(s["planes"], s["cam_pos"], pv=pv_dead), capacity), none, rd["draw_index_total"], untouched, ("every triangle dies", rep))
+        _assert_frame(st.run(normal, capacity), want_cmds, r["draw_index_total"], np.concatenate([want_out, pad]), "normal after a frame without survivors")
+    with _Stage(ra, s, vertices, indices, alloc) as st:   # a context whose FIRST frames are the degenerate ones
+        _assert_frame(st.run(make_frame(away_planes, away_cam, pv=pv), capacity), none, 0, untouched, "no instance visible, fresh context")
+        _assert_frame(st.run(make_frame(s["planes"], s["cam_pos"], pv=pv_dead), capacity), none, rd["draw_index_total"], untouched, "every triangle dies, fresh context")
+        _assert_frame(st.run(normal, capacity), want_cmds, r["draw_index_total"], np.concatenate([want_out, pad]), "normal after both")
+
+
+@pytest.mark.parametrize("large_frame_path", [False, True])
+def test_one_instance_of_one_triangle(ra, oracle_mod, monkeypatch, large_frame_path):
+    """The smallest frame there is: one instance, one mesh of exactly one triangle — kept (front-facing), culled (two corners
+    swapped), kept again; against the oracle and the restatement, which the known answers of tests/triangle_cases.py pin."""
+    import triangle_cases as tc
+    from renderer_amd.pipeline import make_frame
+
+    if large_frame_path:
+        monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_MAX", "0")
+    pv = ra.scene.default_pv()
+    front = tc.tri(0, 1, 12)
+    for corners, kept in ((front, True), (tc.swapped(front), False)):
+        s, vertices, indices = _one_triangle_scene(ra, corners)
+        r, want_cmds, want_out = _oracle_and_restatement(oracle_mod, s, vertices, indices, pv, 6)
+        assert r["draw_count"] == 1 and len(want_cmds) == int(kept)
+        assert want_out.tolist() == ([0, 1, 2] if kept else [SENTINEL] * 3) + [SENTINEL] * 3
+        with _Stage(ra, s, vertices, indices, 64) as st:
+            frame = make_frame(s["planes"], s["cam_pos"], pv=pv)
+            for rep in range(2):
+                _assert_frame(st.run(frame, 6), want_cmds, 3, want_out, (kept, rep))
+            _assert_frame(st.run(frame, 3), want_cmds, 3, want_out[:3], (kept, "capacity exactly the frame's"))

@@ -52,6 +52,56 @@ def test_extension_fixtures_reproduce(oracle_mod):
     assert lists.tobytes() == g["lists"].tobytes()
 
 
+TRIANGLE_FIXTURES = ("triangles_mixed_300", "triangles_special_24", "triangles_bases_200")
+
+
+@pytest.mark.parametrize("name", TRIANGLE_FIXTURES)
+def test_triangle_fixtures_reproduce(oracle_mod, name):
+    """tests/golden/ext/triangles_*.npz (row f-1): the oracle reproduces the committed frame list, source offsets, final
+    commands and whole culled stream from the committed inputs, and so does the numpy restatement."""
+    import numpy_restatement as npr
+
+    g = np.load(os.path.join(HERE, "golden", "ext", name + ".npz"))
+    fib, fxb = int(g["first_instance_base"]), int(g["first_index_base"])
+    r = oracle_mod.run(g["pos"], g["rot"], g["scale"], g["mesh_id"], g["meshes"], g["planes"], g["cam_pos"], first_instance_base=fib, first_index_base=fxb)
+    assert r["draw_cmds"].tobytes() == g["draw_cmds"].tobytes() and r["draw_count"] == int(g["draw_count"])
+    assert r["draw_index_total"] == int(g["draw_index_total"])
+    capacity = len(g["culled_stream"])
+    assert capacity == fxb + r["draw_index_total"] + 3
+    for threads in (1, 8):
+        final, stream, src = oracle_mod.cull_all_triangles(r, g["pos"], g["mesh_id"], g["meshes"], g["cam_pos"], g["pv"], g["vertices"], g["indices"],
+                                                           first_instance_base=fib, out_capacity=capacity, threads=threads)
+        assert np.array_equal(src, g["src_index_offset"])
+        assert len(final) == int(g["final_count"]) and final.tobytes() == g["final_cmds"].tobytes()
+        assert np.array_equal(stream, g["culled_stream"])
+    b = npr.run(dict(pos=g["pos"], rot=g["rot"], scale=g["scale"], mesh_id=g["mesh_id"], meshes=g["meshes"], planes=g["planes"], cam_pos=g["cam_pos"]))
+    src = npr.src_index_offsets(g["pos"], g["mesh_id"], b["coarse_culled"], g["meshes"], g["cam_pos"])
+    assert np.array_equal(src, g["src_index_offset"])
+    final, stream = npr.cull_all_triangles(g["draw_cmds"], src, b["model"], fib, g["pv"], g["vertices"], g["indices"], capacity)
+    assert final.tobytes() == g["final_cmds"].tobytes() and np.array_equal(stream, g["culled_stream"])
+    assert 0 < int(final["indexCount"].sum()) < int(g["draw_cmds"]["indexCount"].sum())
+
+
+def test_triangle_special_fixture_holds_the_known_answers():
+    """Instance 0 of triangles_special_24 is the identity over the known-answer mesh, instance 1 the mirrored one: their
+    committed survivors are exactly the triangles tests/triangle_cases.py says the shader keeps."""
+    import triangle_cases as tc
+
+    g = np.load(os.path.join(HERE, "golden", "ext", "triangles_special_24.npz"))
+    cases = tc.CASES + tc.MIRROR_CASES
+    identity_kept = [k for _, _, k, _ in tc.CASES] + [not k for _, _, k, _ in tc.MIRROR_CASES]
+    mirror_kept = {len(tc.CASES) + j: k for j, (_, _, k, _) in enumerate(tc.MIRROR_CASES)}
+    for inst, want in ((0, [t for t, k in enumerate(identity_kept) if k]), (1, None)):
+        c = g["final_cmds"][g["final_cmds"]["firstInstance"] == inst][0]
+        first = int(c["firstIndex"]) // 3 * 3
+        got = (g["culled_stream"][first : first + int(c["indexCount"])].reshape(-1, 3)[:, 0] // 3).tolist()
+        if want is not None:
+            assert got == want, (inst, got, want)
+        else:
+            assert [t for t in got if t in mirror_kept] == [t for t, k in mirror_kept.items() if k], (inst, got)
+    assert len(cases) * 3 == int(g["meshes"]["index_len"][0, 0])
+
+
 def test_golden_set_is_present():
     names = {os.path.basename(p) for p in GOLDEN}
     assert {"box_1024.npz", "special_513.npz", "mixed_4097_bases.npz"} <= names
