@@ -450,6 +450,51 @@ typedef struct MipOcclusion {
 
 int32_t mip_run_occluded(MipContext* ctx, const MipFrame* frame, const MipOcclusion* occ, const MipOutputs* out);
 
+/* ---- Extension: batched draws — one instanced command per (mesh, LOD), built on the device -------------------
+ * NOT a reference behaviour: farnoy/renderer issues one VkDrawIndexedIndirectCommand with instanceCount = 1 per visible
+ * entity (generate_work.comp:61-67). Specified here and checked against this repository's own restatement
+ * (tests/batch_restatement.py) only. Everything but batch_model is integer, so every byte is determined.
+ *
+ * MEMBERS: resident instance i < N is a member iff bit i of `visible_bitmap` (DEVICE, ceil(N/32) words, the layout of
+ * MipOutputs.visible_bitmap; bits at or above N are ignored) is set AND index_len[lod_i] > 0, where lod_i is what pick_lod
+ * gives for frame->cam_pos and the instance's position, exactly as the frame kernel evaluates it (0 or 1; 0 for a mesh with
+ * one LOD). With the bitmap of a mip_run of the same frame the members are exactly the firstInstance values of that run's
+ * compacted list.
+ * BUCKET of a member: mesh_id * 2 + lod; buckets are ordered ascending (mesh-major).
+ * SLOTS: the members sorted by (bucket, draw index) — a stable binning. instance_ids[s] = frame->first_instance_base + i for
+ * the member in slot s; slots [0, members) are written, nothing at or behind `members` is touched.
+ * COMMANDS: one per NON-EMPTY bucket, in ascending bucket order, packed from entry 0:
+ *   indexCount = index_len[lod], instanceCount = members of the bucket, firstIndex = index_offset[lod] (the mesh's own range
+ *   of the consolidated index buffer: these draws read the source meshes, not a culled stream), vertexOffset =
+ *   vertex_offset, firstInstance = the slot of the bucket's first member.
+ * Entries at or behind *batch_count are not touched. batch_cmds needs room for min(2 m, N) commands (m = meshes in the table).
+ * batch_model (optional): slot s receives exactly the 64 bytes mip_run's `model` output holds for the instance in slot s,
+ * non-finite inputs included; no `model` output of any frame is needed for it. Slots at or behind `members` are not touched.
+ * A consumer's vertex shader reads entity_id = instance_ids[gl_InstanceIndex] (or, needing only the matrix, model =
+ * batch_model[gl_InstanceIndex]) under vkCmdDrawIndexedIndirectCount(batch_cmds, batch_count).
+ * frame->planes, first_index_base and pv are not read. N = 0 is legal and writes two zeros.
+ *
+ * ORDERING: enqueued on the stream of the frame slot the context's most recent mip_run / mip_run_occluded / mip_run_skinned
+ * used, so a bitmap that frame writes needs no wait in between. A bitmap from anywhere else — a view of mip_run_views, an OR of
+ * two occlusion phases made by the caller, an earlier frame of another slot — needs mip_wait or the caller's own ordering
+ * first. Without MIP_OUT_ASYNC the call returns when the outputs are complete. Scratch is per frame slot, so calls behind
+ * different frames in flight do not disturb each other; give each its own outputs.
+ * ERRORS: NULL ctx / frame / bitmap / batch_cmds / batch_count / instance_ids, a wrong struct_size, a missing MIP_OUT_DEVICE,
+ * unknown flags: MIP_ERR_INVALID_ARGUMENT; no instances or no mesh table: MIP_ERR_NOT_READY.
+ * OUT OF SCOPE: per-triangle culling of batched draws (culled_index_buffer addresses a per-instance region), merging the
+ * batches of several shards, mip_run_many / recorded launch graphs, the wire forms. */
+typedef struct MipBatchOutputs {
+  uint32_t struct_size;      /* = sizeof(MipBatchOutputs) */
+  uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
+  void* batch_cmds;          /* DEVICE: room for min(2 * m, N) MipDrawIndexedIndirectCommand */
+  uint32_t* batch_count;     /* DEVICE: number of commands written */
+  uint32_t* instance_ids;    /* DEVICE: room for N words; slots [0, members) are written */
+  uint32_t* instance_count;  /* DEVICE, optional: members */
+  void* batch_model;         /* DEVICE, optional, 16-byte aligned: room for N x 64 B */
+} MipBatchOutputs;           /* 48 B */
+
+int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipBatchOutputs* out);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every

@@ -90,6 +90,21 @@ int main(void) {
     running += cmds[k].indexCount;
   }
   ok = ok && running == index_total && model[12] == pos[0] && model[15] == 1.0f;
+  /* Batched draws (extension): with DEVICE buffers — the renderer's own, imported with mip_import_external_fd — the frame above
+   * is followed, without a wait, by
+   *     MipBatchOutputs b = { sizeof b, MIP_OUT_DEVICE | MIP_OUT_ASYNC, batch_cmds, batch_count, instance_ids, NULL, batch_model };
+   *     mip_batch_draws(ctx, &frame, visible_bitmap_dev, &b);
+   * and drawn with vkCmdDrawIndexedIndirectCount(cb, batch_cmds, 0, batch_count, 0, 2 * n_meshes, 20); the vertex shader reads
+   * entity_id = instance_ids[gl_InstanceIndex] (the depth pass: model = batch_model[gl_InstanceIndex]). This host owns no
+   * device memory, so it only checks that the entry point links from C and refuses host pointers without harming the context. */
+  MipBatchOutputs batch;
+  memset(&batch, 0, sizeof batch);
+  batch.struct_size = sizeof batch;
+  batch.flags = MIP_OUT_HOST;
+  batch.batch_cmds = cmds;
+  batch.batch_count = &count;
+  batch.instance_ids = bitmap;
+  ok = ok && mip_batch_draws(ctx, &frame, bitmap, &batch) == MIP_ERR_INVALID_ARGUMENT && mip_instance_count(ctx) == N;
   printf("C_SMOKE %s instances=%d visible=%u commands=%u index_total=%u checksum=%08x\n", ok ? "OK" : "BAD", N, visible, count,
          index_total, sum);
   mip_destroy(ctx);

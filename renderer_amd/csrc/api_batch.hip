@@ -1,0 +1,182 @@
+// api_batch.hip — C ABI of the instance pipeline, part 6: batched draws (extension, not reference behaviour).
+// mip_batch_draws bins the members of a visibility bitmap by (mesh, LOD) and writes one instanced command per non-empty
+// bucket, the entity ids in slot order and, optionally, the members' model matrices in slot order.
+// The kernels (batch_kernel.hpp) are instantiated here and only here.
+#include "context.hpp"
+#include "batch_kernel.hpp"
+
+namespace mip_host {
+namespace {
+
+uint32_t batch_tiles_for(uint32_t n) { return (n + mip::kBatchTile - 1u) / mip::kBatchTile; }
+
+// ceil(log2(buckets)), at least 1: the bits of a key
+uint32_t key_bits(unsigned long long buckets) {
+  uint32_t bits = 1;
+  while ((1ull << bits) < buckets) ++bits;
+  return bits;
+}
+
+// The slot's scratch, sized from the context's capacities at first use: the tile x bin counts and the digit totals for every
+// frame; the (key, instance) lists, the bucket histogram and the slot map only once a frame needs more than one pass.
+int32_t ensure_scratch(MipContext* ctx, MipContext::BatchScratch& bs, bool several_passes, bool slot_map) {
+  const size_t cap = ctx->max_instances ? ctx->max_instances : 1;
+  if (!bs.d_counts) {
+    MIP_HIP(ctx, hipMalloc(&bs.d_counts, (size_t)mip::kBatchBins * batch_tiles_for((uint32_t)cap) * 4));
+    MIP_HIP(ctx, hipMalloc(&bs.d_totals, (mip::kBatchMaxPasses * mip::kBatchBins + 1) * 4));
+  }
+  if (several_passes && !bs.d_keys[0]) {
+    for (int k = 0; k < 2; ++k) {
+      MIP_HIP(ctx, hipMalloc(&bs.d_keys[k], cap * 4));
+      MIP_HIP(ctx, hipMalloc(&bs.d_ids[k], cap * 4));
+    }
+    MIP_HIP(ctx, hipMalloc(&bs.d_bucket_hist, (size_t)(ctx->max_meshes ? ctx->max_meshes : 1) * 2 * 4));
+  }
+  if (several_passes && slot_map && !bs.d_slot_of) MIP_HIP(ctx, hipMalloc(&bs.d_slot_of, cap * 4));
+  return MIP_OK;
+}
+
+template <class K>
+int32_t launch(MipContext* ctx, K kernel, uint32_t blocks, hipStream_t stream, mip::BatchArgs& a) {
+  void* params[] = {&a};
+  MIP_HIP(ctx, hipLaunchKernel((const void*)kernel, dim3(blocks), dim3(mip::kTile), params, 0, stream));
+  MIP_HIP(ctx, hipGetLastError());
+  return MIP_OK;
+}
+
+}  // namespace
+
+void batch_release(MipContext* ctx) {
+  for (auto& bs : ctx->batch) {
+    (void)hipFree(bs.d_counts);
+    (void)hipFree(bs.d_totals);
+    for (int k = 0; k < 2; ++k) {
+      (void)hipFree(bs.d_keys[k]);
+      (void)hipFree(bs.d_ids[k]);
+    }
+    (void)hipFree(bs.d_bucket_hist);
+    (void)hipFree(bs.d_slot_of);
+  }
+  ctx->batch.clear();
+}
+
+}  // namespace mip_host
+
+using namespace mip_host;
+
+extern "C" {
+
+int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipBatchOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
+  if (out->struct_size != sizeof(MipBatchOutputs))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipBatchOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipBatchOutputs));
+  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipBatchOutputs flags 0x%x", out->flags);
+  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_batch_draws needs MIP_OUT_DEVICE outputs");
+  if (!out->batch_cmds || !out->batch_count || !out->instance_ids)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds/batch_count/instance_ids is NULL");
+  if ((uintptr_t)out->batch_cmds % 4u != 0u || (uintptr_t)out->batch_model % 16u != 0u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds / batch_model is not aligned (4 / 16 bytes)");
+  if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
+  if (int32_t rc = bind_device(ctx)) return rc;
+  // behind the frame issued last: a bitmap that frame writes is ordered before these launches without a wait
+  const uint32_t slot = ctx->last_slot;
+  hipStream_t stream = ctx->slots[slot].stream;
+  const uint32_t n = ctx->n;
+  const unsigned long long buckets = 2ull * ctx->m;
+  if (buckets > 0x80000000ull) return fail(ctx, MIP_ERR_CAPACITY, "%u meshes: a bucket does not fit a 32-bit key", ctx->m);
+
+  if (n == 0 || buckets == 0) {  // nothing to bin: two zeros
+    MIP_HIP(ctx, hipMemsetAsync(out->batch_count, 0, 4, stream));
+    if (out->instance_count) MIP_HIP(ctx, hipMemsetAsync(out->instance_count, 0, 4, stream));
+  } else {
+    const uint32_t bits = key_bits(buckets);
+    const uint32_t passes = (bits + mip::kBatchDigitBits - 1u) / mip::kBatchDigitBits;
+    static_assert(mip::kBatchMaxPasses * mip::kBatchDigitBits >= 32, "a 32-bit key takes at most kBatchMaxPasses digits");
+    const bool several = passes > 1;
+    if (ctx->batch.size() != ctx->slots.size()) ctx->batch.resize(ctx->slots.size());
+    MipContext::BatchScratch& bs = ctx->batch[slot];
+    if (int32_t rc = ensure_scratch(ctx, bs, several, out->batch_model != nullptr)) return rc;
+    // the arithmetic mip_run's `model` comes from: the census decides (frame_plan.hpp, LaunchPlan.general)
+    const bool general = ctx->nonfinite_instances != 0 || ctx->force_general;
+
+    mip::BatchArgs a{};
+    a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
+    a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
+    a.bitmap = visible_bitmap;
+    a.n = n;
+    a.n_tiles = batch_tiles_for(n);
+    a.n_buckets = (uint32_t)buckets;
+    a.n_bins = several ? mip::kBatchBins : (uint32_t)buckets;
+    a.first_instance_base = frame->first_instance_base;
+    std::memcpy(a.cam, frame->cam_pos, sizeof a.cam);
+    a.counts = bs.d_counts;
+    a.members = a.members_out = bs.d_totals + mip::kBatchMaxPasses * mip::kBatchBins;
+    a.batch_cmds = static_cast<uint32_t*>(out->batch_cmds);
+    a.batch_count = out->batch_count;
+    a.instance_count = out->instance_count;
+#ifdef MIP_DEBUG_STAMPS
+    if (const char* env = std::getenv("MIP_DEBUG_TILE_ORDER")) {  // as fill_kernel_args (api_frame.hip) permutes the frame's tiles
+      const uint32_t t = a.n_tiles;
+      if (t > 1u && std::strcmp(env, "reverse") == 0) {
+        a.debug_tile_mult = a.debug_tile_add = t - 1u;
+      } else if (t > 1u && std::strcmp(env, "scramble") == 0) {
+        static const uint32_t primes[] = {7919u, 104729u, 1299709u, 15485863u};
+        for (uint32_t p : primes)
+          if (t % p != 0u) { a.debug_tile_mult = p; break; }
+        a.debug_tile_add = 12345u % t;
+      }
+    }
+#endif
+    if (several) MIP_HIP(ctx, hipMemsetAsync(bs.d_bucket_hist, 0, (size_t)buckets * 4, stream));
+
+    for (uint32_t p = 0; p < passes; ++p) {
+      const bool last = p + 1 == passes;
+      a.shift = p * mip::kBatchDigitBits;
+      a.totals = bs.d_totals + p * mip::kBatchBins;
+      a.bucket_hist = (several && p == 0) ? bs.d_bucket_hist : nullptr;
+      a.keys_in = p ? bs.d_keys[(p - 1) & 1u] : nullptr;
+      a.ids_in = p ? bs.d_ids[(p - 1) & 1u] : nullptr;
+      a.keys_out = last ? nullptr : bs.d_keys[p & 1u];
+      a.ids_out = last ? nullptr : bs.d_ids[p & 1u];
+      a.instance_ids = last ? out->instance_ids : nullptr;
+      a.slot_of = (last && several && out->batch_model) ? bs.d_slot_of : nullptr;
+      a.batch_model = (last && !several) ? static_cast<float4*>(out->batch_model) : nullptr;
+      if (int32_t rc = p == 0 ? launch(ctx, mip::mip_batch_count_kernel<false>, a.n_tiles, stream, a)
+                              : launch(ctx, mip::mip_batch_count_kernel<true>, a.n_tiles, stream, a))
+        return rc;
+      if (int32_t rc = launch(ctx, mip::mip_batch_rowscan_kernel, a.n_bins, stream, a)) return rc;
+      if (p == 0) {  // the scan's epilogue: bucket totals -> commands and the two counts (and the list's length for later passes)
+        a.bucket_totals = several ? bs.d_bucket_hist : a.totals;
+        if (int32_t rc = launch(ctx, mip::mip_batch_commands_kernel, 1, stream, a)) return rc;
+      }
+      int32_t rc;
+      if (p == 0 && last) {
+        rc = !a.batch_model ? launch(ctx, mip::mip_batch_scatter_kernel<false, true, 0>, a.n_tiles, stream, a)
+             : general      ? launch(ctx, mip::mip_batch_scatter_kernel<false, true, 2>, a.n_tiles, stream, a)
+                            : launch(ctx, mip::mip_batch_scatter_kernel<false, true, 1>, a.n_tiles, stream, a);
+      } else if (p == 0) {
+        rc = launch(ctx, mip::mip_batch_scatter_kernel<false, false, 0>, a.n_tiles, stream, a);
+      } else if (last) {
+        rc = launch(ctx, mip::mip_batch_scatter_kernel<true, true, 0>, a.n_tiles, stream, a);
+      } else {
+        rc = launch(ctx, mip::mip_batch_scatter_kernel<true, false, 0>, a.n_tiles, stream, a);
+      }
+      if (rc) return rc;
+    }
+    if (several && out->batch_model) {
+      a.batch_model = static_cast<float4*>(out->batch_model);
+      if (int32_t rc = general ? launch(ctx, mip::mip_batch_model_kernel<true>, a.n_tiles, stream, a)
+                               : launch(ctx, mip::mip_batch_model_kernel<false>, a.n_tiles, stream, a))
+        return rc;
+    }
+  }
+  if (out->flags & MIP_OUT_ASYNC) {
+    ctx->pending_async = true;
+    return MIP_OK;
+  }
+  MIP_HIP(ctx, hipStreamSynchronize(stream));
+  return check_device_error(ctx);
+}
+
+}  // extern "C"

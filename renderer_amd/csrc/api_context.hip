@@ -100,6 +100,7 @@ void free_all(MipContext* ctx) {
   (void)interop_drain(ctx);  // the streams have drained: let queued semaphore signals go out before the helper threads stop
   interop_release(ctx);
   comm_release(ctx);
+  batch_release(ctx);
   (void)hipFree(ctx->d_pos);
   (void)hipFree(ctx->d_rot);
   (void)hipFree(ctx->d_scale);
@@ -288,7 +289,7 @@ int32_t mip_set_mesh_table(MipContext* ctx, const MipMesh* meshes, uint32_t m) {
     draw[k].vertex_offset = s.vertex_offset;
     draw[k].src_offset0 = s.index_offset[0];
     draw[k].src_offset1 = s.n_lods > 1 ? s.index_offset[1] : s.index_offset[0];
-    draw[k].pad = 0;
+    draw[k].pad = s.n_lods > 1 ? 1u : 0u;  // the spare word: 1 = the mesh has a LOD 1 of its own (batch_kernel.hpp, mesh_has_lod1)
   }
   if (int32_t rc = bind_device(ctx)) return rc;
   if (int32_t rc = sync_all(ctx)) return rc;

@@ -4,6 +4,7 @@
 //   api_sharded.hip   shard merges, the collective-library seam, mip_run_sharded and its collective repair
 //   api_interop.hip   external memory and external semaphores (row f-2)
 //   api_occlusion.hip the occlusion-culling extension: depth pyramid builds, mip_run_occluded (occlusion_kernel.hpp)
+//   api_batch.hip     the batched-draws extension: mip_batch_draws (batch_kernel.hpp)
 // (round 3 had all of it in one 2 224-line mip_api.hip)
 #pragma once
 
@@ -89,6 +90,16 @@ struct MipContext {
   uint32_t graph_round = 64;          // frames per replay round over all slots (MIP_TUNE_GRAPH_ROUND, 0 = off)
   std::vector<FrameSlot> slots;
   uint32_t next_slot = 0;
+  // mip_batch_draws (api_batch.hip): scratch per frame slot, allocated at first use from max_instances / max_meshes
+  struct BatchScratch {
+    uint32_t* d_counts = nullptr;       // [256 bins][tiles] members per (bin, tile), scanned in place
+    uint32_t* d_totals = nullptr;       // kBatchMaxPasses x 256 digit totals + the member count
+    uint32_t* d_keys[2] = {nullptr, nullptr};  // tables of more than 128 meshes: the (key, instance) lists between passes
+    uint32_t* d_ids[2] = {nullptr, nullptr};
+    uint32_t* d_bucket_hist = nullptr;  //   members per bucket, 2 x max_meshes words
+    uint32_t* d_slot_of = nullptr;      //   slot of every member by instance (batch_model)
+  };
+  std::vector<BatchScratch> batch;
   std::vector<FrameSlot> view_states;  // mip_run_views: one prefix state per view, all on `stream`
   hipStream_t stream = nullptr;  // = slots[0].stream: uploads, merges, timing
   // resident inputs
@@ -237,6 +248,7 @@ int32_t interop_drain(MipContext* ctx);                // api_interop.hip: every
 // occ != null: the occluded frame kernel (api_occlusion.hip, launch_occluded_frame) takes the frame kernel's place
 int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out, bool skinned, void* palette,
                   const MipOcclusion* occ = nullptr);  // api_frame.hip
+void batch_release(MipContext* ctx);                  // api_batch.hip: the batched-draws scratch, for mip_destroy
 int32_t launch_occluded_frame(MipContext* ctx, const MipOcclusion* occ, mip::KernelArgs& a, const mip::LaunchPlan& plan, hipStream_t stream);  // api_occlusion.hip
 
 }  // namespace mip_host

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import MipConfig, MipError, MipFrame, MipOcclusion, MipOutputs, MipShardedOutputs, MipTimings
+from ._lib import MipBatchOutputs, MipConfig, MipError, MipFrame, MipOcclusion, MipOutputs, MipShardedOutputs, MipTimings
 
 MESH_DTYPE = np.dtype(
     [
@@ -437,6 +437,23 @@ class InstancePipeline:
         one built by hand): every output as mip_run gives it for the scene in which the non-candidates and the occluded instances
         had been frustum-culled."""
         self._check(self._lib.mip_run_occluded(self._ctx, C.addressof(frame), C.addressof(occlusion), C.addressof(outputs)))
+
+    # -- batched draws (extension) --
+    def batch_draws(self, frame, visible_bitmap_ptr, *, batch_cmds, batch_count, instance_ids, instance_count=0, batch_model=0,
+                    async_=False):
+        """mip_batch_draws: one instanced command per non-empty (mesh, LOD) bucket of the members of `visible_bitmap_ptr` (a
+        device bitmap in MipOutputs.visible_bitmap's layout), the entity ids in slot order and, optionally, the members' model
+        matrices in slot order. Device pointers; enqueued behind the frame this context issued last. `frame` from make_frame
+        (its cam_pos and first_instance_base are read)."""
+        out = MipBatchOutputs()
+        out.struct_size = C.sizeof(MipBatchOutputs)
+        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+        out.batch_cmds = batch_cmds or None
+        out.batch_count = batch_count or None
+        out.instance_ids = instance_ids or None
+        out.instance_count = instance_count or None
+        out.batch_model = batch_model or None
+        self._check(self._lib.mip_batch_draws(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(out)))
 
     # -- diagnostics --
     def timings(self):

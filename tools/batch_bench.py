@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""GPU time of the batched-draws stage (mip_batch_draws) beside the frame it follows: HIP events on the launch stream around
+BATCH back-to-back repetitions, median of samples, one JSON line per leg.
+
+  (a) mip_run with every output of the flagship frame (model, bitmap, commands, count, index total): the yardstick
+  (b) mip_run with model = NULL  +  mip_batch_draws with batch_model
+  (c) (a)  +  mip_batch_draws with ids only
+  (s) mip_batch_draws alone, ids only / with batch_model (over the bitmap of (a))
+  (copy) a device-to-device copy of 256 MB: the measured ceiling the fractions refer to
+
+  python tools/batch_bench.py [n ...] [--samples 40] [--out profiles/batch_draws_bench.jsonl]"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK_TBS = 8.0  # MI355X HBM3E
+
+
+def measure(st, fn, batch=20, samples=40, warm=3):
+    import numpy as np
+    import torch
+
+    for _ in range(warm * batch):
+        fn()
+    st.synchronize()
+    out = []
+    for _ in range(samples):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(batch):
+            fn()
+        e1.record(st)
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1) / batch * 1e3)
+    us = np.array(out)
+    return dict(median_us=round(float(np.median(us)), 3), min_us=round(float(us.min()), 3), p90_us=round(float(np.percentile(us, 90)), 3))
+
+
+def bench(n, emit, samples=40):
+    import numpy as np
+    import torch
+
+    import renderer_amd
+    from renderer_amd import scene
+    from renderer_amd.pipeline import make_frame
+
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.Stream()
+    config = 2 if n <= 100_000 else 3
+    s = scene.make_scene(config, n=n)
+    m = len(s["meshes"])
+    with torch.cuda.stream(st):
+        p = renderer_amd.InstancePipeline(n, m, stream=st.cuda_stream)
+        p.set_mesh_table(s["meshes"])
+        p.set_instances(s["pos"], s["rot"], s["scale"], s["mesh_id"])
+        model = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        bitmap = torch.zeros((n + 31) // 32 + 1, dtype=torch.int32, device=dev)
+        cmds = torch.empty((n, 5), dtype=torch.int32, device=dev)
+        scal = torch.zeros(8, dtype=torch.int32, device=dev)
+        b_cmds = torch.empty((2 * m, 5), dtype=torch.int32, device=dev)
+        b_ids = torch.empty(n, dtype=torch.int32, device=dev)
+        b_scal = torch.zeros(8, dtype=torch.int32, device=dev)
+        b_model = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        src = torch.empty(64 << 20, dtype=torch.int32, device=dev)
+        dst = torch.empty_like(src)
+        torch.cuda.synchronize()
+        frame = p.frame_ref(make_frame(s["planes"], s["cam_pos"]))
+        common = dict(visible_bitmap=bitmap.data_ptr(), draw_cmds=cmds.data_ptr(), draw_count=scal.data_ptr(), draw_index_total=scal.data_ptr() + 4)
+        full = p.prepare_outputs(model=model.data_ptr(), **common)
+        no_model = p.prepare_outputs(**common)
+        ids_only = dict(batch_cmds=b_cmds.data_ptr(), batch_count=b_scal.data_ptr(), instance_ids=b_ids.data_ptr(),
+                        instance_count=b_scal.data_ptr() + 4, async_=True)
+        with_model = dict(ids_only, batch_model=b_model.data_ptr())
+
+        def leg_a():
+            p.run_prepared(frame, full)
+
+        def leg_b():
+            p.run_prepared(frame, no_model)
+            p.batch_draws(frame, bitmap.data_ptr(), **with_model)
+
+        def leg_c():
+            p.run_prepared(frame, full)
+            p.batch_draws(frame, bitmap.data_ptr(), **ids_only)
+
+        leg_a()
+        p.wait()
+        copy = measure(st, lambda: dst.copy_(src), batch=5, samples=20)
+        copy_tbs = 2 * src.numel() * 4 / 1e6 / copy["median_us"]
+        emit(dict(leg="copy", bytes=2 * src.numel() * 4, tb_per_s=round(copy_tbs, 3), **copy))
+        legs = [("a: mip_run, every output", leg_a, None), ("b: mip_run without model + batch_draws with batch_model", leg_b, None),
+                ("c: mip_run, every output + batch_draws ids only", leg_c, None),
+                ("s: batch_draws ids only, alone", lambda: p.batch_draws(frame, bitmap.data_ptr(), **ids_only), False),
+                ("s: batch_draws with batch_model, alone", lambda: p.batch_draws(frame, bitmap.data_ptr(), **with_model), True)]
+        for name, fn, stage_model in legs:
+            r = measure(st, fn, samples=samples)
+            p.wait()
+            draws, batches, members = int(scal[0].item()), int(b_scal[0].item()), int(b_scal[1].item())
+            row = dict(leg=name, n=n, config=config, meshes=m, draw_count=draws, batch_count=batches, members=members, **r)
+            if stage_model is not None:  # the stage's algorithmic bytes (one pass): bitmap + mesh_id + pos read, ids written; rot + scale read, matrices written
+                v = members / n
+                per_instance = 0.125 + 16 + 4 * v + ((20 + 64 * v) if stage_model else 0)
+                tbs = per_instance * n / 1e6 / r["median_us"]
+                row.update(member_fraction=round(v, 4), algorithmic_bytes_per_instance=round(per_instance, 2), tb_per_s=round(tbs, 3),
+                           of_peak=round(tbs / PEAK_TBS, 3), of_copy=round(tbs / copy_tbs, 3))
+            emit(row)
+        p.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n", nargs="*", type=int, default=[1_000_000, 100_000])
+    ap.add_argument("--samples", type=int, default=40)
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
+    a = ap.parse_args()
+
+    def emit(row):
+        line = json.dumps(row)
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+    for n in a.n:
+        bench(n, emit, a.samples)
+
+
+if __name__ == "__main__":
+    main()
