@@ -46,6 +46,33 @@ def run_gpu(ra, s, **kw):
         return p.run_host(s["planes"], s["cam_pos"], **kw)
 
 
+def truncate_frame(want, n, base=0):
+    """The oracle's frame of the FIRST n instances of a scene, derived from its frame `want` of more of them (run with
+    first_instance_base = base): the scene generator is prefix-stable and no instance's outputs depend on another's, so the
+    per-instance outputs are prefixes, the bitmap is its first n bits, and the command list is the commands of the instances
+    below n — their running firstIndex is unchanged, because only EARLIER commands enter it. draw_index_total is their
+    indexCount sum mod 2^32 (the base is not part of it). tests/test_plan_boundaries.py proves it byte for byte against
+    oracle.run of the prefix."""
+    n = int(n)
+    out = {}
+    for key in ("model", "world_aabb", "coarse_culled"):
+        if key in want:
+            out[key] = want[key][:n].copy()
+    if "visible_bitmap" in want:
+        words = want["visible_bitmap"][: (n + 31) // 32].copy()
+        if n % 32:
+            words[-1] &= np.uint32((1 << (n % 32)) - 1)
+        out["visible_bitmap"] = words
+    if "draw_cmds" in want:
+        cmds = want["draw_cmds"]
+        keep = (cmds["firstInstance"] - np.uint32(base & 0xFFFFFFFF)).astype(np.uint32) < np.uint32(min(n, 0xFFFFFFFF))
+        kept = cmds[keep].copy()
+        out["draw_cmds"] = kept
+        out["draw_count"] = len(kept)
+        out["draw_index_total"] = int(kept["indexCount"].astype(np.uint64).sum()) & 0xFFFFFFFF
+    return out
+
+
 def report_timing_property(name, value, expected, holds):
     """A property of WHEN things ran (help counts, residency, wall-clock) is reported, never asserted: the bytes are the
     test. A fresh GPU lease owes nobody an idle card or a warm first launch (round 4: `helps <= 64` met 91 on the driver's
