@@ -1,4 +1,4 @@
-// api_batch.hip — C ABI of the instance pipeline, part 6: batched draws (extension, not reference behaviour).
+// api_batch.hip — C ABI of the instance pipeline, part 6 of 6: batched draws (extension, not reference behaviour).
 // mip_batch_draws bins the members of a visibility bitmap by (mesh, LOD) and writes one instanced command per non-empty
 // bucket, the entity ids in slot order and, optionally, the members' model matrices in slot order.
 // The kernels (batch_kernel.hpp) are instantiated here and only here.
@@ -20,7 +20,7 @@ uint32_t key_bits(unsigned long long buckets) {
 // The slot's scratch, sized from the context's capacities at first use: the tile x bin counts and the digit totals for every
 // frame; the (key, instance) lists, the bucket histogram and the slot map only once a frame needs more than one pass.
 int32_t ensure_scratch(MipContext* ctx, MipContext::BatchScratch& bs, bool several_passes, bool slot_map) {
-  const size_t cap = ctx->max_instances ? ctx->max_instances : 1;
+  const size_t cap = instance_cap(ctx);
   if (!bs.d_counts) {
     MIP_HIP(ctx, hipMalloc(&bs.d_counts, (size_t)mip::kBatchBins * batch_tiles_for((uint32_t)cap) * 4));
     MIP_HIP(ctx, hipMalloc(&bs.d_totals, (mip::kBatchMaxPasses * mip::kBatchBins + 1) * 4));
@@ -116,17 +116,7 @@ int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* 
     a.batch_count = out->batch_count;
     a.instance_count = out->instance_count;
 #ifdef MIP_DEBUG_STAMPS
-    if (const char* env = std::getenv("MIP_DEBUG_TILE_ORDER")) {  // as fill_kernel_args (api_frame.hip) permutes the frame's tiles
-      const uint32_t t = a.n_tiles;
-      if (t > 1u && std::strcmp(env, "reverse") == 0) {
-        a.debug_tile_mult = a.debug_tile_add = t - 1u;
-      } else if (t > 1u && std::strcmp(env, "scramble") == 0) {
-        static const uint32_t primes[] = {7919u, 104729u, 1299709u, 15485863u};
-        for (uint32_t p : primes)
-          if (t % p != 0u) { a.debug_tile_mult = p; break; }
-        a.debug_tile_add = 12345u % t;
-      }
-    }
+    DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);  // as fill_kernel_args (api_frame.hip) permutes the frame's tiles
 #endif
     if (several) MIP_HIP(ctx, hipMemsetAsync(bs.d_bucket_hist, 0, (size_t)buckets * 4, stream));
 
@@ -171,12 +161,7 @@ int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* 
         return rc;
     }
   }
-  if (out->flags & MIP_OUT_ASYNC) {
-    ctx->pending_async = true;
-    return MIP_OK;
-  }
-  MIP_HIP(ctx, hipStreamSynchronize(stream));
-  return check_device_error(ctx);
+  return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
 }
 
 }  // extern "C"

@@ -251,7 +251,7 @@ int32_t mip_create(const MipConfig* cfg, MipContext** out) {
     if (const char* env = std::getenv("MIP_TUNE_FORCE_GENERAL")) ctx->force_general = std::atoi(env) != 0;
     if (const char* env = std::getenv("MIP_TUNE_GRAPH_ROUND")) ctx->graph_round = (uint32_t)std::strtoul(env, nullptr, 10);
     if (const char* env = std::getenv("MIP_TEST_EPOCH_START"))  // tests: start next to the tag wrap
-      for (auto& sl : ctx->slots) sl.epoch = (uint32_t)std::strtoul(env, nullptr, 10);
+      for (auto& sl : ctx->slots) sl.tags.epoch = (uint32_t)std::strtoul(env, nullptr, 10);
     MIP_HIP(ctx, hipEventCreate(&ctx->ev0));
     MIP_HIP(ctx, hipEventCreate(&ctx->ev1));
     // the memsets above ran on the null stream, which the slots' non-blocking streams do not wait for
@@ -303,8 +303,8 @@ int32_t mip_set_mesh_table(MipContext* ctx, const MipMesh* meshes, uint32_t m) {
       ctx->have_instances = false;
       ctx->n = 0;
       ctx->nonfinite_instances = 0;
-      for (auto& sl : ctx->slots) sl.status_dirty = true;
-      for (auto& sl : ctx->view_states) sl.status_dirty = true;
+      for (auto& sl : ctx->slots) sl.tags.status_dirty = true;
+      for (auto& sl : ctx->view_states) sl.tags.status_dirty = true;
       ctx->graph_generation++;
     }
   }
@@ -404,16 +404,16 @@ static int32_t set_instances_common(MipContext* ctx, const void* pos, const void
     // the resident columns now hold ids the frame kernel would follow out of the mesh table: nothing is resident
     ctx->have_instances = false;
     ctx->n = 0;
-    for (auto& sl : ctx->slots) sl.status_dirty = true;
-    for (auto& sl : ctx->view_states) sl.status_dirty = true;
+    for (auto& sl : ctx->slots) sl.tags.status_dirty = true;
+    for (auto& sl : ctx->view_states) sl.tags.status_dirty = true;
     ctx->graph_generation++;
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "%u instance(s) with a mesh id >= %u meshes; no instances are resident now", bad_ids, ctx->m);
   }
   if ((bad != 0) != (ctx->nonfinite_instances != 0)) ctx->graph_generation++;  // recorded launches name the other kernel
   ctx->nonfinite_instances = bad;
   if (n != ctx->n) {
-    for (auto& sl : ctx->slots) sl.status_dirty = true;  // tile/group geometry changes with n
-    for (auto& sl : ctx->view_states) sl.status_dirty = true;
+    for (auto& sl : ctx->slots) sl.tags.status_dirty = true;  // tile/group geometry changes with n
+    for (auto& sl : ctx->view_states) sl.tags.status_dirty = true;
     ctx->graph_generation++;                             // and so does every recorded launch
   }
   ctx->n = n;

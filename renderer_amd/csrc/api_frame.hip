@@ -1,6 +1,7 @@
-// api_frame.hip — C ABI of the instance pipeline, part 2 of 4: one frame. plan_frame (frame_plan.hpp) decides which
-// kernels run; this file executes that plan: tags of the cross-tile prefix state, the launches, the copy-back of host
-// outputs, recorded launch graphs (mip_run_many), the multi-view launch, the shadow-pass lists, mip_wait.
+// api_frame.hip — C ABI of the instance pipeline, part 2 of 6 (context.hpp lists them): one frame. plan_frame (frame_plan.hpp)
+// decides which kernels run, PrefixTags (prefix_tags.hpp) which tag of the cross-tile prefix state a launch gets; this file
+// executes both: the launches, the per-triangle stage's host side, the copy-back of host outputs, recorded launch graphs
+// (mip_run_many), the multi-view launch, the shadow-pass lists, mip_wait.
 // The stores-first order of the frame kernel (kOrder == 1) is instantiated HERE and only here; the commands-first
 // order lives in stages_tu.hip, which is built with other flags (stage_args.hpp).
 #include "context.hpp"
@@ -9,7 +10,7 @@ namespace mip_host {
 namespace {
 
 int32_t ensure_staging(MipContext* ctx, const MipOutputs* out) {
-  const size_t cap = ctx->max_instances ? ctx->max_instances : 1;
+  const size_t cap = instance_cap(ctx);
   if (out->model && !ctx->s_model) MIP_HIP(ctx, hipMalloc(&ctx->s_model, cap * 64));
   if (out->visible_bitmap && !ctx->s_bitmap) MIP_HIP(ctx, hipMalloc(&ctx->s_bitmap, ((cap + 31) / 32) * 4));
   if (out->draw_cmds && !ctx->s_cmds) MIP_HIP(ctx, hipMalloc(&ctx->s_cmds, cap * 20));
@@ -88,9 +89,10 @@ uint32_t first_mover_rule_now(MipContext* ctx) {
 }
 
 // Everything of a launch except the tag: resident inputs, output pointers, prefix state, frame.
-void fill_kernel_args(MipContext* ctx, MipContext::FrameSlot& sl, const MipFrame* frame, const MipOutputs* out,
-                      bool device_out, mip::KernelArgs& a) {
+void fill_kernel_args(MipContext* ctx, MipContext::FrameSlot& sl, const mip::LaunchPlan& plan, const MipFrame* frame,
+                      const MipOutputs* out, mip::KernelArgs& a) {
   const uint32_t n = ctx->n;
+  const bool device_out = plan.device_out;
   a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
   a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
   a.model = out->model ? (device_out ? (float4*)out->model : ctx->s_model) : nullptr;
@@ -121,35 +123,22 @@ void fill_kernel_args(MipContext* ctx, MipContext::FrameSlot& sl, const MipFrame
   a.first_index_base = frame->first_index_base;
   std::memcpy(a.planes, frame->planes, sizeof a.planes);
   std::memcpy(a.cam, frame->cam_pos, sizeof a.cam);
-  a.n_tiles = tiles_for(n);
-  a.group_shift = a.n_tiles <= 512 ? 4u : (a.n_tiles <= 2048 ? 5u : 6u);
+  a.n_tiles = plan.n_tiles;
+  a.group_shift = plan.group_shift;
 #ifdef MIP_DEBUG_STAMPS
   a.stamps = ctx->d_stamps;
-  // fault injection (diagnostic build): a tile that never publishes; a permutation of the tile numbers (workgroups then
-  // start in an order that is anything but ascending) — the frame must come out byte-identical either way
+  // fault injection (diagnostic build): a tile that never publishes; a permutation of the tile numbers (DebugSwitches)
+  // — the frame must come out byte-identical either way
   if (const char* env = std::getenv("MIP_DEBUG_SKIP_PUBLISH_TILE")) a.debug_skip_publish_tile = (uint32_t)std::atoi(env) + 1u;
-  if (const char* env = std::getenv("MIP_DEBUG_TILE_ORDER")) {
-    const uint32_t t = a.n_tiles;
-    if (t > 1u && std::strcmp(env, "reverse") == 0) {
-      a.debug_tile_mult = t - 1u;
-      a.debug_tile_add = t - 1u;
-    } else if (t > 1u && std::strcmp(env, "scramble") == 0) {
-      static const uint32_t primes[] = {7919u, 104729u, 1299709u, 15485863u};
-      for (uint32_t p : primes)
-        if (t % p != 0u) { a.debug_tile_mult = p; break; }  // a prime that does not divide t is coprime to it
-      a.debug_tile_add = 12345u % t;
-    }
-  }
+  DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);
 #endif
 }
 
 // Clears a slot's prefix state when the instance count changed or fewer than `need` tags are left.
-int32_t reset_prefix_state_if_needed(MipContext* ctx, MipContext::FrameSlot& sl, uint32_t need) {
-  if (sl.status_dirty || sl.epoch + need > mip::kMaxEpoch) {
+int32_t clear_prefix_state_if_needed(MipContext* ctx, MipContext::FrameSlot& sl, uint32_t need) {
+  if (sl.tags.needs_clear(need)) {
     MIP_HIP(ctx, hipMemsetAsync(sl.d_status, 0, ctx->status_bytes, sl.stream));
-    sl.status_dirty = false;
-    sl.epoch = sl.last_tag = 0;
-    sl.zero_buf = 2;
+    sl.tags.cleared();
     ctx->graph_generation++;  // recorded tags are meaningless on a cleared state
   }
   return MIP_OK;
@@ -201,24 +190,276 @@ int32_t plan_for(MipContext* ctx, const MipFrame* frame, const MipOutputs* out, 
   return MIP_OK;
 }
 
+// A scratch array of 8-byte granules that the launches on a slot validate with a 32-bit tag of their own (range, part and
+// re-compaction granules): allocated and cleared at first use; cleared again, and the tags restarted, where they would wrap.
+// `next`: the tag of the launch that is being prepared — or null: only make sure that the array exists.
+int32_t tagged_scratch(MipContext* ctx, unsigned long long*& granules, uint32_t& tag, size_t count, hipStream_t stream, uint32_t* next) {
+  const bool fresh = !granules;
+  if (fresh) MIP_HIP(ctx, hipMalloc(&granules, count * 8));
+  if (fresh || (next && tag == 0xffffffffu)) {  // (tag wrap: start over on a cleared array)
+    MIP_HIP(ctx, hipMemsetAsync(granules, 0, count * 8, stream));
+    tag = 0;
+  }
+  if (next) *next = ++tag;
+  return MIP_OK;
+}
+
+size_t part_granules(const MipContext* ctx) {  // one per (command, part) of the largest frame the parts kernel takes
+  return (ctx->max_instances < ctx->tri_parts_max ? instance_cap(ctx) : ctx->tri_parts_max) * mip::kTriParts;
+}
+
+// The scratch the plan says the slot must own before the launches of a frame with culled_index_buffer set.
+int32_t ensure_triangle_scratch(MipContext* ctx, MipContext::FrameSlot& sl, const mip::LaunchPlan& plan, const MipOutputs* out, hipStream_t stream) {
+  const size_t cap = instance_cap(ctx);
+  // the instance kernel emits into the slot's scratch list; the triangle stage rewrites
+  // indexCount there and the final compaction lands in the caller's buffers
+  if (!sl.d_tmp_cmds) MIP_HIP(ctx, hipMalloc(&sl.d_tmp_cmds, cap * 20));
+  if (!sl.d_tmp_src) MIP_HIP(ctx, hipMalloc(&sl.d_tmp_src, cap * 4));
+  // one granule per 1024 commands (the one-launch re-compaction; the round-4 form uses the first half as words)
+  if (int32_t rc = tagged_scratch(ctx, sl.d_tmp_blocks, sl.recompact_epoch, cap / 1024 + 1, stream, nullptr)) return rc;
+  if (!sl.d_tmp_final) MIP_HIP(ctx, hipMalloc(&sl.d_tmp_final, cap * 4));
+  if (plan.need_part_status)
+    if (int32_t rc = tagged_scratch(ctx, sl.d_part_status, sl.tri_epoch, part_granules(ctx), stream, nullptr)) return rc;
+  if (plan.need_chunk_scratch) {
+    // ranges of the triangle stream: one per wave of the grid while that keeps them short, else ranges of tri_ticket_slots.
+    // Their number is bounded by the index buffer (a command that does not fit is reported, not walked past it), by what
+    // 32-bit firstIndex can number, and by the largest command times the instances.
+    unsigned long long tris = out->culled_index_capacity / 3ull;
+    if (tris > 0xffffffffull / 3ull) tris = 0xffffffffull / 3ull;
+    // (a command owns floor(indexCount / 3) slots, but the slots are numbered by the running sum of indexCount / 3: index counts that
+    //  are no multiple of 3 push later commands up to 2/3 of a slot each — hence the + 1 per instance)
+    if (tris > (unsigned long long)ctx->n * (ctx->max_lod_tris + 1ull)) tris = (unsigned long long)ctx->n * (ctx->max_lod_tris + 1ull);
+    size_t need = (size_t)(tris / ctx->tri_ticket_slots) + 2;
+    if (need < (size_t)plan.tri_blocks * 4u + 1u) need = (size_t)plan.tri_blocks * 4u + 1u;
+    if (sl.chunks_cap < need) {
+      if (sl.d_chunk_first) {  // a frame of this slot may still read the old arrays
+        MIP_HIP(ctx, hipStreamSynchronize(stream));
+        MIP_HIP(ctx, hipFree(sl.d_chunk_first));
+        MIP_HIP(ctx, hipFree(sl.d_chunk_status));
+        sl.d_chunk_first = nullptr; sl.d_chunk_status = nullptr; sl.chunks_cap = 0;
+      }
+      MIP_HIP(ctx, hipMalloc(&sl.d_chunk_first, need * 4));
+      if (int32_t rc = tagged_scratch(ctx, sl.d_chunk_status, sl.chunk_epoch, need, stream, nullptr)) return rc;
+      sl.chunks_cap = need;
+    }
+    if (plan.tri == mip::TriangleKernel::sorted) {
+      // the commands by descending size class for the wave-per-command decomposition; histogram copies, cursors and the ticket live in one block
+      if (!sl.d_tri_order) MIP_HIP(ctx, hipMalloc(&sl.d_tri_order, cap * 4));
+      if (!sl.d_tri_sort) {
+        MIP_HIP(ctx, hipMalloc(&sl.d_tri_sort, mip::kSortWords * 4));
+        sl.tri_sort_clean = false;
+      }
+    }
+  }
+  return MIP_OK;
+}
+
+// Counters of the triangle stage that the re-compaction clears for the slot's next frame.
+struct StageCounters { uint32_t* words = nullptr; uint32_t n = 0; };
+
+// Re-compaction of the slot's list into the caller's buffers, behind the triangle kernels of the same frame.
+int32_t enqueue_recompaction(MipContext* ctx, MipContext::FrameSlot& sl, const mip::LaunchPlan& plan, const MipOutputs* out,
+                             StageCounters zero, hipStream_t stream) {
+  // (re-compacting inside the workgroup kernels, by the last workgroup to finish, was measured: the
+  // agent-scope fences it needs cost more than the launch they save — 1 k instances 65 vs 49 us)
+  // (the parts and the chunk kernel leave a command's final indexCount beside it: their work items still need the original)
+  const bool final_beside = plan.tri == mip::TriangleKernel::parts || plan.tri == mip::TriangleKernel::chunks || plan.tri == mip::TriangleKernel::sorted;
+  // one launch (round 5); MIP_TUNE_TRI_RECOMPACT_LAUNCHES=3: round 4's count / scan / scatter, which clears no counters
+  const bool clears = plan.recompact == mip::Recompact::single || !ctx->tri_recompact_three_launches;
+  const auto fill = [&](auto& r) {
+    r.in_cmds = sl.d_tmp_cmds;
+    r.index_count = final_beside ? sl.d_tmp_final : nullptr;
+    r.in_count = sl.d_scalars + 2;
+    r.out_cmds = (uint32_t*)out->draw_cmds;
+    r.out_count = out->draw_count;
+    r.zero_words = clears ? zero.words : nullptr;
+    r.n_zero = clears ? zero.n : 0u;
+  };
+  if (plan.recompact == mip::Recompact::single) {
+    mip::RecompactArgs r{};
+    fill(r);
+    mip::launch_recompact(stream, r);
+  } else {
+    mip::RecompactWideArgs r{};
+    fill(r);
+    r.block_base = (uint32_t*)sl.d_tmp_blocks;
+    r.n_blocks = plan.recompact_blocks;
+    if (!ctx->tri_recompact_three_launches) {
+      r.block_status = sl.d_tmp_blocks;
+      if (int32_t rc = tagged_scratch(ctx, sl.d_tmp_blocks, sl.recompact_epoch, instance_cap(ctx) / 1024 + 1, stream, &r.epoch)) return rc;
+      r.help_counter = ctx->d_help + mip::kHelpShards;
+#ifdef MIP_DEBUG_STAMPS
+      r.debug_skip = DebugSwitches().skip ? 1u : 0u;
+#endif
+    }
+    mip::launch_recompact_wide(stream, r);
+  }
+  MIP_HIP(ctx, hipGetLastError());
+  // the counters are cleared by the re-compaction that has just been enqueued
+  const bool cleared = zero.n != 0u && clears;
+  if (zero.words == sl.d_tri_sort && zero.words) sl.tri_sort_clean = cleared;
+  else if (zero.words) sl.tri_ticket_clean = cleared;
+  return MIP_OK;
+}
+
+// The per-triangle stage behind the frame kernel (row f-1): the plan's triangle kernel(s) over the slot's command list,
+// then the re-compaction into the caller's buffers. `index_total`: where the frame kernel left the frame's index total.
+int32_t enqueue_triangle_stage(MipContext* ctx, MipContext::FrameSlot& sl, const mip::LaunchPlan& plan, const MipFrame* frame,
+                               const MipOutputs* out, uint32_t* index_total, hipStream_t stream) {
+  using TK = mip::TriangleKernel;
+  mip::TriangleArgs t{};
+  t.cmds = sl.d_tmp_cmds;
+  t.count = sl.d_scalars + 2;
+  t.src_index_offset = sl.d_tmp_src;
+  t.model = (const float4*)out->model;
+  t.vertices = ctx->d_vertices;
+  t.vertex_bytes = (unsigned long long)ctx->n_vertices * 12ull;
+  t.indices = ctx->d_indices;
+  t.out_indices = (uint32_t*)out->culled_index_buffer;
+  t.capacity = out->culled_index_capacity;
+  t.first_instance_base = frame->first_instance_base;
+  t.error_flag = ctx->d_error;
+  t.help_counter = ctx->d_help + mip::kHelpShards;
+  t.ticket = sl.d_scalars + 3;
+  t.geometry_finite = ctx->geometry_finite ? 1u : 0u;
+  std::memcpy(t.pv, frame->pv, sizeof t.pv);
+  StageCounters zero;
+  if (plan.tri != TK::chunks) sl.tri_ticket_clean = false;  // (the round-4 kernels leave the shared ticket word as it ends)
+  if (plan.tri == TK::chunks || plan.tri == TK::sorted) {
+    const bool either = plan.tri == TK::sorted;  // one grid, either decomposition, chosen on the device (mip_triangle_stage_kernel)
+    t.first_index_base = frame->first_index_base;
+    t.max_lod_tris = ctx->max_lod_tris;
+    if (ctx->tri_force_choice) t.max_lod_tris = ctx->tri_force_choice == 1 ? 0x7fffffffu : 0u;  // tests / A-B runs: ranges | waves
+    t.choice_waves = plan.tri_blocks * 4u;
+    if (either) {
+      // (the re-compaction at the end of a frame clears these counters for the slot's next frame: no clear per frame)
+      if (!sl.tri_sort_clean) MIP_HIP(ctx, hipMemsetAsync(sl.d_tri_sort, 0, mip::kSortWords * 4, stream));
+      sl.tri_sort_clean = false;  // until this frame's re-compaction has been enqueued
+      zero = {sl.d_tri_sort, mip::kSortWords};
+      t.sort_info = sl.d_tri_sort;
+      t.ticket = sl.d_tri_sort + mip::kSortTicket;
+    } else {
+      if (!sl.tri_ticket_clean) MIP_HIP(ctx, hipMemsetAsync(t.ticket, 0, 4, stream));
+      sl.tri_ticket_clean = false;
+      zero = {t.ticket, 1};
+    }
+    mip::TriangleChunkArgs ca{};
+    ca.t = t;
+    ca.t.final_index_count = sl.d_tmp_final;
+    ca.range_first_cmd = sl.d_chunk_first;
+    ca.range_status = sl.d_chunk_status;
+    ca.ranges_cap = (uint32_t)sl.chunks_cap;
+    ca.n_waves = plan.tri_blocks * 4u;
+    ca.ticket_slots = ctx->tri_ticket_slots;
+    if (int32_t rc = tagged_scratch(ctx, sl.d_chunk_status, sl.chunk_epoch, sl.chunks_cap, stream, &ca.epoch)) return rc;
+    ca.first_index_base = frame->first_index_base;
+#ifdef MIP_DEBUG_STAMPS
+    const DebugSwitches dbg;
+    ca.debug_reverse = dbg.reverse() ? 1u : 0u;
+    ca.debug_skip_part = dbg.skip_part(16u);
+#endif
+    if (either) {
+      ca.t.order = sl.d_tri_order;  // (the wave-per-command decomposition's; the range decomposition does not look at it)
+      mip::launch_triangle_stage(plan.tri_map_blocks, plan.tri_blocks, stream, ca);
+    } else {
+      mip::launch_triangle_cull_chunks(plan.tri_map_blocks, plan.tri_blocks, stream, ca);
+    }
+  } else if (plan.tri == TK::parts) {
+    mip::TrianglePartsArgs pa{};
+    pa.t = t;
+    pa.t.final_index_count = sl.d_tmp_final;
+    pa.part_status = sl.d_part_status;
+    if (int32_t rc = tagged_scratch(ctx, sl.d_part_status, sl.tri_epoch, part_granules(ctx), stream, &pa.epoch)) return rc;
+#ifdef MIP_DEBUG_STAMPS
+    const DebugSwitches dbg;
+    pa.debug_reverse = dbg.reverse() ? 1u : 0u;
+    pa.debug_skip_part = dbg.skip_part(mip::kTriParts);
+#endif
+    mip::launch_triangle_cull_parts(plan.tri_blocks, stream, pa);
+  } else {
+    if (plan.tri_reset_ticket) MIP_HIP(ctx, hipMemsetAsync(t.ticket, 0, 4, stream));  // (the counter a grid pulls its commands from)
+    if (plan.tri == TK::block) {
+      t.pull_tickets = plan.tri_block_tickets ? ctx->tri_batch_from : 0u;
+      mip::launch_triangle_cull_block(plan.tri_threads, plan.tri_blocks, stream, t);
+    } else {
+      if (plan.tri_either_blocks) {  // both grids; one returns at once (tri_choice_is_block)
+        t.index_total = index_total;
+        t.max_lod_tris = ctx->max_lod_tris;
+        if (ctx->tri_force_choice) t.max_lod_tris = ctx->tri_force_choice == 1 ? 0x7fffffffu : 0u;  // tests / A-B runs
+        t.pull_tickets = ctx->tri_batch_from;  // (the wave-per-command kernel ignores it: it always pulls single commands)
+        mip::launch_triangle_cull_block(256, plan.tri_either_blocks, stream, t);
+      }
+      mip::launch_triangle_cull_waves(plan.tri_blocks, stream, t);
+    }
+  }
+  MIP_HIP(ctx, hipGetLastError());
+  return enqueue_recompaction(ctx, sl, plan, out, zero, stream);
+}
+
+// The skinning kernel in front of a skinned frame: every instance's posed mesh-space box, into the slot's d_skin_box.
+int32_t enqueue_skinned_bounds(MipContext* ctx, MipContext::FrameSlot& sl, const mip::LaunchPlan& plan, void* palette, hipStream_t stream) {
+  mip::SkinArgs k{};
+  k.poses = ctx->d_poses;
+  k.joints = ctx->d_joints;
+  k.palette = (float4*)palette;
+  k.local_box = sl.d_skin_box;
+  k.n = ctx->n;
+  k.n_joints = ctx->n_joints;
+  k.max_depth = ctx->max_joint_depth;
+  k.box_bound = ctx->joint_box_bound;
+  k.inv_joints = (65536u + ctx->n_joints - 1u) / ctx->n_joints;
+  std::memcpy(k.level_start, ctx->joint_level_start, sizeof k.level_start);
+  std::memcpy(k.level_inv, ctx->joint_level_inv, sizeof k.level_inv);
+  mip::launch_skinned_bounds(plan.skin_blocks, stream, k);
+  MIP_HIP(ctx, hipGetLastError());
+  return MIP_OK;
+}
+
+// MIP_OUT_HOST: the staged outputs to the caller's memory. The command count decides how many commands are copied, so the
+// stream is drained once in the middle; the caller drains it again behind the last copy.
+int32_t copy_back_host_outputs(MipContext* ctx, MipContext::FrameSlot& sl, const MipOutputs* out, hipStream_t stream) {
+  const uint32_t n = ctx->n;
+  if (n) {
+    if (out->model) MIP_HIP(ctx, hipMemcpyAsync(out->model, ctx->s_model, (size_t)n * 64, hipMemcpyDeviceToHost, stream));
+    if (out->visible_bitmap) MIP_HIP(ctx, hipMemcpyAsync(out->visible_bitmap, ctx->s_bitmap, (size_t)((n + 31u) / 32u) * 4, hipMemcpyDeviceToHost, stream));
+    if (out->world_aabb) MIP_HIP(ctx, hipMemcpyAsync(out->world_aabb, ctx->s_aabb, (size_t)n * 24, hipMemcpyDeviceToHost, stream));
+  }
+  if (out->draw_cmds) {
+    uint32_t scalars[2] = {0, 0};
+    MIP_HIP(ctx, hipMemcpyAsync(scalars, sl.d_scalars, 8, hipMemcpyDeviceToHost, stream));
+    MIP_HIP(ctx, hipStreamSynchronize(stream));
+    if (scalars[0] > n) return fail(ctx, MIP_ERR_DEVICE, "draw_count %u > n %u", scalars[0], n);
+    if (scalars[0])
+      MIP_HIP(ctx, hipMemcpyAsync(out->draw_cmds, ctx->s_cmds, (size_t)scalars[0] * 20, hipMemcpyDeviceToHost, stream));
+    *out->draw_count = scalars[0];
+    if (out->draw_index_total) *out->draw_index_total = scalars[1];
+  }
+  return MIP_OK;
+}
+
+void destroy_graph_set(MipContext::GraphSet& gs) {
+  for (auto& fg : gs.per_slot) {
+    if (fg.exec) (void)hipGraphExecDestroy(fg.exec);
+    if (fg.graph) (void)hipGraphDestroy(fg.graph);
+  }
+  gs.per_slot.clear();
+}
+
 }  // namespace
 
 void drop_graphs(MipContext* ctx) {
-  for (auto& gs : ctx->graph_sets)
-    for (auto& fg : gs.per_slot) {
-      if (fg.exec) (void)hipGraphExecDestroy(fg.exec);
-      if (fg.graph) (void)hipGraphDestroy(fg.graph);
-    }
+  for (auto& gs : ctx->graph_sets) destroy_graph_set(gs);
   ctx->graph_sets.clear();
 }
 
-// One frame on the next frame slot. Every decision is in `plan` (frame_plan.hpp); what is left here is the order of
-// the launches and the bookkeeping of the slot's prefix state.
+// One frame on the next frame slot. Every decision is in `plan` (frame_plan.hpp), the tag rule in the slot's PrefixTags
+// (prefix_tags.hpp); what is left here is the order of what goes on the slot's stream:
+//   [clear of the prefix state] [skinning kernel] frame kernel | occluded frame kernel
+//   [triangle kernels, re-compaction] [copies to host outputs]
 int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out, bool skinned, void* palette, const MipOcclusion* occ) {
   mip::LaunchPlan plan;
   if (int32_t rc = plan_for(ctx, frame, out, skinned, &plan)) return rc;
   if (int32_t rc = bind_device(ctx)) return rc;
-  const bool device_out = plan.device_out, async = plan.async;
 
   // Frames rotate over the slots; a slot's stream orders a frame after the frame that last
   // used the same prefix state.
@@ -227,34 +468,20 @@ int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out,
   ctx->next_slot = (ctx->next_slot + 1) % (uint32_t)ctx->slots.size();
   hipStream_t stream = sl.stream;
 
-  const uint32_t n = ctx->n;
-  const uint32_t words = (n + 31u) / 32u;
-  const size_t cap = ctx->max_instances ? ctx->max_instances : 1;
   if (plan.need_staging)
     if (int32_t rc = ensure_staging(ctx, out)) return rc;
-
   mip::KernelArgs a{};
-  fill_kernel_args(ctx, sl, frame, out, device_out, a);
-  a.group_shift = plan.group_shift;
+  fill_kernel_args(ctx, sl, plan, frame, out, a);
   if (plan.uses_prefix_state && !occ) a.first_mover_rule = first_mover_rule_now(ctx);  // (the occluded kernel does not follow the rule)
   if (plan.need_tri_scratch) {
-    // the instance kernel emits into the slot's scratch list; the triangle stage rewrites
-    // indexCount there and the final compaction lands in the caller's buffers
-    if (!sl.d_tmp_cmds) MIP_HIP(ctx, hipMalloc(&sl.d_tmp_cmds, cap * 20));
-    if (!sl.d_tmp_src) MIP_HIP(ctx, hipMalloc(&sl.d_tmp_src, cap * 4));
-    if (!sl.d_tmp_blocks) {  // one granule per 1024 commands (the one-launch re-compaction; the round-4 form uses the first half as words)
-      MIP_HIP(ctx, hipMalloc(&sl.d_tmp_blocks, (cap / 1024 + 1) * 8));
-      MIP_HIP(ctx, hipMemsetAsync(sl.d_tmp_blocks, 0, (cap / 1024 + 1) * 8, stream));
-      sl.recompact_epoch = 0;
-    }
-    if (!sl.d_tmp_final) MIP_HIP(ctx, hipMalloc(&sl.d_tmp_final, cap * 4));
+    if (int32_t rc = ensure_triangle_scratch(ctx, sl, plan, out, stream)) return rc;
     a.cmds = sl.d_tmp_cmds;
     a.draw_count = sl.d_scalars + 2;
     a.src_index_offset = sl.d_tmp_src;
   }
   if (plan.need_skin_box) {
     // the posed mesh-space box replaces the mesh table's; computed first, on the same stream
-    if (!sl.d_skin_box) MIP_HIP(ctx, hipMalloc(&sl.d_skin_box, cap * 32));
+    if (!sl.d_skin_box) MIP_HIP(ctx, hipMalloc(&sl.d_skin_box, instance_cap(ctx) * 32));
     a.box_override = sl.d_skin_box;  // per frame slot: frames in flight may carry different poses
   }
 
@@ -264,264 +491,45 @@ int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out,
     if (a.draw_count) MIP_HIP(ctx, hipMemsetAsync(a.draw_count, 0, 4, stream));
     if (a.index_total) MIP_HIP(ctx, hipMemsetAsync(a.index_total, 0, 4, stream));
   } else {
-    // Cross-tile prefix state (see instance_kernel.hpp): a fresh tag per launch marks
-    // the level-0 words; the level-1 accumulators alternate between two buffers by tag parity,
-    // the kernel zeroing the other one. Launches without draw commands do not touch the state.
+    // Launches without draw commands do not touch the prefix state and take no tag.
     if (plan.uses_prefix_state) {
-      if (int32_t rc = reset_prefix_state_if_needed(ctx, sl, 2)) return rc;
-      uint32_t e = sl.epoch + 1;
-      if (sl.zero_buf != 2 && (e & 1u) != sl.zero_buf) ++e;  // must accumulate in the zeroed buffer
-      a.epoch = sl.epoch = sl.last_tag = e;
-      sl.zero_buf = (e & 1u) ^ 1u;
+      if (int32_t rc = clear_prefix_state_if_needed(ctx, sl, 2)) return rc;
+      a.epoch = sl.tags.next_tag();
     }
     if (timing) MIP_HIP(ctx, hipEventRecord(ctx->ev0, stream));
-    if (plan.skin) {
-      mip::SkinArgs k{};
-      k.poses = ctx->d_poses;
-      k.joints = ctx->d_joints;
-      k.palette = (float4*)palette;
-      k.local_box = sl.d_skin_box;
-      k.n = n;
-      k.n_joints = ctx->n_joints;
-      k.max_depth = ctx->max_joint_depth;
-      k.box_bound = ctx->joint_box_bound;
-      k.inv_joints = (65536u + ctx->n_joints - 1u) / ctx->n_joints;
-      std::memcpy(k.level_start, ctx->joint_level_start, sizeof k.level_start);
-      std::memcpy(k.level_inv, ctx->joint_level_inv, sizeof k.level_inv);
-      mip::launch_skinned_bounds(plan.skin_blocks, stream, k);
-      MIP_HIP(ctx, hipGetLastError());
-    }
+    if (plan.skin)
+      if (int32_t rc = enqueue_skinned_bounds(ctx, sl, plan, palette, stream)) return rc;
+    if (plan.general) ctx->timings.general_launches += 1;
     if (occ) {
-      if (plan.general) ctx->timings.general_launches += 1;
       if (int32_t rc = launch_occluded_frame(ctx, occ, a, plan, stream)) return rc;
     } else {
       mip::FrameKernelParams params(a);
-      if (plan.general) ctx->timings.general_launches += 1;
       MIP_HIP(ctx, hipLaunchKernel((const void*)frame_kernel_of(plan, a.first_mover_rule == 1u), dim3(plan.n_tiles), dim3(mip::kTile), params.p, ctx->lds_pad, stream));
     }
-    if (plan.tri != mip::TriangleKernel::none) {
-      mip::TriangleArgs t{};
-      t.cmds = sl.d_tmp_cmds;
-      t.count = sl.d_scalars + 2;
-      t.src_index_offset = sl.d_tmp_src;
-      t.model = (const float4*)out->model;
-      t.vertices = ctx->d_vertices;
-      t.vertex_bytes = (unsigned long long)ctx->n_vertices * 12ull;
-      t.indices = ctx->d_indices;
-      t.out_indices = (uint32_t*)out->culled_index_buffer;
-      t.capacity = out->culled_index_capacity;
-      t.first_instance_base = frame->first_instance_base;
-      t.error_flag = ctx->d_error;
-      t.help_counter = ctx->d_help + mip::kHelpShards;
-      t.ticket = sl.d_scalars + 3;
-      t.geometry_finite = ctx->geometry_finite ? 1u : 0u;
-      std::memcpy(t.pv, frame->pv, sizeof t.pv);
-      uint32_t* zero_words = nullptr;  // counters of the stage that the re-compaction clears for the slot's next frame
-      uint32_t n_zero = 0;
-      if (plan.tri != mip::TriangleKernel::chunks) sl.tri_ticket_clean = false;  // (the round-4 kernels leave the shared ticket word as it ends)
-      if (plan.tri == mip::TriangleKernel::chunks || plan.tri == mip::TriangleKernel::sorted) {
-        const bool either = plan.tri == mip::TriangleKernel::sorted;  // one grid, either decomposition, chosen on the device (mip_triangle_stage_kernel)
-        t.first_index_base = frame->first_index_base;
-        t.max_lod_tris = ctx->max_lod_tris;
-        if (ctx->tri_force_choice) t.max_lod_tris = ctx->tri_force_choice == 1 ? 0x7fffffffu : 0u;  // tests / A-B runs: ranges | waves
-        t.choice_waves = plan.tri_blocks * 4u;
-        // ranges of the triangle stream: one per wave of the grid while that keeps them short, else ranges of tri_ticket_slots.
-        // Their number is bounded by the index buffer (a command that does not fit is reported, not walked past it), by what
-        // 32-bit firstIndex can number, and by the largest command times the instances.
-        unsigned long long tris = out->culled_index_capacity / 3ull;
-        if (tris > 0xffffffffull / 3ull) tris = 0xffffffffull / 3ull;
-        // (a command owns floor(indexCount / 3) slots, but the slots are numbered by the running sum of indexCount / 3: index counts that
-        //  are no multiple of 3 push later commands up to 2/3 of a slot each — hence the + 1 per instance)
-        if (tris > (unsigned long long)n * (ctx->max_lod_tris + 1ull)) tris = (unsigned long long)n * (ctx->max_lod_tris + 1ull);
-        size_t need = (size_t)(tris / ctx->tri_ticket_slots) + 2;
-        if (need < (size_t)plan.tri_blocks * 4u + 1u) need = (size_t)plan.tri_blocks * 4u + 1u;
-        if (sl.chunks_cap < need) {
-          if (sl.d_chunk_first) {  // a frame of this slot may still read the old arrays
-            MIP_HIP(ctx, hipStreamSynchronize(stream));
-            MIP_HIP(ctx, hipFree(sl.d_chunk_first));
-            MIP_HIP(ctx, hipFree(sl.d_chunk_status));
-            sl.d_chunk_first = nullptr; sl.d_chunk_status = nullptr; sl.chunks_cap = 0;
-          }
-          MIP_HIP(ctx, hipMalloc(&sl.d_chunk_first, need * 4));
-          MIP_HIP(ctx, hipMalloc(&sl.d_chunk_status, need * 8));
-          MIP_HIP(ctx, hipMemsetAsync(sl.d_chunk_status, 0, need * 8, stream));
-          sl.chunks_cap = need;
-          sl.chunk_epoch = 0;
-        }
-        if (sl.chunk_epoch == 0xffffffffu) {  // tag wrap: start over on a cleared array
-          MIP_HIP(ctx, hipMemsetAsync(sl.d_chunk_status, 0, sl.chunks_cap * 8, stream));
-          sl.chunk_epoch = 0;
-        }
-        if (either) {
-          // the commands by descending size class for the wave-per-command decomposition; histogram copies, cursors and the ticket live in one block
-          if (!sl.d_tri_order) MIP_HIP(ctx, hipMalloc(&sl.d_tri_order, cap * 4));
-          if (!sl.d_tri_sort) {
-            MIP_HIP(ctx, hipMalloc(&sl.d_tri_sort, mip::kSortWords * 4));
-            sl.tri_sort_clean = false;
-          }
-          // (the re-compaction at the end of a frame clears these counters for the slot's next frame: no clear per frame)
-          if (!sl.tri_sort_clean) MIP_HIP(ctx, hipMemsetAsync(sl.d_tri_sort, 0, mip::kSortWords * 4, stream));
-          sl.tri_sort_clean = false;  // until this frame's re-compaction has been enqueued
-          zero_words = sl.d_tri_sort;
-          n_zero = mip::kSortWords;
-          t.sort_info = sl.d_tri_sort;
-          t.ticket = sl.d_tri_sort + mip::kSortTicket;
-          t.final_index_count = sl.d_tmp_final;
-        } else {
-          if (!sl.tri_ticket_clean) MIP_HIP(ctx, hipMemsetAsync(t.ticket, 0, 4, stream));
-          sl.tri_ticket_clean = false;
-          zero_words = t.ticket;
-          n_zero = 1;
-        }
-        mip::TriangleChunkArgs ca{};
-        ca.t = t;
-        ca.t.final_index_count = sl.d_tmp_final;
-        ca.range_first_cmd = sl.d_chunk_first;
-        ca.range_status = sl.d_chunk_status;
-        ca.ranges_cap = (uint32_t)sl.chunks_cap;
-        ca.n_waves = plan.tri_blocks * 4u;
-        ca.ticket_slots = ctx->tri_ticket_slots;
-        ca.epoch = ++sl.chunk_epoch;
-        ca.first_index_base = frame->first_index_base;
-#ifdef MIP_DEBUG_STAMPS
-        if (const char* env = std::getenv("MIP_DEBUG_TILE_ORDER")) ca.debug_reverse = std::strcmp(env, "reverse") == 0 ? 1u : 0u;
-        if (const char* env = std::getenv("MIP_DEBUG_SKIP_PART")) ca.debug_skip_part = (uint32_t)std::atoi(env) % 16u + 1u;
-#endif
-        if (either) {
-          ca.t.order = sl.d_tri_order;  // (the wave-per-command decomposition's; the range decomposition does not look at it)
-          mip::launch_triangle_stage(plan.tri_map_blocks, plan.tri_blocks, stream, ca);
-        } else {
-          mip::launch_triangle_cull_chunks(plan.tri_map_blocks, plan.tri_blocks, stream, ca);
-        }
-      } else if (plan.tri == mip::TriangleKernel::parts) {
-        const size_t cap_cmds = ctx->max_instances < ctx->tri_parts_max ? cap : ctx->tri_parts_max;
-        if (!sl.d_part_status) {
-          MIP_HIP(ctx, hipMalloc(&sl.d_part_status, cap_cmds * mip::kTriParts * 8));
-          MIP_HIP(ctx, hipMemsetAsync(sl.d_part_status, 0, cap_cmds * mip::kTriParts * 8, stream));
-          sl.tri_epoch = 0;
-        }
-        if (sl.tri_epoch == 0xffffffffu) {  // tag wrap: start over on a cleared array
-          MIP_HIP(ctx, hipMemsetAsync(sl.d_part_status, 0, cap_cmds * mip::kTriParts * 8, stream));
-          sl.tri_epoch = 0;
-        }
-        mip::TrianglePartsArgs pa{};
-        pa.t = t;
-        pa.t.final_index_count = sl.d_tmp_final;
-        pa.part_status = sl.d_part_status;
-        pa.epoch = ++sl.tri_epoch;
-#ifdef MIP_DEBUG_STAMPS
-        if (const char* env = std::getenv("MIP_DEBUG_TILE_ORDER")) pa.debug_reverse = std::strcmp(env, "reverse") == 0 ? 1u : 0u;
-        if (const char* env = std::getenv("MIP_DEBUG_SKIP_PART")) pa.debug_skip_part = (uint32_t)std::atoi(env) % mip::kTriParts + 1u;
-#endif
-        mip::launch_triangle_cull_parts(plan.tri_blocks, stream, pa);
-      } else if (plan.tri == mip::TriangleKernel::block) {
-        if (plan.tri_reset_ticket) MIP_HIP(ctx, hipMemsetAsync(t.ticket, 0, 4, stream));
-        t.pull_tickets = plan.tri_block_tickets ? ctx->tri_batch_from : 0u;
-        mip::launch_triangle_cull_block(plan.tri_threads, plan.tri_blocks, stream, t);
-      } else {
-        if (plan.tri_reset_ticket) MIP_HIP(ctx, hipMemsetAsync(t.ticket, 0, 4, stream));  // only the wave-per-command kernel hands out tickets
-        if (plan.tri_either_blocks) {  // both grids; one returns at once (tri_choice_is_block)
-          t.index_total = a.index_total;
-          t.max_lod_tris = ctx->max_lod_tris;
-          if (ctx->tri_force_choice) t.max_lod_tris = ctx->tri_force_choice == 1 ? 0x7fffffffu : 0u;  // tests / A-B runs
-          t.pull_tickets = ctx->tri_batch_from;  // (the wave-per-command kernel ignores it: it always pulls single commands)
-          mip::launch_triangle_cull_block(256, plan.tri_either_blocks, stream, t);
-        }
-        mip::launch_triangle_cull_waves(plan.tri_blocks, stream, t);
-      }
-      MIP_HIP(ctx, hipGetLastError());
-      // (re-compacting inside the workgroup kernels, by the last workgroup to finish, was measured: the
-      // agent-scope fences it needs cost more than the launch they save — 1 k instances 65 vs 49 us)
-      // (the parts and the chunk kernel leave a command's final indexCount beside it: their work items still need the original)
-      const bool final_beside = plan.tri == mip::TriangleKernel::parts || plan.tri == mip::TriangleKernel::chunks || plan.tri == mip::TriangleKernel::sorted;
-      if (plan.recompact == mip::Recompact::single) {
-        mip::RecompactArgs r{};
-        r.in_cmds = sl.d_tmp_cmds;
-        r.index_count = final_beside ? sl.d_tmp_final : nullptr;
-        r.in_count = sl.d_scalars + 2;
-        r.out_cmds = (uint32_t*)out->draw_cmds;
-        r.out_count = out->draw_count;
-        r.zero_words = zero_words;
-        r.n_zero = n_zero;
-        mip::launch_recompact(stream, r);
-      } else {
-        mip::RecompactWideArgs r{};
-        r.in_cmds = sl.d_tmp_cmds;
-        r.index_count = final_beside ? sl.d_tmp_final : nullptr;
-        r.in_count = sl.d_scalars + 2;
-        r.out_cmds = (uint32_t*)out->draw_cmds;
-        r.out_count = out->draw_count;
-        r.block_base = (uint32_t*)sl.d_tmp_blocks;
-        r.n_blocks = plan.recompact_blocks;
-        if (!ctx->tri_recompact_three_launches) {  // one launch (round 5); MIP_TUNE_TRI_RECOMPACT_LAUNCHES=3: round 4's count / scan / scatter
-          if (sl.recompact_epoch == 0xffffffffu) {  // tag wrap: start over on cleared granules
-            MIP_HIP(ctx, hipMemsetAsync(sl.d_tmp_blocks, 0, (cap / 1024 + 1) * 8, stream));
-            sl.recompact_epoch = 0;
-          }
-          r.block_status = sl.d_tmp_blocks;
-          r.epoch = ++sl.recompact_epoch;
-          r.help_counter = ctx->d_help + mip::kHelpShards;
-          r.zero_words = zero_words;
-          r.n_zero = n_zero;
-#ifdef MIP_DEBUG_STAMPS
-          r.debug_skip = std::getenv("MIP_DEBUG_SKIP_PART") ? 1u : 0u;
-#endif
-        }
-        mip::launch_recompact_wide(stream, r);
-      }
-      MIP_HIP(ctx, hipGetLastError());
-      // the counters are cleared by the re-compaction that has just been enqueued (not by the three-launch form)
-      const bool cleared = n_zero != 0u && (plan.recompact == mip::Recompact::single || !ctx->tri_recompact_three_launches);
-      if (zero_words == sl.d_tri_sort && zero_words) sl.tri_sort_clean = cleared;
-      else if (zero_words) sl.tri_ticket_clean = cleared;
-    }
+    if (plan.tri != mip::TriangleKernel::none)
+      if (int32_t rc = enqueue_triangle_stage(ctx, sl, plan, frame, out, a.index_total, stream)) return rc;
     if (timing) MIP_HIP(ctx, hipEventRecord(ctx->ev1, stream));
   }
+  if (!plan.device_out)
+    if (int32_t rc = copy_back_host_outputs(ctx, sl, out, stream)) return rc;
 
-  if (!device_out) {
-    if (n) {
-      if (out->model) MIP_HIP(ctx, hipMemcpyAsync(out->model, ctx->s_model, (size_t)n * 64, hipMemcpyDeviceToHost, stream));
-      if (out->visible_bitmap) MIP_HIP(ctx, hipMemcpyAsync(out->visible_bitmap, ctx->s_bitmap, (size_t)words * 4, hipMemcpyDeviceToHost, stream));
-      if (out->world_aabb) MIP_HIP(ctx, hipMemcpyAsync(out->world_aabb, ctx->s_aabb, (size_t)n * 24, hipMemcpyDeviceToHost, stream));
-    }
-    uint32_t scalars[2] = {0, 0};
-    if (out->draw_cmds) {
-      MIP_HIP(ctx, hipMemcpyAsync(scalars, sl.d_scalars, 8, hipMemcpyDeviceToHost, stream));
-      MIP_HIP(ctx, hipStreamSynchronize(stream));
-      if (scalars[0] > n) return fail(ctx, MIP_ERR_DEVICE, "draw_count %u > n %u", scalars[0], n);
-      if (scalars[0])
-        MIP_HIP(ctx, hipMemcpyAsync(out->draw_cmds, ctx->s_cmds, (size_t)scalars[0] * 20, hipMemcpyDeviceToHost, stream));
-      *out->draw_count = scalars[0];
-      if (out->draw_index_total) *out->draw_index_total = scalars[1];
-    }
-    MIP_HIP(ctx, hipStreamSynchronize(stream));
-  } else if (!async) {
-    MIP_HIP(ctx, hipStreamSynchronize(stream));
-  }
-
-  if (async) {
-    ctx->pending_async = true;
-    return MIP_OK;
-  }
-  if (timing && n) {
+  const int32_t rc = finish(ctx, stream, plan.async);
+  if (timing && ctx->n && !plan.async) {
     float ms = 0.f;
     MIP_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     ctx->timings.runs += 1;
     ctx->timings.last_kernel_ms = ms;
     ctx->timings.total_kernel_ms += ms;
   }
-  return check_device_error(ctx);
+  return rc;
 }
 
 namespace {
 
 // mip_run_many with the launches recorded once and replayed: per slot a linear hipGraph of
 // G launches of the instance kernel. Two things change from launch to launch:
-//  - the prefix tag: a chain bakes the tags base+1 .. base+G. Replaying the same tags is sound because
-//    every launch rewrites every level-0 word and group start it later reads, so the only stale tag a
-//    word can hold is the previous launch's — base+G before the chain's first launch (G >= 2) — and
-//    because G is even, so the accumulator buffer the first launch adds into is the one the last
-//    launch zeroed;
+//  - the prefix tag: a chain bakes the tags base+1 .. base+G, G even (prefix_tags.hpp says why replaying
+//    the same tags is sound, also after direct launches ran in between);
 //  - the frame (camera planes, LOD reference point, bases): NOT baked. Node j of a chain reads entry j
 //    of the slot's frame ring in device memory (KernelArgs.frame_ring); the host refreshes the ring
 //    with one stream-ordered copy in front of every replay. A renderer moves its camera every frame
@@ -535,20 +543,12 @@ static void frame_words(const MipFrame& f, uint32_t* w) {
   w[29] = w[30] = w[31] = 0;
 }
 
-static void destroy_graph_set(MipContext::GraphSet& gs) {
-  for (auto& fg : gs.per_slot) {
-    if (fg.exec) (void)hipGraphExecDestroy(fg.exec);
-    if (fg.graph) (void)hipGraphDestroy(fg.graph);
-  }
-  gs.per_slot.clear();
-}
-
 static int32_t run_many_graphed(MipContext* ctx, const MipFrame* frames, uint32_t n_frames, uint32_t first_step,
                                 const MipOutputs* outputs, uint32_t n_outputs, uint32_t rounds, uint32_t frames_per_slot) {
   const uint32_t F = (uint32_t)ctx->slots.size();
   const uint32_t G = frames_per_slot;
   for (auto& sl : ctx->slots) {
-    if (int32_t rc = reset_prefix_state_if_needed(ctx, sl, G + 2)) return rc;
+    if (int32_t rc = clear_prefix_state_if_needed(ctx, sl, G + 2)) return rc;
     if (sl.frame_ring_frames < G) {  // ring + two pinned staging halves, sized for one chain
       MIP_HIP(ctx, hipStreamSynchronize(sl.stream));
       (void)hipFree(sl.d_frame_ring);
@@ -581,7 +581,7 @@ static int32_t run_many_graphed(MipContext* ctx, const MipFrame* frames, uint32_
   }
   if (set)
     for (uint32_t i = 0; i < F; ++i)
-      if (ctx->slots[(set->first_slot + i) % F].last_tag == set->per_slot[i].base_epoch + 1) set = nullptr;  // cannot happen; re-record if it does
+      if (!ctx->slots[(set->first_slot + i) % F].tags.chain_replayable(set->per_slot[i].base_epoch)) set = nullptr;  // cannot happen; re-record if it does
   if (!set) {
     if (ctx->graph_sets.size() >= 4) {
       destroy_graph_set(ctx->graph_sets.front());
@@ -600,21 +600,18 @@ static int32_t run_many_graphed(MipContext* ctx, const MipFrame* frames, uint32_
       for (uint32_t i = 0; i < F; ++i) {
         MipContext::FrameSlot& sl = ctx->slots[(gs.first_slot + i) % F];
         MipContext::FrameGraph& fg = gs.per_slot[i];
-        uint32_t base = sl.epoch > sl.last_tag ? sl.epoch : sl.last_tag;
-        if (sl.zero_buf != 2 && ((base + 1) & 1u) != sl.zero_buf) ++base;
-        fg.base_epoch = base;
+        fg.base_epoch = sl.tags.chain_base();
         MIP_HIP(ctx, hipGraphCreate(&fg.graph, 0));
         hipGraphNode_t prev = nullptr;
         for (uint32_t j = 0; j < G; ++j) {
           const MipOutputs* out = &outputs[(i + j * F) % n_outputs];
+          const mip::LaunchPlan plan = mip::plan_frame(plan_state(ctx), plan_request(out, false));  // validated by mip_run_many
           mip::KernelArgs a{};
-          fill_kernel_args(ctx, sl, &blank, out, true, a);
+          fill_kernel_args(ctx, sl, plan, &blank, out, a);
           a.frame_ring = sl.d_frame_ring + (size_t)j * mip::kFrameWords;
-          a.epoch = base + 1 + j;
+          a.epoch = mip::PrefixTags::chain_tag(fg.base_epoch, j);
           mip::FrameKernelParams params(a);
           hipKernelNodeParams kp{};
-          const mip::LaunchPlan plan = mip::plan_frame(plan_state(ctx), plan_request(out, false));  // validated by mip_run_many
-          a.group_shift = plan.group_shift;
           kp.func = (void*)frame_kernel_of(plan, a.first_mover_rule == 1u);
           kp.gridDim = dim3(plan.n_tiles);
           kp.blockDim = dim3(mip::kTile);
@@ -642,10 +639,9 @@ static int32_t run_many_graphed(MipContext* ctx, const MipFrame* frames, uint32_
     for (uint32_t i = 0; i < F; ++i) {
       MipContext::FrameSlot& sl = ctx->slots[(set->first_slot + i) % F];
       const MipContext::FrameGraph& fg = set->per_slot[i];
-      const uint32_t first_buf = (fg.base_epoch + 1) & 1u;
-      if (sl.zero_buf != 2 && sl.zero_buf != first_buf)  // other launches ran in between: zero the buffer the chain starts in
-        MIP_HIP(ctx, hipMemsetAsync(sl.d_status + ctx->acc1_offset_words + (size_t)first_buf * ctx->groups_cap * mip::kAccStrideWords, 0,
-                                    (size_t)ctx->groups_cap * mip::kAccStrideWords * 8, sl.stream));
+      if (sl.tags.chain_needs_zero(fg.base_epoch))  // other launches ran in between: zero the buffer the chain starts in
+        MIP_HIP(ctx, hipMemsetAsync(sl.d_status + ctx->acc1_offset_words + (size_t)mip::PrefixTags::chain_first_buf(fg.base_epoch) * ctx->groups_cap * mip::kAccStrideWords,
+                                    0, (size_t)ctx->groups_cap * mip::kAccStrideWords * 8, sl.stream));
       // this replay's frames -> a free staging half -> the ring (stream-ordered behind the previous replay)
       const uint32_t half = sl.stage_next;
       sl.stage_next ^= 1u;
@@ -658,9 +654,7 @@ static int32_t run_many_graphed(MipContext* ctx, const MipFrame* frames, uint32_
       MIP_HIP(ctx, hipMemcpyAsync(sl.d_frame_ring, stage, (size_t)G * mip::kFrameWords * 4, hipMemcpyHostToDevice, sl.stream));
       MIP_HIP(ctx, hipEventRecord(sl.stage_free[half], sl.stream));
       MIP_HIP(ctx, hipGraphLaunch(fg.exec, sl.stream));
-      sl.last_tag = fg.base_epoch + G;
-      if (sl.epoch < sl.last_tag) sl.epoch = sl.last_tag;
-      sl.zero_buf = first_buf;  // G is even: the last launch zeroed the buffer the first one uses
+      sl.tags.chain_replayed(fg.base_epoch, G);
       ctx->timings.graph_frames += G;
     }
   ctx->pending_async = true;
@@ -697,11 +691,10 @@ int32_t mip_run_many(MipContext* ctx, const MipFrame* frames, uint32_t n_frames,
       const uint32_t round = (uint32_t)(ctx->graph_round / unit * unit);
       const uint32_t rounds = steps / round;
       if (rounds) {
-        for (uint32_t k = 0; k < n_outputs; ++k)
-          {
-            mip::LaunchPlan plan;
-            if (int32_t rc = plan_for(ctx, &frames[0], &outputs[k], false, &plan)) return rc;
-          }
+        for (uint32_t k = 0; k < n_outputs; ++k) {
+          mip::LaunchPlan plan;
+          if (int32_t rc = plan_for(ctx, &frames[0], &outputs[k], false, &plan)) return rc;
+        }
         if (int32_t rc = bind_device(ctx)) return rc;
         if (int32_t rc = run_many_graphed(ctx, frames, n_frames, 0, outputs, n_outputs, rounds, round / F)) return rc;
         done = rounds * round;
@@ -763,23 +756,18 @@ static int32_t run_views_chunk(MipContext* ctx, const MipFrame* frames, const Mi
     a.bitmap_words = (n + 31u) / 32u;
     a.n_views = n_views;
 #ifdef MIP_DEBUG_STAMPS
-    if (const char* env = std::getenv("MIP_DEBUG_TILE_ORDER"))
-      if (a.n_tiles > 1u && std::strcmp(env, "reverse") == 0) a.debug_tile_mult = a.debug_tile_add = a.n_tiles - 1u;
+    DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add, false);  // (this kernel knows "reverse" only)
 #endif
     for (uint32_t v = 0; v < n_views; ++v) {
       MipContext::FrameSlot& vs = ctx->view_states[v];
-      if (int32_t rc = reset_prefix_state_if_needed(ctx, vs, 2)) return rc;
-      uint32_t e = vs.epoch + 1;
-      if (vs.zero_buf != 2 && (e & 1u) != vs.zero_buf) ++e;
-      vs.epoch = vs.last_tag = e;
-      vs.zero_buf = (e & 1u) ^ 1u;
+      if (int32_t rc = clear_prefix_state_if_needed(ctx, vs, 2)) return rc;
       mip::ViewArgs& w = a.view[v];
       w.status0 = vs.d_status;
       w.acc1 = vs.d_status + ctx->acc1_offset_words;
       w.start1 = vs.d_status + ctx->start1_offset_words;
       w.groups_cap = ctx->groups_cap;
-      w.group_shift = a.n_tiles <= 512 ? 4u : (a.n_tiles <= 2048 ? 5u : 6u);
-      w.epoch = e;
+      w.group_shift = mip::plan_group_shift(a.n_tiles);
+      w.epoch = vs.tags.next_tag();
       w.error_flag = ctx->d_error;
       w.help_counter = ctx->d_help + mip::kHelpShards;
       w.bitmap = outs[v].visible_bitmap;
@@ -796,12 +784,7 @@ static int32_t run_views_chunk(MipContext* ctx, const MipFrame* frames, const Mi
     mip::launch_cull_views(general, a.n_tiles, stream, a);
     MIP_HIP(ctx, hipGetLastError());
   }
-  if (async) {
-    ctx->pending_async = true;
-    return MIP_OK;
-  }
-  MIP_HIP(ctx, hipStreamSynchronize(stream));
-  return check_device_error(ctx);
+  return finish(ctx, stream, async);
 }
 
 int32_t mip_run_views(MipContext* ctx, const MipFrame* frames, const MipOutputs* outs, uint32_t n_views) {
@@ -852,12 +835,7 @@ int32_t mip_light_draw_lists(MipContext* ctx, const float* light_pos_xyz, uint32
     mip::launch_light_draw_lists(aligned, tiles_for(ctx->n), ctx->stream, a);
     MIP_HIP(ctx, hipGetLastError());
   }
-  if (async) {
-    ctx->pending_async = true;
-    return MIP_OK;
-  }
-  MIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return check_device_error(ctx);
+  return finish(ctx, ctx->stream, async != 0);
 }
 
 int32_t mip_wait(MipContext* ctx) {

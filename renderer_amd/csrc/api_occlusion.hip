@@ -1,4 +1,4 @@
-// api_occlusion.hip — C ABI of the instance pipeline, part 5: the occlusion-culling extension (not reference behaviour).
+// api_occlusion.hip — C ABI of the instance pipeline, part 5 of 6: the occlusion-culling extension (not reference behaviour).
 // Depth pyramid builds, and mip_run_occluded: run_frame (api_frame.hip) with the occluded frame kernel in the frame kernel's
 // place, so that outputs, host copies, frame slots and the per-triangle stage behind it are mip_run's own.
 // The kernels (occlusion_kernel.hpp) are instantiated here and only here.
@@ -105,12 +105,7 @@ int32_t mip_build_depth_pyramid(MipContext* ctx, const void* depth, uint32_t wid
   void* params[] = {&a};
   MIP_HIP(ctx, hipLaunchKernel((const void*)mip::mip_depth_pyramid_kernel, dim3(a.blocks), dim3(256), params, 0, sl.stream));
   MIP_HIP(ctx, hipGetLastError());
-  if (async) {
-    ctx->pending_async = true;
-    return MIP_OK;
-  }
-  MIP_HIP(ctx, hipStreamSynchronize(sl.stream));
-  return check_device_error(ctx);
+  return finish(ctx, sl.stream, async != 0);
 }
 
 int32_t mip_run_occluded(MipContext* ctx, const MipFrame* frame, const MipOcclusion* occ, const MipOutputs* out) {

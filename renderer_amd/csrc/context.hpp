@@ -1,6 +1,7 @@
-// context.hpp — the state behind a MipContext and the helpers the four host translation units share.
+// context.hpp — the state behind a MipContext and the helpers the six host translation units share.
 //   api_context.hip   create / destroy, uploads (mesh table, instances, geometry, skeleton, poses), census, diagnostics
-//   api_frame.hip     one frame: plan (frame_plan.hpp) -> launches; recorded launch graphs; views; light lists; mip_wait
+//   api_frame.hip     one frame: plan (frame_plan.hpp) -> tag (prefix_tags.hpp) -> launches; the per-triangle stage's host side;
+//                     recorded launch graphs; views; light lists; mip_wait
 //   api_sharded.hip   shard merges, the collective-library seam, mip_run_sharded and its collective repair
 //   api_interop.hip   external memory and external semaphores (row f-2)
 //   api_occlusion.hip the occlusion-culling extension: depth pyramid builds, mip_run_occluded (occlusion_kernel.hpp)
@@ -10,6 +11,7 @@
 
 #include "../../include/mi_instance_pipeline.h"
 #include "frame_plan.hpp"
+#include "prefix_tags.hpp"
 #include "instance_kernel.hpp"  // rows a-1 .. a-7 (the kernel itself is instantiated in api_frame.hip and stages_tu.hip only)
 #include "stage_args.hpp"      // argument blocks + launchers of everything built in stages_tu.hip
 
@@ -67,10 +69,7 @@ struct MipContext {
     uint32_t* h_frame_stage = nullptr;
     uint32_t frame_ring_frames = 0, stage_next = 0;
     hipEvent_t stage_free[2] = {nullptr, nullptr};
-    uint32_t epoch = 0;         // highest tag handed out on this state
-    uint32_t last_tag = 0;      // tag of the last launch (what the level-0 words hold now)
-    uint32_t zero_buf = 2;      // which accumulator buffer is all-zero now: 0, 1, or 2 = both
-    bool status_dirty = false;  // instance count changed: clear the prefix state before the next launch
+    mip::PrefixTags tags;       // which tag the next launch on d_status gets (prefix_tags.hpp)
   };
   // mip_run_many replays: per slot one linear hipGraph of `frames` launches with baked tags
   // base_epoch+1 .. base_epoch+frames (see run_many_graphed).
@@ -229,8 +228,36 @@ int32_t fail(MipContext* ctx, int32_t code, const char* fmt, ...) __attribute__(
   } while (0)
 
 inline uint32_t tiles_for(uint32_t n) { return (n + mip::kTile - 1) / mip::kTile; }
+inline size_t instance_cap(const MipContext* ctx) { return ctx->max_instances ? ctx->max_instances : 1; }  // what per-instance scratch is sized by
 static_assert(mip::kPlanTile == mip::kTile && mip::kPlanTriParts == mip::kTriParts && mip::kPlanTriPartMaxT == mip::kTriPartMaxT,
               "frame_plan.hpp restates kernel constants");
+static_assert(mip::kPlanMaxEpoch == mip::kMaxEpoch, "prefix_tags.hpp restates the kernel's largest tag");
+
+#ifdef MIP_DEBUG_STAMPS
+// The diagnostic build's fault-injection switches (never the product), read from the environment by every launch (a test
+// sets them between launches): the outputs must come out byte-identical whatever they say.
+//   MIP_DEBUG_TILE_ORDER=reverse|scramble  a permutation tile -> (tile * mult + add) % n_tiles of the tile numbers (workgroups
+//                                          then start in an order that is anything but ascending); reverse: the per-triangle
+//                                          stage takes its work items from the last one down as well
+//   MIP_DEBUG_SKIP_PART=k                  part k of every command (range k of every 16, every fourth re-compaction workgroup)
+//                                          never publishes: its successors count it themselves
+struct DebugSwitches {
+  const char* order = std::getenv("MIP_DEBUG_TILE_ORDER");
+  const char* skip = std::getenv("MIP_DEBUG_SKIP_PART");
+  bool reverse() const { return order && std::strcmp(order, "reverse") == 0; }
+  uint32_t skip_part(uint32_t parts) const { return skip ? (uint32_t)std::atoi(skip) % parts + 1u : 0u; }  // 0 = off
+  void tile_order(uint32_t t, uint32_t& mult, uint32_t& add, bool can_scramble = true) const {
+    if (t > 1u && reverse()) {
+      mult = add = t - 1u;
+    } else if (t > 1u && can_scramble && order && std::strcmp(order, "scramble") == 0) {
+      static const uint32_t primes[] = {7919u, 104729u, 1299709u, 15485863u};
+      for (uint32_t p : primes)
+        if (t % p != 0u) { mult = p; break; }  // a prime that does not divide t is coprime to it
+      add = 12345u % t;
+    }
+  }
+};
+#endif
 
 int32_t bind_device(MipContext* ctx);
 int32_t sync_all(MipContext* ctx);
@@ -241,6 +268,12 @@ int32_t check_device_error(MipContext* ctx);
 // outside a table of `m` entries. Synchronous.
 int32_t census(MipContext* ctx, uint32_t first, uint32_t count, uint32_t* out, uint32_t* bad_ids = nullptr, uint32_t m = 0);
 void drop_graphs(MipContext* ctx);                    // api_frame.hip
+// The tail of every entry point that enqueues on `stream`: asynchronous calls leave it to mip_wait, the others drain it.
+inline int32_t finish(MipContext* ctx, hipStream_t stream, bool async) {
+  if (async) { ctx->pending_async = true; return MIP_OK; }
+  MIP_HIP(ctx, hipStreamSynchronize(stream));
+  return check_device_error(ctx);
+}
 int32_t repair_sharded_overflow(MipContext* ctx);     // api_sharded.hip
 void comm_release(MipContext* ctx);                   // api_sharded.hip: communicator + buffers, for mip_destroy
 void interop_release(MipContext* ctx);                // api_interop.hip: imported memory and semaphores, for mip_destroy

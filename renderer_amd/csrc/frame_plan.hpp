@@ -89,6 +89,9 @@ struct LaunchPlan {
 
 inline uint32_t plan_tiles_for(uint32_t n) { return (n + kPlanTile - 1u) / kPlanTile; }
 
+// log2(tiles per level-1 group of the cross-tile prefix state): every kernel that carries one (frame, occluded, views)
+inline uint32_t plan_group_shift(uint32_t n_tiles) { return n_tiles <= 512u ? 4u : (n_tiles <= 2048u ? 5u : 6u); }
+
 inline int plan_wire_form(uint32_t out_flags) { return (out_flags & MIP_OUT_WIRE) ? ((out_flags & MIP_OUT_WIRE_PACKED) ? 2 : 1) : 0; }
 
 // mip_wire_index_bits, restated here so that the plan has no link-time dependency (test_abi.py checks both against the header's formula)
@@ -193,7 +196,7 @@ inline LaunchPlan plan_frame(const PlanState& st, const PlanRequest& rq) {
   p.box_override = rq.skinned;
   p.general = rq.skinned || st.nonfinite || st.force_general;  // a per-instance box may be non-finite
   p.wire = device_out ? plan_wire_form(rq.flags) : 0;
-  p.group_shift = p.n_tiles <= 512u ? 4u : (p.n_tiles <= 2048u ? 5u : 6u);
+  p.group_shift = plan_group_shift(p.n_tiles);
   p.uses_prefix_state = rq.cmds;
   if (rq.skinned) {
     p.skin = true;

@@ -19,11 +19,28 @@ def test_plan_frame_invariants_over_every_combination(tmp_path):
     assert int(last.split()[2]) > 5_000_000  # the sweep really ran
 
 
+def test_prefix_tag_rule_over_call_sequences(tmp_path):
+    """PrefixTags (renderer_amd/csrc/prefix_tags.hpp), the rule that hands out the tags of the cross-tile prefix state: direct
+    launches, recorded chains of every even length and their replays, clears forced by a new instance count, starts up to the
+    tag wrap — against a model of the two accumulator buffers. A wrong tag on the GPU is not a crash, it is wrong command bytes."""
+    exe = str(tmp_path / "prefix_tags_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "native", "prefix_tags_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    last = out.stdout.strip().split("\n")[-1]
+    assert last.startswith("TAGS OK"), out.stdout[-2000:]
+    assert int(last.split()[2]) > 4_000_000  # the sweep really ran
+
+
 def test_plan_header_has_no_hip_dependency():
-    """frame_plan.hpp must stay compilable by a plain host compiler: that is what keeps the decision table testable here."""
-    text = open(os.path.join(ROOT, "renderer_amd", "csrc", "frame_plan.hpp")).read()
-    assert "hip/" not in text and "__device__" not in text and "__global__" not in text
+    """frame_plan.hpp and prefix_tags.hpp must stay compilable by a plain host compiler: that is what keeps the decision table
+    and the tag rule testable here."""
+    for header in ("frame_plan.hpp", "prefix_tags.hpp"):
+        text = open(os.path.join(ROOT, "renderer_amd", "csrc", header)).read()
+        assert "hip/" not in text and "__device__" not in text and "__global__" not in text, header
     api = open(os.path.join(ROOT, "renderer_amd", "csrc", "api_frame.hip")).read()
     # the launch code takes the kernel, the grids and the scratch from the plan
-    for field in ("plan.n_tiles", "plan.tri_blocks", "plan.recompact_blocks", "plan.skin_blocks", "frame_kernel_of(plan, ", "plan.need_tri_scratch"):
+    for field in ("plan.n_tiles", "plan.tri_blocks", "plan.recompact_blocks", "plan.skin_blocks", "frame_kernel_of(plan, ", "plan.need_tri_scratch",
+                  "plan.need_part_status", "plan.need_chunk_scratch"):
         assert field in api, field
