@@ -343,7 +343,9 @@ int32_t mip_light_draw_lists(MipContext* ctx, const float* light_pos_xyz, uint32
 /* ---- Extension: skinned instances (BASELINE config 5) ----------------------------------------
  * NOT a reference behaviour: farnoy/renderer has no skins, joints or animation (SURVEY.md
  * section 8, top table). Specified from glTF 2.0 section 3.7.3 and checked against this repository's
- * oracle only. One skeleton per context, shared by every instance:
+ * oracle, which is itself pinned to a float64 evaluation of that definition within a derived float32
+ * rounding bound (tests/float64_reference.py, skinned_reference). One skeleton per context, shared by
+ * every instance:
  *   parent[k]        index of the parent joint, < k, or -1 (parents precede children)
  *   inverse_bind     n_joints x 16 floats, column-major mat4 (skin.inverseBindMatrices; rows 0..2 used)
  *   joint_box        n_joints x 6 floats: min xyz, max xyz of the bind-pose vertices weighted to
@@ -359,12 +361,15 @@ int32_t mip_set_skeleton(MipContext* ctx, const int32_t* parent, const float* in
  * flight). device != 0: a DEVICE pointer (8-byte aligned) that is borrowed, not copied; the call does not
  * wait for anything — frames already queued keep the pointer they were launched with, so an animation
  * system can alternate two buffers with frames_in_flight = 2. It keeps each buffer alive and unmodified
- * while a frame that reads it is in flight. */
+ * while a frame that reads it is in flight. A device pointer that is not 8-byte aligned is refused with
+ * MIP_ERR_INVALID_ARGUMENT. */
 int32_t mip_set_poses(MipContext* ctx, const void* joint_trs, uint32_t n, int32_t device);
 
 /* One frame of skinned instances. Per instance and joint
  *   L_k = T*R*S of the pose, G_k = G_parent * L_k, J_k = G_k * inverse_bind_k   (affine, fp32)
- * the palette (n x n_joints mat4, column-major, DEVICE pointer, may be NULL) receives J_k. The
+ * the palette (n x n_joints mat4, column-major, DEVICE pointer, may be NULL) receives J_k. It must be
+ * 16-byte aligned (it is written in 16-byte stores); one that is not is refused with
+ * MIP_ERR_INVALID_ARGUMENT before anything is enqueued. The
  * union over joints of J_k * joint_box_k (8 corners each) is the instance's posed box in mesh
  * space; it takes the place of the mesh table's aabb for that instance, and everything else —
  * model[], world box, frustum test, bitmap, draw commands, count, TLAS rows — is produced from

@@ -473,32 +473,20 @@ int32_t mip_set_skeleton(MipContext* ctx, const int32_t* parent, const float* in
   static_assert(MIP_MAX_JOINTS == mip::kMaxJoints && MIP_POSE_FLOATS == mip::kPoseWords, "skinning limits");
   if (n_joints == 0 || n_joints > MIP_MAX_JOINTS)
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "n_joints %u outside 1..%u", n_joints, (unsigned)MIP_MAX_JOINTS);
+  // the depth order and the per-level look-ups the kernel walks: a pure function, enumerated on the CPU (skin_plan.hpp)
+  static_assert(mip::kPlanMaxJoints == mip::kMaxJoints && mip::kPlanSkinBlock == mip::kSkinBlock, "skin_plan.hpp restates these");
+  const mip::SkinPlan plan = mip::plan_skeleton(parent, n_joints);
+  if (!plan.ok)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "joint %u: parent %d must be -1 or an earlier joint", plan.bad_joint, parent[plan.bad_joint]);
   std::vector<mip::JointEntry> joints(n_joints);
-  std::vector<uint32_t> depth(n_joints);
-  uint32_t max_depth = 0;
   for (uint32_t k = 0; k < n_joints; ++k) {
-    if (parent[k] >= (int32_t)k || parent[k] < -1)
-      return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "joint %u: parent %d must be -1 or an earlier joint", k, parent[k]);
     mip::JointEntry& j = joints[k];
     for (int c = 0; c < 4; ++c)
       for (int r = 0; r < 3; ++r) j.ibm[c * 3 + r] = inverse_bind[(size_t)k * 16 + c * 4 + r];
     std::memcpy(j.box, joint_box + (size_t)k * 6, sizeof j.box);
     j.parent = parent[k];
-    depth[k] = parent[k] < 0 ? 0u : depth[parent[k]] + 1u;
-    if (depth[k] > max_depth) max_depth = depth[k];
+    j.sorted = plan.sorted[k];
   }
-  // joints in depth order (stable): level d owns sorted entries [level_start[d], level_start[d+1])
-  uint8_t level_start[mip::kMaxJoints + 2] = {0};
-  uint32_t level_inv[mip::kMaxJoints + 1] = {0};
-  uint32_t at = 0;
-  for (uint32_t d = 0; d <= max_depth; ++d) {
-    level_start[d] = (uint8_t)at;
-    for (uint32_t k = 0; k < n_joints; ++k)
-      if (depth[k] == d) joints[at++].sorted = k | ((uint32_t)(parent[k] < 0 ? 0 : parent[k]) << 8);
-    const uint32_t cnt = at - level_start[d];
-    level_inv[d] = (65536u + cnt - 1u) / cnt;
-  }
-  for (uint32_t d = max_depth + 1; d < mip::kMaxJoints + 2; ++d) level_start[d] = (uint8_t)at;
   if (int32_t rc = bind_device(ctx)) return rc;
   if (int32_t rc = sync_all(ctx)) return rc;
   if (!ctx->d_joints) MIP_HIP(ctx, hipMalloc(&ctx->d_joints, sizeof(mip::JointEntry) * MIP_MAX_JOINTS));
@@ -509,7 +497,7 @@ int32_t mip_set_skeleton(MipContext* ctx, const int32_t* parent, const float* in
     ctx->poses_n = 0;
   }
   ctx->n_joints = n_joints;
-  ctx->max_joint_depth = max_depth;
+  ctx->max_joint_depth = plan.max_depth;
   {
     float box_max = 0.0f;
     bool finite = true;
@@ -519,8 +507,9 @@ int32_t mip_set_skeleton(MipContext* ctx, const int32_t* parent, const float* in
     }
     ctx->joint_box_bound = finite ? 3.0f * box_max + 1.0f : INFINITY;
   }
-  std::memcpy(ctx->joint_level_start, level_start, sizeof level_start);
-  std::memcpy(ctx->joint_level_inv, level_inv, sizeof level_inv);
+  static_assert(sizeof ctx->joint_level_start == sizeof plan.level_start && sizeof ctx->joint_level_inv == sizeof plan.level_inv, "skin tables");
+  std::memcpy(ctx->joint_level_start, plan.level_start, sizeof plan.level_start);
+  std::memcpy(ctx->joint_level_inv, plan.level_inv, sizeof plan.level_inv);
   return MIP_OK;
 }
 
@@ -530,6 +519,8 @@ int32_t mip_set_poses(MipContext* ctx, const void* joint_trs, uint32_t n, int32_
   if (!ctx->have_instances || n != ctx->n) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "%u poses for %u instances", n, ctx->n);
   if (!joint_trs && n) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "joint_trs is NULL");
   if (device) {
+    // the kernel reads a pose as five 8-byte loads (skinning_kernel.hpp): refused here, before anything is enqueued
+    if ((uintptr_t)joint_trs & 7u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "device joint_trs %p is not 8-byte aligned", joint_trs);
     // borrowed: nothing is copied and nothing in flight is touched — frames already queued keep the
     // pointer they were launched with, so an animation system can alternate two buffers
     ctx->d_poses = (const float*)joint_trs;

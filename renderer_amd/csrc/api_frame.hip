@@ -407,7 +407,7 @@ int32_t enqueue_skinned_bounds(MipContext* ctx, MipContext::FrameSlot& sl, const
   k.n_joints = ctx->n_joints;
   k.max_depth = ctx->max_joint_depth;
   k.box_bound = ctx->joint_box_bound;
-  k.inv_joints = (65536u + ctx->n_joints - 1u) / ctx->n_joints;
+  k.inv_joints = mip::skin_inv_joints(ctx->n_joints);
   std::memcpy(k.level_start, ctx->joint_level_start, sizeof k.level_start);
   std::memcpy(k.level_inv, ctx->joint_level_inv, sizeof k.level_inv);
   mip::launch_skinned_bounds(plan.skin_blocks, stream, k);
@@ -807,6 +807,8 @@ int32_t mip_run_skinned(MipContext* ctx, const MipFrame* frame, const MipOutputs
   if (out->culled_index_buffer) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "the per-triangle stage does not skin vertices");
   if (!ctx->n_joints || ctx->poses_n != ctx->n || (ctx->n && !ctx->d_poses))
     return fail(ctx, MIP_ERR_NOT_READY, "skeleton or poses not set for the resident instances");
+  // palette entries leave as 16-byte stores (skinning_kernel.hpp): refused here, before anything is enqueued
+  if ((uintptr_t)palette & 15u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "palette %p is not 16-byte aligned", palette);
   if (int32_t rc = bind_device(ctx)) return rc;
   return run_frame(ctx, frame, out, true, palette);
 }

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/mi_instance_pipeline.h"
+#include "skin_plan.hpp"
 
 namespace mip {
 
@@ -167,7 +168,7 @@ inline LaunchPlan plan_frame(const PlanState& st, const PlanRequest& rq) {
   }
   if (rq.tlas && !device_out) return plan_refuse(MIP_ERR_INVALID_ARGUMENT, "tlas_instances needs MIP_OUT_DEVICE");
   if (rq.skinned && !device_out) return plan_refuse(MIP_ERR_INVALID_ARGUMENT, "mip_run_skinned needs MIP_OUT_DEVICE outputs");
-  if (rq.skinned && (st.n_joints == 0 || st.n_joints > 32u)) return plan_refuse(MIP_ERR_NOT_READY, "skeleton or poses not set for the resident instances");
+  if (rq.skinned && (st.n_joints == 0 || st.n_joints > kPlanMaxJoints)) return plan_refuse(MIP_ERR_NOT_READY, "skeleton or poses not set for the resident instances");
 
   LaunchPlan p;
   p.device_out = device_out;
@@ -200,8 +201,7 @@ inline LaunchPlan plan_frame(const PlanState& st, const PlanRequest& rq) {
   p.uses_prefix_state = rq.cmds;
   if (rq.skinned) {
     p.skin = true;
-    const uint32_t per_block = 4u * (64u / st.n_joints);
-    p.skin_blocks = (n + per_block - 1u) / per_block;
+    p.skin_blocks = skin_blocks_for(n, st.n_joints);  // skin_plan.hpp: four waves of floor(64 / J) instances
   }
   if (rq.triangles) {
     // The command count lives on the device; the instance count bounds it.

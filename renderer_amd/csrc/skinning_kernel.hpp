@@ -12,7 +12,13 @@ namespace mip {
 // Extension (BASELINE config 5): skinned instances — joint palette + posed mesh-space box
 // ---------------------------------------------------------------------------------------
 // The reference has no skinning: this is specified from glTF 2.0
-// (section 3.7.3, skins) and checked against this repository's oracle only (orc_skinned_bounds).
+// (section 3.7.3, skins) and checked against this repository's oracle (orc_skinned_bounds), which tests/test_oracle.py pins to
+// a float64 evaluation of the same definition within a derived float32 rounding bound (tests/float64_reference.py,
+// skinned_reference) on the very inputs tests/test_gpu_skinned_edges.py runs this kernel on: every joint count at every
+// edge of the lane mapping, chain / star / forest / comb hierarchies, the guard of the separable fold from finite inputs.
+// The integer tables it walks (depth order, level words, both multiply-shift divisions) are built and enumerated on the CPU:
+// skin_plan.hpp, tests/native/skin_plan_check.cpp. Pointers: poses 8-byte, palette 16-byte aligned (refused otherwise by
+// mip_set_poses / mip_run_skinned).
 //   L_k = T(t_k) * R(q_k) * S(s_k)           the animated LOCAL transform of joint k
 //   G_k = G_parent(k) * L_k                  (roots: G_k = L_k; parents precede children)
 //   J_k = G_k * inverseBind_k                the palette entry the vertex shader blends

@@ -77,3 +77,86 @@ def triangle_decisions(model, pv, v, k=TRIANGLE_K):
             & (np.abs(w) > k * u * mag[..., 3]).all(axis=1) \
             & np.isfinite(clip).all(axis=(1, 2))
     return culled, decided
+
+
+# ---- extension, BASELINE config 5: the joint palette and the posed box (glTF 2.0 section 3.7.3) ----------------------
+#
+# skinned_reference evaluates the DEFINITION in float64 from the float32 inputs — L = T R S, G_k = G_parent L_k,
+# J_k = G_k IBM_k, the union of the eight transformed corners per non-empty joint box — vectorised over the instances and
+# independent of the oracle's loop. Beside every quantity it evaluates the same expression with every term replaced by its
+# absolute value: the running bound A of the float32 chain. With u = 2^-24, a float32 evaluation whose terms pass through at
+# most k roundings differs from the exact value by at most k u / (1 - k u) * A (Higham, Accuracy and Stability, lemma 3.1):
+#   * quaternion -> rotation -> scale: a diagonal entry is four products and three additions, then the scale: at most 8;
+#   * every affine product on the path from the root, and the inverse-bind product: (a0 b0 + a1 b1) + a2 b2 (+ a3), a
+#     product, two additions and the translation's: 4 per product, over depth_k + 2 products at the most;
+#   so k = 4 (depth_k + 2) + 8 for palette entry J_k, and 4 more for a corner J_k (x, y, z, 1). min / max are 1-Lipschitz:
+#   a component of the posed box is within the largest of its corners' bounds.
+SKIN_U = 2.0 ** -24
+
+
+def skin_rounding_bound(k, a):
+    return (k * SKIN_U) / (1.0 - k * SKIN_U) * a
+
+
+def _trs_and_bound(poses):
+    """poses (n, J, 10) -> L, |L| as (n, J, 3, 4) row-major affine matrices."""
+    p = np.asarray(poses, np.float64)
+    t, s = p[..., 0:3], p[..., 7:10]
+    i, j, k, w = (p[..., 3 + c] for c in range(4))
+    R = np.empty(p.shape[:2] + (3, 3))
+    A = np.empty_like(R)
+    sq = (w * w, i * i, j * j, k * k)
+    R[..., 0, 0] = sq[0] + sq[1] - sq[2] - sq[3]; R[..., 1, 1] = sq[0] - sq[1] + sq[2] - sq[3]; R[..., 2, 2] = sq[0] - sq[1] - sq[2] + sq[3]
+    R[..., 0, 1] = 2 * (i * j - w * k); R[..., 0, 2] = 2 * (w * j + i * k)
+    R[..., 1, 0] = 2 * (w * k + i * j); R[..., 1, 2] = 2 * (j * k - w * i)
+    R[..., 2, 0] = 2 * (i * k - w * j); R[..., 2, 1] = 2 * (w * i + j * k)
+    A[..., 0, 0] = A[..., 1, 1] = A[..., 2, 2] = sq[0] + sq[1] + sq[2] + sq[3]
+    A[..., 0, 1] = A[..., 1, 0] = 2 * (np.abs(i * j) + np.abs(w * k))
+    A[..., 0, 2] = A[..., 2, 0] = 2 * (np.abs(w * j) + np.abs(i * k))
+    A[..., 1, 2] = A[..., 2, 1] = 2 * (np.abs(j * k) + np.abs(w * i))
+    L = np.concatenate([R * s[..., None, :], t[..., :, None]], axis=-1)
+    LA = np.concatenate([A * np.abs(s)[..., None, :], np.abs(t)[..., :, None]], axis=-1)
+    return L, LA
+
+
+def _affine(a, b):
+    """(.., 3, 4) x (.., 3, 4) as affine transforms (bottom row 0 0 0 1)."""
+    out = a[..., :, :3] @ b
+    out[..., :, 3] += a[..., :, 3]
+    return out
+
+
+CORNERS = ((0, 1, 2), (3, 1, 2), (0, 1, 5), (3, 1, 5), (0, 4, 2), (3, 4, 2), (0, 4, 5), (3, 4, 5))  # (x, y, z) picks out of min xyz max xyz
+
+
+def skinned_reference(skeleton, poses):
+    """float64: palette (n, J, 3, 4) row-major, posed box (n, 6) = min xyz, max xyz over the non-empty joint boxes (+inf /
+    -inf where there is none), and their float32 rounding bounds palette_tol / box_tol, element for element."""
+    parent = np.asarray(skeleton["parent"])
+    J = len(parent)
+    ibm = np.asarray(skeleton["inverse_bind"], np.float64).reshape(J, 4, 4).transpose(0, 2, 1)[:, :3, :]  # column-major mat4 -> rows 0..2
+    box = np.asarray(skeleton["joint_box"], np.float64).reshape(J, 6)
+    L, LA = _trs_and_bound(poses)
+    n = L.shape[0]
+    G, GA = L.copy(), LA.copy()
+    depth = np.zeros(J, int)
+    for k in range(J):
+        if parent[k] >= 0:
+            depth[k] = depth[parent[k]] + 1
+            G[:, k], GA[:, k] = _affine(G[:, parent[k]], L[:, k]), _affine(GA[:, parent[k]], LA[:, k])
+    palette = _affine(G, ibm[None])
+    palette_a = _affine(GA, np.abs(ibm)[None])
+    kk = 4.0 * (depth + 2) + 8.0
+    palette_tol = skin_rounding_bound(kk[None, :, None, None], palette_a)
+    lo, hi = np.full((n, 3), np.inf), np.full((n, 3), -np.inf)
+    tol = np.zeros((n, 3))
+    for k in range(J):
+        b = box[k]
+        if b[0] > b[3] or b[1] > b[4] or b[2] > b[5]:
+            continue  # the joint binds no vertex
+        for pick in CORNERS:
+            c = np.array([b[pick[0]], b[pick[1]], b[pick[2]], 1.0])
+            v = palette[:, k] @ c
+            lo, hi = np.minimum(lo, v), np.maximum(hi, v)
+            tol = np.maximum(tol, skin_rounding_bound(kk[k] + 4.0, palette_a[:, k] @ np.abs(c)))
+    return dict(palette=palette, palette_tol=palette_tol, box=np.concatenate([lo, hi], axis=1), box_tol=np.concatenate([tol, tol], axis=1))

@@ -33,10 +33,26 @@ def test_prefix_tag_rule_over_call_sequences(tmp_path):
     assert int(last.split()[2]) > 4_000_000  # the sweep really ran
 
 
+def test_skin_plan_tables_over_every_small_skeleton(tmp_path):
+    """plan_skeleton (renderer_amd/csrc/skin_plan.hpp), the integer tables the skinning kernel walks: every legal parent array
+    of up to seven joints, the hierarchy families of tests/skinned_cases.py and seeded random arrays for 8 .. 32 joints — the
+    depth order, the packed words, both multiply-shift divisions, and the kernel's level walk replayed with integer labels
+    against the parent-order recursion. A wrong table on the GPU is not a crash, it is a joint composed with the wrong parent."""
+    exe = str(tmp_path / "skin_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "native", "skin_plan_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    last = out.stdout.strip().split("\n")[-1]
+    assert last.startswith("SKIN OK"), out.stdout[-2000:]
+    assert int(last.split()[3]) == 5913               # every legal parent array of 1 .. 7 joints
+    assert int(last.split()[2]) >= 5913 + 25 * 164    # 8 .. 32 joints: four families + 160 random arrays each: the sweep really ran
+
+
 def test_plan_header_has_no_hip_dependency():
-    """frame_plan.hpp and prefix_tags.hpp must stay compilable by a plain host compiler: that is what keeps the decision table
-    and the tag rule testable here."""
-    for header in ("frame_plan.hpp", "prefix_tags.hpp"):
+    """frame_plan.hpp, prefix_tags.hpp and skin_plan.hpp must stay compilable by a plain host compiler: that is what keeps the
+    decision table, the tag rule and the skeleton tables testable here."""
+    for header in ("frame_plan.hpp", "prefix_tags.hpp", "skin_plan.hpp"):
         text = open(os.path.join(ROOT, "renderer_amd", "csrc", header)).read()
         assert "hip/" not in text and "__device__" not in text and "__global__" not in text, header
     api = open(os.path.join(ROOT, "renderer_amd", "csrc", "api_frame.hip")).read()

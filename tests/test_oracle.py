@@ -415,6 +415,110 @@ def test_skinned_extension_against_float64(oracle_mod):
                                dict(sk, parent=np.array([0] + list(sk["parent"][1:]), np.int32)), bind, s["planes"], s["cam_pos"])
 
 
+def _assert_skinned_within_rounding(got, sk, poses, what, box_rows=None):
+    """Every palette entry of every instance, and every posed-box component of the rows in box_rows (default: all), within
+    the float32 rounding bound of the float64 definition (float64_reference.skinned_reference: derived, not chosen)."""
+    import float64_reference as f64
+
+    ref = f64.skinned_reference(sk, poses)
+    n, j = poses.shape[:2]
+    pal = got["palette"].reshape(n, j, 4, 4).transpose(0, 1, 3, 2).astype(np.float64)
+    assert np.array_equal(pal[:, :, 3, :], np.broadcast_to([0.0, 0.0, 0.0, 1.0], (n, j, 4))), what
+    err = np.abs(pal[:, :, :3, :] - ref["palette"])
+    bad = np.argwhere(~(err <= ref["palette_tol"]))
+    assert len(bad) == 0, f"{what}: {len(bad)} palette entries outside the bound, first (instance, joint, row, column) {bad[:3].tolist()}"
+    rows = np.arange(n) if box_rows is None else np.nonzero(box_rows)[0]
+    err = np.abs(got["local_box"][rows].astype(np.float64) - ref["box"][rows])
+    bad = np.argwhere(~(err <= ref["box_tol"][rows]))
+    assert len(bad) == 0, f"{what}: {len(bad)} posed-box components outside the bound, first (row, component) {bad[:3].tolist()}"
+    return ref
+
+
+def _run_skinned_case(oracle_mod, s, sk, poses):
+    return oracle_mod.run_skinned(s["pos"], s["rot"], s["scale"], s["mesh_id"], s["meshes"], sk, poses, s["planes"], s["cam_pos"])
+
+
+@pytest.mark.parametrize("j", [1, 2, 3, 21, 32])
+def test_skinned_families_against_float64_rounding_bound(oracle_mod, j):
+    """The inputs tests/test_gpu_skinned_edges.py runs the kernel on (tests/skinned_cases.py): on every one of them the
+    oracle is the float64 definition up to float32 rounding, element for element, no instance left out — so a kernel that
+    equals the oracle there equals glTF's skinning, and one that does not has a bug of its own."""
+    import skinned_cases as sc
+
+    for family in sc.FAMILIES:
+        sk, poses = sc.family_case(family, j)
+        got = _run_skinned_case(oracle_mod, sc.instances(len(poses)), sk, poses)
+        ref = _assert_skinned_within_rounding(got, sk, poses, f"{family} J={j}")
+        assert np.isfinite(ref["box"]).all() and np.isfinite(got["local_box"]).all()   # every case has a non-empty joint box
+
+
+def test_skinned_guard_bands_against_float64_rounding_bound(oracle_mod):
+    """The guard-band launch (finite inputs; one joint box reaches 1e18, that joint's scale runs over five decades): the three
+    bands exist by the ORACLE's own outputs, and in the two finite ones the oracle is within rounding of float64. Where
+    float32 products overflow, and for non-finite joint boxes, the oracle IS the definition (f32 overflow, f32::min / max
+    ignoring a NaN): float64 is not consulted, only the properties that follow from those rules."""
+    import skinned_cases as sc
+
+    n = 600
+    sk, poses, s = sc.guard_skeleton(), sc.guard_poses(n), sc.guard_instances(n)
+    assert np.isfinite(poses).all() and np.isfinite(sk["joint_box"]).all() and np.isfinite(sk["inverse_bind"]).all()
+    got = _run_skinned_case(oracle_mod, s, sk, poses)
+    bands = sc.guard_bands(sk, got)     # asserts a tenth of the instances in each
+    finite = np.isfinite(got["local_box"]).all(axis=1)
+    assert np.isfinite(got["palette"]).all()
+    assert (bands["separable"] | bands["corner"] <= finite).all()
+    _assert_skinned_within_rounding(got, sk, poses, "guard bands", box_rows=finite)   # both finite bands, and what lies between them
+    # one wave of the kernel (12 instances) holds several bands, and whole waves sit below the guard
+    band_of = np.where(bands["separable"], 1, 0) + np.where(bands["corner"], 2, 0) + np.where(bands["overflow"], 4, 0)
+    waves = [set(band_of[w:w + 12].tolist()) - {0} for w in range(0, n, 12)]
+    assert any(len(w) == 3 for w in waves) and sum(w == {1} for w in waves) >= 3
+    # overflow band: the big joint's products left float32's range, and min / max carried the infinity into the box
+    over = got["local_box"][bands["overflow"]]
+    assert np.isinf(over).any(axis=1).all()
+    for name, bad_sk in sc.nonfinite_box_skeletons().items():
+        m = 109
+        r = _run_skinned_case(oracle_mod, sc.instances(m), bad_sk, poses[:m] * np.float32(1.0))
+        assert np.isinf(sc.box_bound(bad_sk)), name
+        box = r["local_box"]
+        if name == "inf_max":    # the infinite maximum reaches every instance's box (as +-inf, or NaN beside it ignored)
+            assert (~np.isfinite(box)).any(axis=1).all(), name
+        else:                    # a NaN corner coordinate is ignored by min / max: the other joints' corners still bound the box
+            assert not np.isnan(box).any(), name
+
+
+def test_separable_box_fold_equals_the_corner_fold_in_float32():
+    """The skinning kernel folds a joint box without its corners (sum of the three smaller / larger products) while a guard on
+    the magnitudes holds, and over the eight corners otherwise. Restated here in float32 on adversarial values — zeros of
+    both signs, 1e18 .. 3.4e38, infinities, NaNs in the matrix and in the box: behind the joint fold (seeds +-FLT_MAX, a NaN
+    operand ignored) the two agree for EVERY input, not only below the guard: the extreme corner is evaluated by the same
+    expression in both, rounding and overflow are monotone, and where it is NaN every rival corner is -inf, NaN or loses to
+    the seed. So the guard selects a cheaper path, never another result — which is why raising its constant, or forcing the
+    separable fold, changes no output of the GPU tests, and why none of them can be made to notice."""
+    rng = np.random.default_rng(1)
+    n = 200_000
+    vals = np.array([0.0, -0.0, 1e-30, -1e-30, 0.3, -0.7, 1.0, -1.0, 1e18, -1e18, 1e20, -1e20, 2e38, -2e38, 3.4e38, -3.4e38,
+                     np.inf, -np.inf, np.nan], np.float32)
+    fmax_ = np.float32(3.40282347e+38)
+
+    with np.errstate(all="ignore"):
+        def pick(*shape):
+            return (vals[rng.integers(0, len(vals), shape)] * rng.choice(np.array([1, 1, 0.5, 1.5], np.float32), shape)).astype(np.float32)
+
+        m, a, b = pick(n, 3, 4), pick(n, 3), pick(n, 3)
+        lo_b, hi_b = np.fmin(a, b), np.where(rng.random((n, 3)) < 0.05, np.float32(np.nan), np.fmax(a, b))  # never "empty" by the > test
+        clo, chi = np.full((n, 3), fmax_, np.float32), np.full((n, 3), -fmax_, np.float32)
+        for c in range(8):
+            x, z, y = (np.where(c & bit, hi_b[:, ax], lo_b[:, ax])[:, None] for bit, ax in ((1, 0), (2, 2), (4, 1)))
+            v = ((m[:, :, 0] * x + m[:, :, 1] * y) + m[:, :, 2] * z) + m[:, :, 3]
+            clo, chi = np.fmin(clo, v), np.fmax(chi, v)
+        p = [(m[:, :, ax] * lo_b[:, None, ax], m[:, :, ax] * hi_b[:, None, ax]) for ax in range(3)]
+        slo = ((np.fmin(*p[0]) + np.fmin(*p[1])) + np.fmin(*p[2])) + m[:, :, 3]
+        shi = ((np.fmax(*p[0]) + np.fmax(*p[1])) + np.fmax(*p[2])) + m[:, :, 3]
+        assert m.dtype == slo.dtype == clo.dtype == np.float32
+        assert np.isnan(slo).any() and np.isinf(slo).any() and (np.isnan(slo) != np.isnan(clo)).any()   # the lanes do differ ...
+        assert same_floats(np.fmin(fmax_, clo), np.fmin(fmax_, slo)) and same_floats(np.fmax(-fmax_, chi), np.fmax(-fmax_, shi))  # ... the fold does not
+
+
 def test_mesh_id_out_of_range_is_rejected(oracle_mod):
     from renderer_amd import scene
 
