@@ -77,18 +77,43 @@ def world_aabbs(model, mesh_min, mesh_max):
         return centre - half, centre + half
 
 
-def coarse_culled(mins, maxs, planes):
+def plane_terms(mins, maxs, planes):
+    """The two operands of the plane test, per instance and plane slot (n, 6): sd, the signed distance of the box centre,
+    and e, the box's extent along the normal. The instance is outside plane p when sd - e > 0."""
     with np.errstate(all="ignore"):
         h = (maxs - mins) * F(0.5)
         c = (mins + maxs) * F(0.5)
-        outside = np.zeros(len(mins), bool)
+        sd = np.empty((len(mins), 6), F)
+        e = np.empty((len(mins), 6), F)
         for p in range(6):
             nx, ny, nz, d = (F(v) for v in planes[p * 4 : p * 4 + 4])
-            e = h[:, 0] * np.abs(nx) + h[:, 1] * np.abs(ny) + h[:, 2] * np.abs(nz)
+            e[:, p] = h[:, 0] * np.abs(nx) + h[:, 1] * np.abs(ny) + h[:, 2] * np.abs(nz)
             a0, a1, a2, a3 = nx * c[:, 0], ny * c[:, 1], nz * c[:, 2], d * F(1.0)
-            s = (a0 + a2) + (a1 + a3)
-            outside |= (s - e) > 0
-    return outside
+            sd[:, p] = (a0 + a2) + (a1 + a3)
+    return sd, e
+
+
+def plane_margins(mins, maxs, planes):
+    with np.errstate(all="ignore"):
+        sd, e = plane_terms(mins, maxs, planes)
+        return sd - e
+
+
+def coarse_culled(mins, maxs, planes):
+    with np.errstate(all="ignore"):
+        return (plane_margins(mins, maxs, np.asarray(planes, F).reshape(24)) > 0).any(axis=1)
+
+
+def dist_sq(pos, ref):
+    """norm_squared of (ref - pos) as pick_lod forms it (helpers.rs:3-11), float32."""
+    with np.errstate(all="ignore"):
+        d = np.asarray(ref).astype(F).reshape(3)[None, :] - np.asarray(pos).astype(F)
+        return F(0.0) + ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+
+
+def lod_is_far(sq):
+    with np.errstate(all="ignore"):
+        return np.sqrt(sq) > F(10.0)
 
 
 def draw_commands(pos, mesh_id, culled, meshes, cam_pos, first_instance_base=0, first_index_base=0):
