@@ -500,6 +500,48 @@ typedef struct MipBatchOutputs {
 
 int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipBatchOutputs* out);
 
+/* ---- Extension: batched draws over the whole LOD chain, with a selection rule the caller tunes --------------------
+ * mip_batch_draws with every level of MipMesh (up to MIP_MAX_LODS) and a caller's thresholds in pick_lod's place. NOT a
+ * reference behaviour; checked against this repository's restatement (tests/lod_restatement.py), byte for byte.
+ * The per-instance lists of mip_run, mip_run_views, mip_run_occluded and the wire forms keep pick_lod (LOD 0 or 1), so a
+ * frame's own draw list and these batches agree on members only under the pin policy below, not on LOD in general.
+ *
+ * SELECTION, per instance, in float32 with contraction off, every product and sum rounded once:
+ *   d = cam_pos - pos (per component; cam_pos is frame->cam_pos)
+ *   q = (d.x*d.x + d.y*d.y) + d.z*d.z                                  (the expression pick_lod's test evaluates)
+ *   MIP_LOD_DISTANCE:  b_k = switch_sq[k]
+ *   MIP_LOD_RELATIVE:  e = aabb_max - aabb_min of the instance's mesh (per component)
+ *                      diag_sq = (e.x*e.x + e.y*e.y) + e.z*e.z
+ *                      b_k = switch_sq[k] * ((scale*scale) * diag_sq)
+ *   lod = #{ k in [0, n_lods - 1) : q > b_k }
+ * lod is a COUNT, not a walk that stops at the first failure. A NaN on either side of a comparison counts as false, so a NaN
+ * position or scale selects LOD 0 (as pick_lod does); q = +inf selects the last LOD whose b_k is finite. A mesh with n_lods
+ * levels never selects a level at or above n_lods. No square root and no division: every decision can be reproduced bit for
+ * bit. switch_sq holds SQUARED metrics: squared distances (DISTANCE), or squared distances in diagonals of the instance's
+ * scaled mesh box (RELATIVE).
+ * THRESHOLDS: every switch_sq[k] is >= 0 and not NaN, and the five are non-decreasing; +inf is legal and means "never".
+ * Anything else is MIP_ERR_INVALID_ARGUMENT.
+ * PIN: with mode = MIP_LOD_DISTANCE and switch_sq = {100.00000762939453125f, +inf, +inf, +inf, +inf} (the first value is
+ * nextafter(100): sqrt(q) > 10 exactly when q exceeds it) every output is byte-identical to mip_batch_draws on any mesh table.
+ *
+ * MEMBERS: as mip_batch_draws — bit i of the bitmap is set and index_len[lod_i] > 0 — with lod_i as above.
+ * BUCKET of a member: lod_base[mesh_id] + lod, lod_base = the exclusive prefix sum of n_lods over the mesh table; there are
+ * B = sum of n_lods buckets, mesh-major, ascending. SLOTS, instance_ids, instance_count, batch_model and the packing of
+ * COMMANDS are exactly as mip_batch_draws documents, with indexCount = index_len[lod] and firstIndex = index_offset[lod] of
+ * the bucket's level. batch_cmds needs room for min(B, N) commands.
+ * ORDERING, ERRORS and OUT OF SCOPE are mip_batch_draws's; a NULL policy, a wrong MipLodPolicy.struct_size and an unknown
+ * mode are MIP_ERR_INVALID_ARGUMENT as well. A refused call writes nothing. */
+#define MIP_LOD_DISTANCE 0u  /* metric = squared distance from frame->cam_pos to the instance position */
+#define MIP_LOD_RELATIVE 1u  /* the same, measured in diagonals of the instance's scaled mesh box */
+typedef struct MipLodPolicy {
+  uint32_t struct_size;                 /* = sizeof(MipLodPolicy), 28 */
+  uint32_t mode;                        /* MIP_LOD_* */
+  float switch_sq[MIP_MAX_LODS - 1];    /* LOD k+1 replaces LOD k beyond this SQUARED metric */
+} MipLodPolicy;
+
+int32_t mip_batch_draws_lods(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap,
+                             const MipLodPolicy* policy, const MipBatchOutputs* out);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every

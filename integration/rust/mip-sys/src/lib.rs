@@ -97,6 +97,29 @@ pub struct MipShardedOutputs {
     pub flags: u32,
 }
 
+/// Extension (not a reference behaviour): outputs of the batched draws, device pointers (see the header).
+#[repr(C)]
+pub struct MipBatchOutputs {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub batch_cmds: *mut c_void,
+    pub batch_count: *mut u32,
+    pub instance_ids: *mut u32,
+    pub instance_count: *mut u32,
+    pub batch_model: *mut c_void,
+}
+
+pub const MIP_LOD_DISTANCE: u32 = 0;
+pub const MIP_LOD_RELATIVE: u32 = 1;
+
+/// The selection rule of mip_batch_draws_lods: LOD k+1 replaces LOD k beyond switch_sq[k], a SQUARED metric.
+#[repr(C)]
+pub struct MipLodPolicy {
+    pub struct_size: u32,
+    pub mode: u32,
+    pub switch_sq: [f32; 5],
+}
+
 extern "C" {
     pub fn mip_abi_version() -> u32;
     pub fn mip_create(cfg: *const MipConfig, out: *mut *mut MipContext) -> i32;
@@ -150,6 +173,9 @@ extern "C" {
     /// Signals `value` behind the frame issued last.
     pub fn mip_signal_external(ctx: *mut MipContext, semaphore: *mut MipExternalSemaphore, value: u64) -> i32;
     pub fn mip_release_external_semaphore(ctx: *mut MipContext, semaphore: *mut MipExternalSemaphore) -> i32;
+    /// Extension: one instanced command per (mesh, LOD) bucket over the whole LOD chain, LODs chosen by `policy`.
+    pub fn mip_batch_draws_lods(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32,
+                                policy: *const MipLodPolicy, out: *const MipBatchOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -160,6 +186,9 @@ const _: () = assert!(std::mem::size_of::<MipMesh>() == 80);
 const _: () = assert!(std::mem::size_of::<MipFrame>() == 180);
 const _: () = assert!(std::mem::size_of::<MipOutputs>() == 80);
 const _: () = assert!(std::mem::size_of::<MipDrawIndexedIndirectCommand>() == 20);
+// the extension structs, as array lengths (a mismatch is a type error)
+const _: [u8; 48] = [0; std::mem::size_of::<MipBatchOutputs>()];
+const _: [u8; 28] = [0; std::mem::size_of::<MipLodPolicy>()];
 
 impl Pipeline {
     /// `panic = "abort"` (Cargo.toml:133,138) makes a panic here as final as in the rest of the renderer.

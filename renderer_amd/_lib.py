@@ -39,12 +39,14 @@ MIP_DEPTH_UNORM16 = 0
 MIP_DEPTH_FLOAT32 = 1
 MIP_MAX_DEPTH_EXTENT = 16384
 MIP_OCC_CANDIDATES_INVERTED = 0x1
+MIP_LOD_DISTANCE = 0
+MIP_LOD_RELATIVE = 1
 
 # Every symbol include/mi_instance_pipeline.h declares.
 EXPORTS = (
     "mip_abi_version", "mip_create", "mip_destroy", "mip_set_mesh_table", "mip_set_instances",
     "mip_set_instances_device", "mip_update_instances", "mip_set_geometry", "mip_set_blas_addresses", "mip_run", "mip_run_many", "mip_wait", "mip_merge_draw_lists", "mip_merge_wire_lists", "mip_merge_wire_lists_packed", "mip_wire_index_bits", "mip_light_draw_lists", "mip_set_skeleton", "mip_set_poses", "mip_run_skinned", "mip_run_views", "mip_comm_unique_id", "mip_comm_init", "mip_comm_destroy", "mip_run_sharded", "mip_import_external_fd", "mip_release_external", "mip_import_external_semaphore_fd", "mip_external_semaphore_on_device", "mip_wait_external", "mip_signal_external", "mip_release_external_semaphore", "mip_last_error",
-    "mip_get_timings", "mip_depth_pyramid_bytes", "mip_build_depth_pyramid", "mip_run_occluded", "mip_batch_draws", "mip_reset_timings", "mip_instance_count",
+    "mip_get_timings", "mip_depth_pyramid_bytes", "mip_build_depth_pyramid", "mip_run_occluded", "mip_batch_draws", "mip_batch_draws_lods", "mip_reset_timings", "mip_instance_count",
 )
 
 
@@ -128,6 +130,15 @@ class MipBatchOutputs(C.Structure):
         ("instance_ids", C.c_void_p),
         ("instance_count", C.c_void_p),
         ("batch_model", C.c_void_p),
+    ]
+
+
+class MipLodPolicy(C.Structure):
+    """mip_batch_draws_lods' selection rule (include/mi_instance_pipeline.h): mode and five SQUARED thresholds, 28 B."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("switch_sq", C.c_float * (MIP_MAX_LODS - 1)),
     ]
 
 
@@ -254,6 +265,7 @@ def load_library():
     _declare_newer(lib, "mip_build_depth_pyramid", [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int32])
     _declare_newer(lib, "mip_run_occluded", [vp, vp, vp, vp])
     _declare_newer(lib, "mip_batch_draws", [vp, vp, vp, vp])
+    _declare_newer(lib, "mip_batch_draws_lods", [vp, vp, vp, vp, vp])
     lib.mip_instance_count.argtypes = [vp]
     lib.mip_instance_count.restype = C.c_uint32
     _lib = lib

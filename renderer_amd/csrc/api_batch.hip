@@ -1,9 +1,10 @@
 // api_batch.hip — C ABI of the instance pipeline, part 6 of 6: batched draws (extension, not reference behaviour).
 // mip_batch_draws bins the members of a visibility bitmap by (mesh, LOD) and writes one instanced command per non-empty
 // bucket, the entity ids in slot order and, optionally, the members' model matrices in slot order.
-// The kernels (batch_kernel.hpp) are instantiated here and only here.
+// mip_batch_draws_lods does the same over the whole LOD chain, bucket = lod_base[mesh] + lod, with the caller's thresholds.
+// The kernels (batch_kernel.hpp, batch_lods_kernel.hpp) are instantiated here and only here.
 #include "context.hpp"
-#include "batch_kernel.hpp"
+#include "batch_lods_kernel.hpp"
 
 namespace mip_host {
 namespace {
@@ -30,14 +31,15 @@ int32_t ensure_scratch(MipContext* ctx, MipContext::BatchScratch& bs, bool sever
       MIP_HIP(ctx, hipMalloc(&bs.d_keys[k], cap * 4));
       MIP_HIP(ctx, hipMalloc(&bs.d_ids[k], cap * 4));
     }
-    MIP_HIP(ctx, hipMalloc(&bs.d_bucket_hist, (size_t)(ctx->max_meshes ? ctx->max_meshes : 1) * 2 * 4));
+    MIP_HIP(ctx, hipMalloc(&bs.d_bucket_hist, (size_t)(ctx->max_meshes ? ctx->max_meshes : 1) * MIP_MAX_LODS * 4));
   }
   if (several_passes && slot_map && !bs.d_slot_of) MIP_HIP(ctx, hipMalloc(&bs.d_slot_of, cap * 4));
   return MIP_OK;
 }
 
-template <class K>
-int32_t launch(MipContext* ctx, K kernel, uint32_t blocks, hipStream_t stream, mip::BatchArgs& a) {
+// `a` is the kernel's own argument block: BatchArgs, or LodBatchArgs whose leading part the shared kernels take
+template <class K, class A>
+int32_t launch(MipContext* ctx, K kernel, uint32_t blocks, hipStream_t stream, A& a) {
   void* params[] = {&a};
   MIP_HIP(ctx, hipLaunchKernel((const void*)kernel, dim3(blocks), dim3(mip::kTile), params, 0, stream));
   MIP_HIP(ctx, hipGetLastError());
@@ -60,14 +62,35 @@ void batch_release(MipContext* ctx) {
   ctx->batch.clear();
 }
 
-}  // namespace mip_host
+namespace {
 
-using namespace mip_host;
+// The kernels of mip_batch_draws_lods that form keys, by the policy's mode (a template parameter of each).
+template <uint32_t kMode>
+int32_t launch_scatter_mode(MipContext* ctx, bool last, int model, hipStream_t stream, mip::LodBatchArgs& a) {
+  if (!last) return launch(ctx, mip::mip_batch_lods_scatter_kernel<mip::BatchLodChainKey<kMode>, false, 0>, a.n_tiles, stream, a);
+  return model == 0   ? launch(ctx, mip::mip_batch_lods_scatter_kernel<mip::BatchLodChainKey<kMode>, true, 0>, a.n_tiles, stream, a)
+         : model == 2 ? launch(ctx, mip::mip_batch_lods_scatter_kernel<mip::BatchLodChainKey<kMode>, true, 2>, a.n_tiles, stream, a)
+                      : launch(ctx, mip::mip_batch_lods_scatter_kernel<mip::BatchLodChainKey<kMode>, true, 1>, a.n_tiles, stream, a);
+}
+int32_t launch_scatter(MipContext* ctx, uint32_t mode, bool last, int model, hipStream_t stream, mip::LodBatchArgs& a) {
+  return mode == MIP_LOD_RELATIVE ? launch_scatter_mode<MIP_LOD_RELATIVE>(ctx, last, model, stream, a)
+                                  : launch_scatter_mode<MIP_LOD_DISTANCE>(ctx, last, model, stream, a);
+}
+int32_t launch_count(MipContext* ctx, uint32_t mode, hipStream_t stream, mip::LodBatchArgs& a) {
+  return mode == MIP_LOD_RELATIVE ? launch(ctx, mip::mip_batch_lods_count_kernel<mip::BatchLodChainKey<MIP_LOD_RELATIVE>>, a.n_tiles, stream, a)
+                                  : launch(ctx, mip::mip_batch_lods_count_kernel<mip::BatchLodChainKey<MIP_LOD_DISTANCE>>, a.n_tiles, stream, a);
+}
+int32_t launch_model(MipContext* ctx, uint32_t mode, bool general, hipStream_t stream, mip::LodBatchArgs& a) {
+  if (mode == MIP_LOD_RELATIVE)
+    return general ? launch(ctx, mip::mip_batch_lods_model_kernel<mip::BatchLodChainKey<MIP_LOD_RELATIVE>, true>, a.n_tiles, stream, a)
+                   : launch(ctx, mip::mip_batch_lods_model_kernel<mip::BatchLodChainKey<MIP_LOD_RELATIVE>, false>, a.n_tiles, stream, a);
+  return general ? launch(ctx, mip::mip_batch_lods_model_kernel<mip::BatchLodChainKey<MIP_LOD_DISTANCE>, true>, a.n_tiles, stream, a)
+                 : launch(ctx, mip::mip_batch_lods_model_kernel<mip::BatchLodChainKey<MIP_LOD_DISTANCE>, false>, a.n_tiles, stream, a);
+}
 
-extern "C" {
-
-int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipBatchOutputs* out) {
-  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+// Both entry points; policy == null: mip_batch_draws (pick_lod, bucket = mesh * 2 + lod).
+int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                    const MipBatchOutputs* out) {
   if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
   if (out->struct_size != sizeof(MipBatchOutputs))
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipBatchOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipBatchOutputs));
@@ -83,8 +106,9 @@ int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* 
   const uint32_t slot = ctx->last_slot;
   hipStream_t stream = ctx->slots[slot].stream;
   const uint32_t n = ctx->n;
-  const unsigned long long buckets = 2ull * ctx->m;
-  if (buckets > 0x80000000ull) return fail(ctx, MIP_ERR_CAPACITY, "%u meshes: a bucket does not fit a 32-bit key", ctx->m);
+  const unsigned long long buckets = policy ? ctx->lod_buckets : 2ull * ctx->m;
+  if (buckets > 0x80000000ull || (policy && ctx->m > 0x20000000u))
+    return fail(ctx, MIP_ERR_CAPACITY, "%u meshes, %llu buckets: a bucket does not fit a 32-bit key", ctx->m, buckets);
 
   if (n == 0 || buckets == 0) {  // nothing to bin: two zeros
     MIP_HIP(ctx, hipMemsetAsync(out->batch_count, 0, 4, stream));
@@ -100,7 +124,14 @@ int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* 
     // the arithmetic mip_run's `model` comes from: the census decides (frame_plan.hpp, LaunchPlan.general)
     const bool general = ctx->nonfinite_instances != 0 || ctx->force_general;
 
-    mip::BatchArgs a{};
+    mip::LodBatchArgs a{};  // (mip_batch_draws's kernels take its leading part, BatchArgs)
+    mip::BatchArgs& base = a;
+    const uint32_t mode = policy ? policy->mode : 0u;
+    if (policy) {
+      a.chain = ctx->d_mesh_chain;
+      a.bucket_lod = ctx->d_bucket_lod;
+      std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
+    }
     a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
     a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
     a.bitmap = visible_bitmap;
@@ -132,36 +163,71 @@ int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* 
       a.instance_ids = last ? out->instance_ids : nullptr;
       a.slot_of = (last && several && out->batch_model) ? bs.d_slot_of : nullptr;
       a.batch_model = (last && !several) ? static_cast<float4*>(out->batch_model) : nullptr;
-      if (int32_t rc = p == 0 ? launch(ctx, mip::mip_batch_count_kernel<false>, a.n_tiles, stream, a)
-                              : launch(ctx, mip::mip_batch_count_kernel<true>, a.n_tiles, stream, a))
+      // pass 0 forms keys from the instance columns: the kernels of the call's key policy; the list passes are shared
+      if (int32_t rc = p != 0    ? launch(ctx, mip::mip_batch_count_kernel<true>, a.n_tiles, stream, base)
+                       : !policy ? launch(ctx, mip::mip_batch_count_kernel<false>, a.n_tiles, stream, base)
+                                 : launch_count(ctx, mode, stream, a))
         return rc;
-      if (int32_t rc = launch(ctx, mip::mip_batch_rowscan_kernel, a.n_bins, stream, a)) return rc;
+      if (int32_t rc = launch(ctx, mip::mip_batch_rowscan_kernel, a.n_bins, stream, base)) return rc;
       if (p == 0) {  // the scan's epilogue: bucket totals -> commands and the two counts (and the list's length for later passes)
         a.bucket_totals = several ? bs.d_bucket_hist : a.totals;
-        if (int32_t rc = launch(ctx, mip::mip_batch_commands_kernel, 1, stream, a)) return rc;
+        if (int32_t rc = policy ? launch(ctx, mip::mip_batch_lods_commands_kernel, 1, stream, a)
+                                : launch(ctx, mip::mip_batch_commands_kernel, 1, stream, base))
+          return rc;
       }
       int32_t rc;
-      if (p == 0 && last) {
-        rc = !a.batch_model ? launch(ctx, mip::mip_batch_scatter_kernel<false, true, 0>, a.n_tiles, stream, a)
-             : general      ? launch(ctx, mip::mip_batch_scatter_kernel<false, true, 2>, a.n_tiles, stream, a)
-                            : launch(ctx, mip::mip_batch_scatter_kernel<false, true, 1>, a.n_tiles, stream, a);
+      if (p == 0 && policy) {
+        rc = launch_scatter(ctx, mode, last, !a.batch_model ? 0 : general ? 2 : 1, stream, a);
+      } else if (p == 0 && last) {
+        rc = !a.batch_model ? launch(ctx, mip::mip_batch_scatter_kernel<false, true, 0>, a.n_tiles, stream, base)
+             : general      ? launch(ctx, mip::mip_batch_scatter_kernel<false, true, 2>, a.n_tiles, stream, base)
+                            : launch(ctx, mip::mip_batch_scatter_kernel<false, true, 1>, a.n_tiles, stream, base);
       } else if (p == 0) {
-        rc = launch(ctx, mip::mip_batch_scatter_kernel<false, false, 0>, a.n_tiles, stream, a);
+        rc = launch(ctx, mip::mip_batch_scatter_kernel<false, false, 0>, a.n_tiles, stream, base);
       } else if (last) {
-        rc = launch(ctx, mip::mip_batch_scatter_kernel<true, true, 0>, a.n_tiles, stream, a);
+        rc = launch(ctx, mip::mip_batch_scatter_kernel<true, true, 0>, a.n_tiles, stream, base);
       } else {
-        rc = launch(ctx, mip::mip_batch_scatter_kernel<true, false, 0>, a.n_tiles, stream, a);
+        rc = launch(ctx, mip::mip_batch_scatter_kernel<true, false, 0>, a.n_tiles, stream, base);
       }
       if (rc) return rc;
     }
     if (several && out->batch_model) {
       a.batch_model = static_cast<float4*>(out->batch_model);
-      if (int32_t rc = general ? launch(ctx, mip::mip_batch_model_kernel<true>, a.n_tiles, stream, a)
-                               : launch(ctx, mip::mip_batch_model_kernel<false>, a.n_tiles, stream, a))
+      if (int32_t rc = policy    ? launch_model(ctx, mode, general, stream, a)
+                       : general ? launch(ctx, mip::mip_batch_model_kernel<true>, a.n_tiles, stream, base)
+                                 : launch(ctx, mip::mip_batch_model_kernel<false>, a.n_tiles, stream, base))
         return rc;
     }
   }
   return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
+}
+
+}  // namespace
+}  // namespace mip_host
+
+using namespace mip_host;
+
+extern "C" {
+
+int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipBatchOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  return batch_draws(ctx, frame, visible_bitmap, nullptr, out);
+}
+
+int32_t mip_batch_draws_lods(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                             const MipBatchOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (!policy) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "policy is NULL");
+  if (policy->struct_size != sizeof(MipLodPolicy))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipLodPolicy.struct_size %u != %zu", policy->struct_size, sizeof(MipLodPolicy));
+  if (policy->mode != MIP_LOD_DISTANCE && policy->mode != MIP_LOD_RELATIVE)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipLodPolicy.mode %u", policy->mode);
+  for (uint32_t k = 0; k + 1u < MIP_MAX_LODS; ++k) {
+    const float t = policy->switch_sq[k];
+    if (!(t >= 0.0f)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "switch_sq[%u] = %g is negative or NaN", k, (double)t);
+    if (k && t < policy->switch_sq[k - 1]) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "switch_sq[%u] = %g decreases", k, (double)t);
+  }
+  return batch_draws(ctx, frame, visible_bitmap, policy, out);
 }
 
 }  // extern "C"

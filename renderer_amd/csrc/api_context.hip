@@ -109,6 +109,8 @@ void free_all(MipContext* ctx) {
   (void)hipFree(ctx->d_census);
   (void)hipFree(ctx->d_help);
   (void)hipFree(ctx->d_mesh_draw);
+  (void)hipFree(ctx->d_mesh_chain);
+  (void)hipFree(ctx->d_bucket_lod);
   (void)hipFree(ctx->d_blas);
   (void)hipFree(ctx->d_vertices);
   (void)hipFree(ctx->d_indices);
@@ -200,6 +202,8 @@ int32_t mip_create(const MipConfig* cfg, MipContext** out) {
     MIP_HIP(ctx, hipMalloc(&ctx->d_mesh_id, cap * 4));
     MIP_HIP(ctx, hipMalloc(&ctx->d_meshes, mcap * sizeof(mip::MeshEntry)));
     MIP_HIP(ctx, hipMalloc(&ctx->d_mesh_draw, mcap * sizeof(mip::MeshDraw)));
+    MIP_HIP(ctx, hipMalloc(&ctx->d_mesh_chain, mcap * sizeof(mip::MeshChain)));
+    MIP_HIP(ctx, hipMalloc(&ctx->d_bucket_lod, mcap * MIP_MAX_LODS * 4));
     MIP_HIP(ctx, hipMalloc(&ctx->d_census, 8));
     ctx->cu_count = prop.multiProcessorCount;
     const size_t tiles_cap = tiles_for((uint32_t)cap);
@@ -274,6 +278,9 @@ int32_t mip_set_mesh_table(MipContext* ctx, const MipMesh* meshes, uint32_t m) {
   if (m > ctx->max_meshes) return fail(ctx, MIP_ERR_CAPACITY, "%u meshes > max_meshes %u", m, ctx->max_meshes);
   std::vector<mip::MeshEntry> entries(m);
   std::vector<mip::MeshDraw> draw(m);
+  std::vector<mip::MeshChain> chain(m);  // the whole LOD chain and the bucket numbering of mip_batch_draws_lods
+  std::vector<uint32_t> bucket_lod;
+  bucket_lod.reserve((size_t)m * 2);
   for (uint32_t k = 0; k < m; ++k) {
     const MipMesh& s = meshes[k];
     if (s.n_lods < 1 || s.n_lods > MIP_MAX_LODS)
@@ -290,6 +297,15 @@ int32_t mip_set_mesh_table(MipContext* ctx, const MipMesh* meshes, uint32_t m) {
     draw[k].src_offset0 = s.index_offset[0];
     draw[k].src_offset1 = s.n_lods > 1 ? s.index_offset[1] : s.index_offset[0];
     draw[k].pad = s.n_lods > 1 ? 1u : 0u;  // the spare word: 1 = the mesh has a LOD 1 of its own (batch_kernel.hpp, mesh_has_lod1)
+    mip::MeshChain& c = chain[k];
+    c = mip::MeshChain{};
+    c.n_lods = s.n_lods;
+    c.lod_base = (uint32_t)bucket_lod.size();  // (mip_batch_draws_lods refuses a table whose buckets do not fit a key)
+    for (uint32_t l = 0; l < s.n_lods; ++l) {
+      c.index_len[l] = s.index_len[l];
+      c.index_offset[l] = s.index_offset[l];
+      bucket_lod.push_back(k << 3 | l);
+    }
   }
   if (int32_t rc = bind_device(ctx)) return rc;
   if (int32_t rc = sync_all(ctx)) return rc;
@@ -311,12 +327,15 @@ int32_t mip_set_mesh_table(MipContext* ctx, const MipMesh* meshes, uint32_t m) {
   if (m) {
     MIP_HIP(ctx, hipMemcpyAsync(ctx->d_meshes, entries.data(), m * sizeof(mip::MeshEntry), hipMemcpyHostToDevice, ctx->stream));
     MIP_HIP(ctx, hipMemcpyAsync(ctx->d_mesh_draw, draw.data(), m * sizeof(mip::MeshDraw), hipMemcpyHostToDevice, ctx->stream));
+    MIP_HIP(ctx, hipMemcpyAsync(ctx->d_mesh_chain, chain.data(), m * sizeof(mip::MeshChain), hipMemcpyHostToDevice, ctx->stream));
+    MIP_HIP(ctx, hipMemcpyAsync(ctx->d_bucket_lod, bucket_lod.data(), bucket_lod.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     MIP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the sources are locals
   }
   // recorded launches carry what follows from the table's SIZE in their arguments (n_meshes, the wire form's index bits, and whether
   // the one entry of a one-mesh table is read as a scalar: KernelArgs.one_mesh): another size, another recording
   if (m != ctx->m) ctx->graph_generation++;
   ctx->m = m;
+  ctx->lod_buckets = bucket_lod.size();
   ctx->have_meshes = true;
   ctx->h_meshes.assign(meshes, meshes + m);
   ctx->geometry_checked = 0;

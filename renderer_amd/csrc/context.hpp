@@ -5,7 +5,7 @@
 //   api_sharded.hip   shard merges, the collective-library seam, mip_run_sharded and its collective repair
 //   api_interop.hip   external memory and external semaphores (row f-2)
 //   api_occlusion.hip the occlusion-culling extension: depth pyramid builds, mip_run_occluded (occlusion_kernel.hpp)
-//   api_batch.hip     the batched-draws extension: mip_batch_draws (batch_kernel.hpp)
+//   api_batch.hip     the batched-draws extension: mip_batch_draws (batch_kernel.hpp), mip_batch_draws_lods (batch_lods_kernel.hpp)
 // (round 3 had all of it in one 2 224-line mip_api.hip)
 #pragma once
 
@@ -14,6 +14,7 @@
 #include "prefix_tags.hpp"
 #include "instance_kernel.hpp"  // rows a-1 .. a-7 (the kernel itself is instantiated in api_frame.hip and stages_tu.hip only)
 #include "stage_args.hpp"      // argument blocks + launchers of everything built in stages_tu.hip
+#include "mesh_chain.hpp"      // the per-mesh LOD chain of mip_batch_draws_lods
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library is opened with dlopen, never linked
@@ -89,13 +90,13 @@ struct MipContext {
   uint32_t graph_round = 64;          // frames per replay round over all slots (MIP_TUNE_GRAPH_ROUND, 0 = off)
   std::vector<FrameSlot> slots;
   uint32_t next_slot = 0;
-  // mip_batch_draws (api_batch.hip): scratch per frame slot, allocated at first use from max_instances / max_meshes
+  // mip_batch_draws / mip_batch_draws_lods (api_batch.hip): scratch per frame slot, allocated at first use from max_instances / max_meshes
   struct BatchScratch {
     uint32_t* d_counts = nullptr;       // [256 bins][tiles] members per (bin, tile), scanned in place
     uint32_t* d_totals = nullptr;       // kBatchMaxPasses x 256 digit totals + the member count
     uint32_t* d_keys[2] = {nullptr, nullptr};  // tables of more than 128 meshes: the (key, instance) lists between passes
     uint32_t* d_ids[2] = {nullptr, nullptr};
-    uint32_t* d_bucket_hist = nullptr;  //   members per bucket, 2 x max_meshes words
+    uint32_t* d_bucket_hist = nullptr;  //   members per bucket, MIP_MAX_LODS x max_meshes words
     uint32_t* d_slot_of = nullptr;      //   slot of every member by instance (batch_model)
   };
   std::vector<BatchScratch> batch;
@@ -108,6 +109,9 @@ struct MipContext {
   uint32_t* d_mesh_id = nullptr;
   mip::MeshEntry* d_meshes = nullptr;
   mip::MeshDraw* d_mesh_draw = nullptr;
+  mip::MeshChain* d_mesh_chain = nullptr;  // mip_batch_draws_lods: every level of every mesh (filled by mip_set_mesh_table)
+  uint32_t* d_bucket_lod = nullptr;        //   mesh << 3 | lod of every (mesh, LOD) bucket, MIP_MAX_LODS x max_meshes words
+  unsigned long long lod_buckets = 0;      //   B = sum of n_lods over the table
   unsigned long long* d_blas = nullptr;  // per-mesh BLAS device addresses (optional, row f-4)
   // consolidated geometry for the per-triangle stage (row f-1)
   float* d_vertices = nullptr;

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import MipBatchOutputs, MipConfig, MipError, MipFrame, MipOcclusion, MipOutputs, MipShardedOutputs, MipTimings
+from ._lib import MipBatchOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipTimings
 
 MESH_DTYPE = np.dtype(
     [
@@ -87,6 +87,28 @@ def make_occlusion(width, height, pyramid_ptr, pv, candidates=0, occluded_bitmap
     o.occluded_bitmap = occluded_bitmap or None
     o.pv[:] = np.ascontiguousarray(pv, dtype=np.float32).reshape(16).tolist()
     return o
+
+
+# mip_batch_draws_lods with this policy is mip_batch_draws, byte for byte: pick_lod's `distance > 10` as a squared threshold
+# (nextafter(100) in float32), levels 2.. never
+LOD_PIN_SWITCH_SQ = (100.00000762939453125, float("inf"), float("inf"), float("inf"), float("inf"))
+
+
+def make_lod_policy(mode, switch_sq):
+    """A MipLodPolicy: mode MIP_LOD_DISTANCE / MIP_LOD_RELATIVE (or "distance" / "relative") and the five SQUARED thresholds
+    (fewer are padded with +inf: those levels are never selected). The values are rounded to float32 here; the library checks them
+    (>= 0, not NaN, non-decreasing)."""
+    if isinstance(mode, str):
+        mode = {"distance": _lib.MIP_LOD_DISTANCE, "relative": _lib.MIP_LOD_RELATIVE}[mode]
+    sw = [float(v) for v in np.asarray(switch_sq, dtype=np.float32).reshape(-1)]
+    if len(sw) > _lib.MIP_MAX_LODS - 1:
+        raise ValueError(f"{len(sw)} thresholds for {_lib.MIP_MAX_LODS} LODs")
+    sw += [float("inf")] * (_lib.MIP_MAX_LODS - 1 - len(sw))
+    p = MipLodPolicy()
+    p.struct_size = C.sizeof(MipLodPolicy)
+    p.mode = int(mode)
+    p.switch_sq[:] = sw
+    return p
 
 
 def make_frame(planes, cam_pos, first_instance_base=0, first_index_base=0, pv=None):
@@ -454,6 +476,22 @@ class InstancePipeline:
         out.instance_count = instance_count or None
         out.batch_model = batch_model or None
         self._check(self._lib.mip_batch_draws(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(out)))
+
+    def batch_draws_lods(self, frame, visible_bitmap_ptr, policy, *, batch_cmds, batch_count, instance_ids, instance_count=0,
+                         batch_model=0, async_=False):
+        """mip_batch_draws_lods: batch_draws over the whole LOD chain — one instanced command per non-empty (mesh, LOD) bucket,
+        bucket = lod_base[mesh] + lod, the LOD chosen by `policy` (make_lod_policy). batch_cmds needs room for
+        min(sum of n_lods, N) commands; everything else as batch_draws."""
+        out = MipBatchOutputs()
+        out.struct_size = C.sizeof(MipBatchOutputs)
+        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+        out.batch_cmds = batch_cmds or None
+        out.batch_count = batch_count or None
+        out.instance_ids = instance_ids or None
+        out.instance_count = instance_count or None
+        out.batch_model = batch_model or None
+        self._check(self._lib.mip_batch_draws_lods(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                   C.addressof(out)))
 
     # -- diagnostics --
     def timings(self):
