@@ -542,6 +542,43 @@ typedef struct MipLodPolicy {
 int32_t mip_batch_draws_lods(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap,
                              const MipLodPolicy* policy, const MipBatchOutputs* out);
 
+/* ---- Extension: depth-ordered batched draws ------------------------------------------------------------------------
+ * mip_batch_draws_lods with a chosen order of the members INSIDE every bucket: nearest first (a depth prepass, the depth a
+ * two-phase occlusion pyramid is built from) or farthest first (a blended single-mesh layer). NOT a reference behaviour;
+ * checked against this repository's restatement (tests/order_restatement.py), byte for byte.
+ *
+ * MEMBERS, LOD, BUCKET: exactly mip_batch_draws_lods for the same policy: the members, every member's lod and its bucket
+ * lod_base[mesh_id] + lod.
+ * COMMANDS AND COUNTS: batch_cmds, batch_count and instance_count are, for every order, the bytes mip_batch_draws_lods
+ * writes. The order permutes members only inside a bucket's slot range [firstInstance, firstInstance + instanceCount).
+ * DEPTH KEY of instance i, in float32 with contraction off:
+ *   d = cam_pos - pos (per component; cam_pos is frame->cam_pos)
+ *   q = (d.x*d.x + d.y*d.y) + d.z*d.z          (the q of the selection rule above)
+ *   K = 0x7F80 if q is NaN, else bits(q) >> 16 (bits: the float's 32-bit pattern)
+ * q is a sum of squares and never negative, so K is monotone (non-decreasing) in q and lies in [0, 0x7F80]; 0x7F80 is the
+ * K of q = +inf and of a NaN. K keeps the sign, the exponent and 7 mantissa bits of q: a step of K is at most 1/128 in q,
+ * about 0.4 % in distance. Members whose q differ by less may share a K.
+ *   D = K            MIP_BATCH_ORDER_NEAR_FIRST
+ *   D = 0x7F80 - K   MIP_BATCH_ORDER_FAR_FIRST
+ *   D = 0            MIP_BATCH_ORDER_DRAW_INDEX
+ * SLOTS: the members sorted by (bucket, D, draw index), ascending. Equal D keeps draw order: the sort is stable. A member
+ * whose distance is NaN is last in its bucket under NEAR_FIRST (together with q = +inf, in draw order) and first under
+ * FAR_FIRST. instance_ids[s] = first_instance_base + the instance of slot s, batch_model[s] = the 64 bytes mip_run's `model`
+ * holds for that instance, and nothing at or behind `members` is touched: all as mip_batch_draws documents.
+ * MIP_BATCH_ORDER_DRAW_INDEX is mip_batch_draws_lods, byte for byte in every output.
+ * CAPACITY: NEAR_FIRST and FAR_FIRST sort a 32-bit key bucket << 16 | D. With B = sum of n_lods > 65 536 buckets the call
+ * returns MIP_ERR_CAPACITY and writes nothing. DRAW_INDEX has the limits of mip_batch_draws_lods.
+ * ERRORS: an unknown order is MIP_ERR_INVALID_ARGUMENT. Every other error, the ordering on the stream behind the frame issued
+ * last, the scratch per frame slot and the out-of-scope list are mip_batch_draws_lods's. A refused call writes nothing.
+ * OUT OF SCOPE, besides that list: an order ACROSS buckets (one globally depth-sorted per-instance list); view-space depth
+ * (the metric is the radial distance the LOD rule already forms, not the distance along the view direction); sharded
+ * scenes, mip_run_many and the per-triangle stage. */
+#define MIP_BATCH_ORDER_DRAW_INDEX 0u  /* mip_batch_draws_lods, byte for byte */
+#define MIP_BATCH_ORDER_NEAR_FIRST 1u
+#define MIP_BATCH_ORDER_FAR_FIRST  2u
+int32_t mip_batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap,
+                                const MipLodPolicy* policy, uint32_t order, const MipBatchOutputs* out);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every

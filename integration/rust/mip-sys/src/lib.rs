@@ -120,6 +120,11 @@ pub struct MipLodPolicy {
     pub switch_sq: [f32; 5],
 }
 
+/// The order of the members inside a bucket (mip_batch_draws_ordered).
+pub const MIP_BATCH_ORDER_DRAW_INDEX: u32 = 0;
+pub const MIP_BATCH_ORDER_NEAR_FIRST: u32 = 1;
+pub const MIP_BATCH_ORDER_FAR_FIRST: u32 = 2;
+
 extern "C" {
     pub fn mip_abi_version() -> u32;
     pub fn mip_create(cfg: *const MipConfig, out: *mut *mut MipContext) -> i32;
@@ -176,6 +181,9 @@ extern "C" {
     /// Extension: one instanced command per (mesh, LOD) bucket over the whole LOD chain, LODs chosen by `policy`.
     pub fn mip_batch_draws_lods(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32,
                                 policy: *const MipLodPolicy, out: *const MipBatchOutputs) -> i32;
+    /// Extension: mip_batch_draws_lods with the members of every bucket nearest first or farthest first (MIP_BATCH_ORDER_*).
+    pub fn mip_batch_draws_ordered(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32,
+                                   policy: *const MipLodPolicy, order: u32, out: *const MipBatchOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }

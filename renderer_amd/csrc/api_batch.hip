@@ -2,9 +2,10 @@
 // mip_batch_draws bins the members of a visibility bitmap by (mesh, LOD) and writes one instanced command per non-empty
 // bucket, the entity ids in slot order and, optionally, the members' model matrices in slot order.
 // mip_batch_draws_lods does the same over the whole LOD chain, bucket = lod_base[mesh] + lod, with the caller's thresholds.
-// The kernels (batch_kernel.hpp, batch_lods_kernel.hpp) are instantiated here and only here.
+// mip_batch_draws_ordered is mip_batch_draws_lods with the members of a bucket nearest first or farthest first.
+// The kernels (batch_kernel.hpp, batch_lods_kernel.hpp, batch_ordered_kernel.hpp) are instantiated here and only here.
 #include "context.hpp"
-#include "batch_lods_kernel.hpp"
+#include "batch_ordered_kernel.hpp"
 
 namespace mip_host {
 namespace {
@@ -88,9 +89,8 @@ int32_t launch_model(MipContext* ctx, uint32_t mode, bool general, hipStream_t s
                  : launch(ctx, mip::mip_batch_lods_model_kernel<mip::BatchLodChainKey<MIP_LOD_DISTANCE>, false>, a.n_tiles, stream, a);
 }
 
-// Both entry points; policy == null: mip_batch_draws (pick_lod, bucket = mesh * 2 + lod).
-int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
-                    const MipBatchOutputs* out) {
+// The argument checks every entry point shares, and the context's device made current.
+int32_t check_call(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipBatchOutputs* out) {
   if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
   if (out->struct_size != sizeof(MipBatchOutputs))
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipBatchOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipBatchOutputs));
@@ -102,6 +102,13 @@ int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visi
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds / batch_model is not aligned (4 / 16 bytes)");
   if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
   if (int32_t rc = bind_device(ctx)) return rc;
+  return MIP_OK;
+}
+
+// mip_batch_draws and mip_batch_draws_lods; policy == null: mip_batch_draws (pick_lod, bucket = mesh * 2 + lod).
+int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                    const MipBatchOutputs* out) {
+  if (int32_t rc = check_call(ctx, frame, visible_bitmap, out)) return rc;
   // behind the frame issued last: a bitmap that frame writes is ordered before these launches without a wait
   const uint32_t slot = ctx->last_slot;
   hipStream_t stream = ctx->slots[slot].stream;
@@ -202,6 +209,110 @@ int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visi
   return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
 }
 
+// The pass-0 kernels of mip_batch_draws_ordered, by the policy's mode.
+int32_t launch_ordered_count(MipContext* ctx, uint32_t mode, hipStream_t stream, mip::OrderedBatchArgs& a) {
+  return mode == MIP_LOD_RELATIVE ? launch(ctx, mip::mip_batch_ordered_count_kernel<mip::BatchOrderedKey<MIP_LOD_RELATIVE>>, a.n_tiles, stream, a)
+                                  : launch(ctx, mip::mip_batch_ordered_count_kernel<mip::BatchOrderedKey<MIP_LOD_DISTANCE>>, a.n_tiles, stream, a);
+}
+int32_t launch_ordered_scatter(MipContext* ctx, uint32_t mode, hipStream_t stream, mip::OrderedBatchArgs& a) {
+  return mode == MIP_LOD_RELATIVE ? launch(ctx, mip::mip_batch_ordered_scatter_kernel<mip::BatchOrderedKey<MIP_LOD_RELATIVE>>, a.n_tiles, stream, a)
+                                  : launch(ctx, mip::mip_batch_ordered_scatter_kernel<mip::BatchOrderedKey<MIP_LOD_DISTANCE>>, a.n_tiles, stream, a);
+}
+
+// mip_batch_draws_ordered, NEAR_FIRST / FAR_FIRST: a stable sort by key = bucket << 16 | D. Pass 0 forms the keys
+// (batch_ordered_kernel.hpp) and counts the buckets; the later digits, the commands and the matrices are the existing kernels.
+int32_t batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                            bool far_first, const MipBatchOutputs* out) {
+  if (int32_t rc = check_call(ctx, frame, visible_bitmap, out)) return rc;
+  const uint32_t slot = ctx->last_slot;  // behind the frame issued last, as batch_draws
+  hipStream_t stream = ctx->slots[slot].stream;
+  const uint32_t n = ctx->n;
+  const unsigned long long buckets = ctx->lod_buckets;
+  if (buckets > mip::kBatchOrderedMaxBuckets)
+    return fail(ctx, MIP_ERR_CAPACITY, "%llu buckets: bucket << 16 | depth does not fit a 32-bit key (at most %u)", buckets, mip::kBatchOrderedMaxBuckets);
+
+  if (n == 0 || buckets == 0) {  // nothing to bin: two zeros
+    MIP_HIP(ctx, hipMemsetAsync(out->batch_count, 0, 4, stream));
+    if (out->instance_count) MIP_HIP(ctx, hipMemsetAsync(out->instance_count, 0, 4, stream));
+    return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
+  }
+  const uint32_t bits = mip::kBatchDepthBits + key_bits(buckets);
+  const uint32_t passes = (bits + mip::kBatchDigitBits - 1u) / mip::kBatchDigitBits;  // 3 up to 256 buckets, 4 up to 65 536
+  if (ctx->batch.size() != ctx->slots.size()) ctx->batch.resize(ctx->slots.size());
+  MipContext::BatchScratch& bs = ctx->batch[slot];
+  if (int32_t rc = ensure_scratch(ctx, bs, true, out->batch_model != nullptr)) return rc;
+  const bool general = ctx->nonfinite_instances != 0 || ctx->force_general;
+
+  mip::OrderedBatchArgs a{};
+  mip::LodBatchArgs& lods = a;  // (the command writer and the matrix kernel take this part, the list passes BatchArgs)
+  mip::BatchArgs& base = a;
+  a.depth_flip = far_first ? mip::kBatchDepthMax : 0u;
+  a.chain = ctx->d_mesh_chain;
+  a.bucket_lod = ctx->d_bucket_lod;
+  std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
+  a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
+  a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
+  a.bitmap = visible_bitmap;
+  a.n = n;
+  a.n_tiles = batch_tiles_for(n);
+  a.n_buckets = (uint32_t)buckets;
+  a.n_bins = mip::kBatchBins;
+  a.first_instance_base = frame->first_instance_base;
+  std::memcpy(a.cam, frame->cam_pos, sizeof a.cam);
+  a.counts = bs.d_counts;
+  a.members = a.members_out = bs.d_totals + mip::kBatchMaxPasses * mip::kBatchBins;
+  a.batch_cmds = static_cast<uint32_t*>(out->batch_cmds);
+  a.batch_count = out->batch_count;
+  a.instance_count = out->instance_count;
+  a.bucket_totals = bs.d_bucket_hist;
+#ifdef MIP_DEBUG_STAMPS
+  DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);
+#endif
+  MIP_HIP(ctx, hipMemsetAsync(bs.d_bucket_hist, 0, (size_t)buckets * 4, stream));
+
+  for (uint32_t p = 0; p < passes; ++p) {
+    const bool last = p + 1 == passes;
+    a.shift = p * mip::kBatchDigitBits;
+    a.totals = bs.d_totals + p * mip::kBatchBins;
+    a.bucket_hist = p == 0 ? bs.d_bucket_hist : nullptr;
+    a.keys_in = p ? bs.d_keys[(p - 1) & 1u] : nullptr;
+    a.ids_in = p ? bs.d_ids[(p - 1) & 1u] : nullptr;
+    a.keys_out = last ? nullptr : bs.d_keys[p & 1u];
+    a.ids_out = last ? nullptr : bs.d_ids[p & 1u];
+    a.instance_ids = last ? out->instance_ids : nullptr;
+    a.slot_of = (last && out->batch_model) ? bs.d_slot_of : nullptr;
+    if (int32_t rc = p == 0 ? launch_ordered_count(ctx, policy->mode, stream, a) : launch(ctx, mip::mip_batch_count_kernel<true>, a.n_tiles, stream, base))
+      return rc;
+    if (int32_t rc = launch(ctx, mip::mip_batch_rowscan_kernel, a.n_bins, stream, base)) return rc;
+    if (p == 0)  // bucket totals -> commands, the two counts and the list's length
+      if (int32_t rc = launch(ctx, mip::mip_batch_lods_commands_kernel, 1, stream, lods)) return rc;
+    if (int32_t rc = p == 0 ? launch_ordered_scatter(ctx, policy->mode, stream, a)
+                     : last ? launch(ctx, mip::mip_batch_scatter_kernel<true, true, 0>, a.n_tiles, stream, base)
+                            : launch(ctx, mip::mip_batch_scatter_kernel<true, false, 0>, a.n_tiles, stream, base))
+      return rc;
+  }
+  if (out->batch_model) {
+    a.batch_model = static_cast<float4*>(out->batch_model);
+    if (int32_t rc = launch_model(ctx, policy->mode, general, stream, lods)) return rc;
+  }
+  return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
+}
+
+// MipLodPolicy as the header states it
+int32_t check_policy(MipContext* ctx, const MipLodPolicy* policy) {
+  if (!policy) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "policy is NULL");
+  if (policy->struct_size != sizeof(MipLodPolicy))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipLodPolicy.struct_size %u != %zu", policy->struct_size, sizeof(MipLodPolicy));
+  if (policy->mode != MIP_LOD_DISTANCE && policy->mode != MIP_LOD_RELATIVE)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipLodPolicy.mode %u", policy->mode);
+  for (uint32_t k = 0; k + 1u < MIP_MAX_LODS; ++k) {
+    const float t = policy->switch_sq[k];
+    if (!(t >= 0.0f)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "switch_sq[%u] = %g is negative or NaN", k, (double)t);
+    if (k && t < policy->switch_sq[k - 1]) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "switch_sq[%u] = %g decreases", k, (double)t);
+  }
+  return MIP_OK;
+}
+
 }  // namespace
 }  // namespace mip_host
 
@@ -217,17 +328,18 @@ int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* 
 int32_t mip_batch_draws_lods(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
                              const MipBatchOutputs* out) {
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
-  if (!policy) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "policy is NULL");
-  if (policy->struct_size != sizeof(MipLodPolicy))
-    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipLodPolicy.struct_size %u != %zu", policy->struct_size, sizeof(MipLodPolicy));
-  if (policy->mode != MIP_LOD_DISTANCE && policy->mode != MIP_LOD_RELATIVE)
-    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipLodPolicy.mode %u", policy->mode);
-  for (uint32_t k = 0; k + 1u < MIP_MAX_LODS; ++k) {
-    const float t = policy->switch_sq[k];
-    if (!(t >= 0.0f)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "switch_sq[%u] = %g is negative or NaN", k, (double)t);
-    if (k && t < policy->switch_sq[k - 1]) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "switch_sq[%u] = %g decreases", k, (double)t);
-  }
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
   return batch_draws(ctx, frame, visible_bitmap, policy, out);
+}
+
+int32_t mip_batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                uint32_t order, const MipBatchOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (order != MIP_BATCH_ORDER_DRAW_INDEX && order != MIP_BATCH_ORDER_NEAR_FIRST && order != MIP_BATCH_ORDER_FAR_FIRST)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown order %u", order);
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  if (order == MIP_BATCH_ORDER_DRAW_INDEX) return batch_draws(ctx, frame, visible_bitmap, policy, out);
+  return batch_draws_ordered(ctx, frame, visible_bitmap, policy, order == MIP_BATCH_ORDER_FAR_FIRST, out);
 }
 
 }  // extern "C"

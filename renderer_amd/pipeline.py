@@ -493,6 +493,26 @@ class InstancePipeline:
         self._check(self._lib.mip_batch_draws_lods(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                    C.addressof(out)))
 
+    def batch_draws_ordered(self, frame, visible_bitmap_ptr, policy, order, *, batch_cmds, batch_count, instance_ids, instance_count=0,
+                            batch_model=0, async_=False):
+        """mip_batch_draws_ordered: batch_draws_lods with the members of every bucket in depth order. `order` is
+        MIP_BATCH_ORDER_DRAW_INDEX / NEAR_FIRST / FAR_FIRST (or "draw_index" / "near_first" / "far_first"); the commands and
+        counts do not depend on it. The depth key is the squared distance to frame.cam_pos at about 0.4 % resolution, ties in
+        draw order. NEAR_FIRST / FAR_FIRST take tables of at most 65 536 buckets (sum of n_lods)."""
+        if isinstance(order, str):
+            order = {"draw_index": _lib.MIP_BATCH_ORDER_DRAW_INDEX, "near_first": _lib.MIP_BATCH_ORDER_NEAR_FIRST,
+                     "far_first": _lib.MIP_BATCH_ORDER_FAR_FIRST}[order]
+        out = MipBatchOutputs()
+        out.struct_size = C.sizeof(MipBatchOutputs)
+        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+        out.batch_cmds = batch_cmds or None
+        out.batch_count = batch_count or None
+        out.instance_ids = instance_ids or None
+        out.instance_count = instance_count or None
+        out.batch_model = batch_model or None
+        self._check(self._lib.mip_batch_draws_ordered(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                      int(order), C.addressof(out)))
+
     # -- diagnostics --
     def timings(self):
         t = MipTimings()

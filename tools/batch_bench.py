@@ -15,7 +15,13 @@ the pin policy (the same buckets and outputs as mip_batch_draws), a DISTANCE and
 with ids only and with batch_model. --parent-library PATH adds mip_batch_draws of another build of the library (the parent
 commit's), measured by a child process of this tool in the same session: the yardstick.
 
-  python tools/batch_bench.py --lods [--parent-library lib.so] [--out profiles/batch_draws_lods_bench.jsonl]"""
+  python tools/batch_bench.py --lods [--parent-library lib.so] [--out profiles/batch_draws_lods_bench.jsonl]
+
+--ordered: the depth-ordered stage (mip_batch_draws_ordered, NEAR_FIRST and FAR_FIRST) beside mip_batch_draws_lods of the same
+build under the two example policies, each with ids only and with batch_model. --parent-library PATH adds mip_batch_draws_lods
+of another build (the parent commit's), measured by a child process in the same session.
+
+  python tools/batch_bench.py --ordered [--parent-library lib.so] [--out profiles/batch_draws_ordered_bench.jsonl]"""
 import argparse
 import json
 import os
@@ -176,13 +182,64 @@ def bench_lods(n, emit, samples=40, only_batch_draws=False, library="this build"
         p.close()
 
 
+def bench_ordered(n, emit, samples=40, only_lods=False, library="this build"):
+    import torch
+
+    import renderer_amd
+    from renderer_amd import _lib, scene
+    from renderer_amd.pipeline import make_frame, make_lod_policy
+
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.Stream()
+    config = 2 if n <= 100_000 else 3
+    s = scene.make_scene(config, n=n)
+    m = len(s["meshes"])
+    buckets = int(s["meshes"]["n_lods"].sum())
+    with torch.cuda.stream(st):
+        p = renderer_amd.InstancePipeline(n, m, stream=st.cuda_stream)
+        p.set_mesh_table(s["meshes"])
+        p.set_instances(s["pos"], s["rot"], s["scale"], s["mesh_id"])
+        bitmap = torch.zeros((n + 31) // 32 + 1, dtype=torch.int32, device=dev)
+        cmds = torch.empty((n, 5), dtype=torch.int32, device=dev)
+        scal = torch.zeros(8, dtype=torch.int32, device=dev)
+        b_cmds = torch.empty((buckets, 5), dtype=torch.int32, device=dev)
+        b_ids = torch.empty(n, dtype=torch.int32, device=dev)
+        b_scal = torch.zeros(8, dtype=torch.int32, device=dev)
+        b_model = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        frame = p.frame_ref(make_frame(s["planes"], s["cam_pos"]))
+        p.run_prepared(frame, p.prepare_outputs(visible_bitmap=bitmap.data_ptr(), draw_cmds=cmds.data_ptr(), draw_count=scal.data_ptr(),
+                                                draw_index_total=scal.data_ptr() + 4))
+        p.wait()
+        ids_only = dict(batch_cmds=b_cmds.data_ptr(), batch_count=b_scal.data_ptr(), instance_ids=b_ids.data_ptr(),
+                        instance_count=b_scal.data_ptr() + 4, async_=True)
+        with_model = dict(ids_only, batch_model=b_model.data_ptr())
+        orders = [("batch_draws_lods", None)]
+        if not only_lods:
+            orders += [("batch_draws_ordered NEAR_FIRST", _lib.MIP_BATCH_ORDER_NEAR_FIRST), ("batch_draws_ordered FAR_FIRST", _lib.MIP_BATCH_ORDER_FAR_FIRST)]
+        for pname, policy in (("DISTANCE", make_lod_policy("distance", LODS_DISTANCE_SQ)), ("RELATIVE", make_lod_policy("relative", LODS_RELATIVE_SQ))):
+            for name, order in orders:
+                for outs, what in ((ids_only, "ids only"), (with_model, "with batch_model")):
+                    if order is None:
+                        fn = lambda: p.batch_draws_lods(frame, bitmap.data_ptr(), policy, **outs)
+                    else:
+                        fn = lambda: p.batch_draws_ordered(frame, bitmap.data_ptr(), policy, order, **outs)
+                    r = measure(st, fn, samples=samples)
+                    p.wait()
+                    emit(dict(leg=f"ordered: {name}, {pname}, {what}", library=library, n=n, config=config, meshes=m, buckets=buckets,
+                              batch_count=int(b_scal[0].item()), members=int(b_scal[1].item()), **r))
+        p.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("n", nargs="*", type=int, default=[1_000_000, 100_000])
     ap.add_argument("--samples", type=int, default=40)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     ap.add_argument("--lods", action="store_true", help="the mip_batch_draws_lods legs instead of (a) .. (s)")
-    ap.add_argument("--parent-library", default=None, help="--lods: also measure mip_batch_draws of this build of the library (a child process)")
+    ap.add_argument("--ordered", action="store_true", help="the mip_batch_draws_ordered legs instead of (a) .. (s)")
+    ap.add_argument("--parent-library", default=None,
+                    help="--lods / --ordered: also measure mip_batch_draws / mip_batch_draws_lods of this build of the library (a child process)")
     ap.add_argument("--only-batch-draws", default=None, help=argparse.SUPPRESS)  # the child's leg: the label of its library
     a = ap.parse_args()
 
@@ -193,14 +250,16 @@ def main():
             with open(a.out, "a") as f:
                 f.write(line + "\n")
 
-    if a.lods and a.parent_library:  # fresh processes, before this one opens the GPU: a library is loaded once per process (MIP_LIBRARY, renderer_amd/_lib.py)
+    if (a.lods or a.ordered) and a.parent_library:  # fresh processes, before this one opens the GPU: a library is loaded once per process (MIP_LIBRARY, renderer_amd/_lib.py)
         import subprocess
 
         for n in a.n:
-            cmd = [sys.executable, os.path.abspath(__file__), str(n), "--lods", "--samples", str(a.samples), "--only-batch-draws", "parent commit"]
+            cmd = [sys.executable, os.path.abspath(__file__), str(n), "--ordered" if a.ordered else "--lods", "--samples", str(a.samples), "--only-batch-draws", "parent commit"]
             subprocess.run(cmd + (["--out", a.out] if a.out else []), check=True, env=dict(os.environ, MIP_LIBRARY=os.path.abspath(a.parent_library)))
     for n in a.n:
-        if a.lods:
+        if a.ordered:
+            bench_ordered(n, emit, a.samples, only_lods=a.only_batch_draws is not None, library=a.only_batch_draws or "this build")
+        elif a.lods:
             bench_lods(n, emit, a.samples, only_batch_draws=a.only_batch_draws is not None, library=a.only_batch_draws or "this build")
         else:
             bench(n, emit, a.samples)
