@@ -3,21 +3,15 @@
 // bucket, the entity ids in slot order and, optionally, the members' model matrices in slot order.
 // mip_batch_draws_lods does the same over the whole LOD chain, bucket = lod_base[mesh] + lod, with the caller's thresholds.
 // mip_batch_draws_ordered is mip_batch_draws_lods with the members of a bucket nearest first or farthest first.
-// The kernels (batch_kernel.hpp, batch_lods_kernel.hpp, batch_ordered_kernel.hpp) are instantiated here and only here.
+// One stage (batch_kernel.hpp) under the key policies of the three entry points (batch_kernel.hpp, batch_lods_kernel.hpp);
+// batch_plan.hpp says which instantiation a call launches. The kernels are instantiated here and only here.
 #include "context.hpp"
-#include "batch_ordered_kernel.hpp"
+#include "batch_lods_kernel.hpp"
 
 namespace mip_host {
 namespace {
 
 uint32_t batch_tiles_for(uint32_t n) { return (n + mip::kBatchTile - 1u) / mip::kBatchTile; }
-
-// ceil(log2(buckets)), at least 1: the bits of a key
-uint32_t key_bits(unsigned long long buckets) {
-  uint32_t bits = 1;
-  while ((1ull << bits) < buckets) ++bits;
-  return bits;
-}
 
 // The slot's scratch, sized from the context's capacities at first use: the tile x bin counts and the digit totals for every
 // frame; the (key, instance) lists, the bucket histogram and the slot map only once a frame needs more than one pass.
@@ -38,11 +32,55 @@ int32_t ensure_scratch(MipContext* ctx, MipContext::BatchScratch& bs, bool sever
   return MIP_OK;
 }
 
-// `a` is the kernel's own argument block: BatchArgs, or LodBatchArgs whose leading part the shared kernels take
-template <class K, class A>
-int32_t launch(MipContext* ctx, K kernel, uint32_t blocks, hipStream_t stream, A& a) {
+// The instantiation behind every name of the plan (batch_plan.hpp).
+const void* kernel_address(mip::BatchKernel k) {
+  using namespace mip;
+  using K = BatchKernel;
+  using ChainD = BatchLodChainKey<MIP_LOD_DISTANCE>;
+  using ChainR = BatchLodChainKey<MIP_LOD_RELATIVE>;
+  using OrderedD = BatchOrderedKey<MIP_LOD_DISTANCE>;
+  using OrderedR = BatchOrderedKey<MIP_LOD_RELATIVE>;
+  switch (k) {
+    case K::none: break;
+    case K::count_pick: return (const void*)mip_batch_count_kernel<BatchPickLodKey>;
+    case K::count_chain_distance: return (const void*)mip_batch_count_kernel<ChainD>;
+    case K::count_chain_relative: return (const void*)mip_batch_count_kernel<ChainR>;
+    case K::count_ordered_distance: return (const void*)mip_batch_count_kernel<OrderedD>;
+    case K::count_ordered_relative: return (const void*)mip_batch_count_kernel<OrderedR>;
+    case K::count_list: return (const void*)mip_batch_count_kernel<BatchListKey>;
+    case K::scatter_pick_mid: return (const void*)mip_batch_scatter_kernel<BatchPickLodKey, false, 0>;
+    case K::scatter_pick_last: return (const void*)mip_batch_scatter_kernel<BatchPickLodKey, true, 0>;
+    case K::scatter_pick_model: return (const void*)mip_batch_scatter_kernel<BatchPickLodKey, true, 1>;
+    case K::scatter_pick_general: return (const void*)mip_batch_scatter_kernel<BatchPickLodKey, true, 2>;
+    case K::scatter_chain_distance_mid: return (const void*)mip_batch_scatter_kernel<ChainD, false, 0>;
+    case K::scatter_chain_distance_last: return (const void*)mip_batch_scatter_kernel<ChainD, true, 0>;
+    case K::scatter_chain_distance_model: return (const void*)mip_batch_scatter_kernel<ChainD, true, 1>;
+    case K::scatter_chain_distance_general: return (const void*)mip_batch_scatter_kernel<ChainD, true, 2>;
+    case K::scatter_chain_relative_mid: return (const void*)mip_batch_scatter_kernel<ChainR, false, 0>;
+    case K::scatter_chain_relative_last: return (const void*)mip_batch_scatter_kernel<ChainR, true, 0>;
+    case K::scatter_chain_relative_model: return (const void*)mip_batch_scatter_kernel<ChainR, true, 1>;
+    case K::scatter_chain_relative_general: return (const void*)mip_batch_scatter_kernel<ChainR, true, 2>;
+    case K::scatter_ordered_distance_mid: return (const void*)mip_batch_scatter_kernel<OrderedD, false, 0>;
+    case K::scatter_ordered_relative_mid: return (const void*)mip_batch_scatter_kernel<OrderedR, false, 0>;
+    case K::scatter_list_mid: return (const void*)mip_batch_scatter_kernel<BatchListKey, false, 0>;
+    case K::scatter_list_last: return (const void*)mip_batch_scatter_kernel<BatchListKey, true, 0>;
+    case K::model_pick: return (const void*)mip_batch_model_kernel<BatchPickLodKey, false>;
+    case K::model_pick_general: return (const void*)mip_batch_model_kernel<BatchPickLodKey, true>;
+    case K::model_chain_distance: return (const void*)mip_batch_model_kernel<ChainD, false>;
+    case K::model_chain_distance_general: return (const void*)mip_batch_model_kernel<ChainD, true>;
+    case K::model_chain_relative: return (const void*)mip_batch_model_kernel<ChainR, false>;
+    case K::model_chain_relative_general: return (const void*)mip_batch_model_kernel<ChainR, true>;
+    case K::rowscan: return (const void*)mip_batch_rowscan_kernel;
+    case K::commands_pair: return (const void*)mip_batch_commands_kernel<BatchPairDraw>;
+    case K::commands_chain: return (const void*)mip_batch_commands_kernel<BatchChainDraw>;
+  }
+  return nullptr;
+}
+
+// `a` is the most derived argument block; every kernel takes its own leading part of it (BatchArgs, LodBatchArgs or all of it)
+int32_t launch(MipContext* ctx, mip::BatchKernel kernel, uint32_t blocks, hipStream_t stream, mip::OrderedBatchArgs& a) {
   void* params[] = {&a};
-  MIP_HIP(ctx, hipLaunchKernel((const void*)kernel, dim3(blocks), dim3(mip::kTile), params, 0, stream));
+  MIP_HIP(ctx, hipLaunchKernel(kernel_address(kernel), dim3(blocks), dim3(mip::kTile), params, 0, stream));
   MIP_HIP(ctx, hipGetLastError());
   return MIP_OK;
 }
@@ -65,30 +103,6 @@ void batch_release(MipContext* ctx) {
 
 namespace {
 
-// The kernels of mip_batch_draws_lods that form keys, by the policy's mode (a template parameter of each).
-template <uint32_t kMode>
-int32_t launch_scatter_mode(MipContext* ctx, bool last, int model, hipStream_t stream, mip::LodBatchArgs& a) {
-  if (!last) return launch(ctx, mip::mip_batch_lods_scatter_kernel<mip::BatchLodChainKey<kMode>, false, 0>, a.n_tiles, stream, a);
-  return model == 0   ? launch(ctx, mip::mip_batch_lods_scatter_kernel<mip::BatchLodChainKey<kMode>, true, 0>, a.n_tiles, stream, a)
-         : model == 2 ? launch(ctx, mip::mip_batch_lods_scatter_kernel<mip::BatchLodChainKey<kMode>, true, 2>, a.n_tiles, stream, a)
-                      : launch(ctx, mip::mip_batch_lods_scatter_kernel<mip::BatchLodChainKey<kMode>, true, 1>, a.n_tiles, stream, a);
-}
-int32_t launch_scatter(MipContext* ctx, uint32_t mode, bool last, int model, hipStream_t stream, mip::LodBatchArgs& a) {
-  return mode == MIP_LOD_RELATIVE ? launch_scatter_mode<MIP_LOD_RELATIVE>(ctx, last, model, stream, a)
-                                  : launch_scatter_mode<MIP_LOD_DISTANCE>(ctx, last, model, stream, a);
-}
-int32_t launch_count(MipContext* ctx, uint32_t mode, hipStream_t stream, mip::LodBatchArgs& a) {
-  return mode == MIP_LOD_RELATIVE ? launch(ctx, mip::mip_batch_lods_count_kernel<mip::BatchLodChainKey<MIP_LOD_RELATIVE>>, a.n_tiles, stream, a)
-                                  : launch(ctx, mip::mip_batch_lods_count_kernel<mip::BatchLodChainKey<MIP_LOD_DISTANCE>>, a.n_tiles, stream, a);
-}
-int32_t launch_model(MipContext* ctx, uint32_t mode, bool general, hipStream_t stream, mip::LodBatchArgs& a) {
-  if (mode == MIP_LOD_RELATIVE)
-    return general ? launch(ctx, mip::mip_batch_lods_model_kernel<mip::BatchLodChainKey<MIP_LOD_RELATIVE>, true>, a.n_tiles, stream, a)
-                   : launch(ctx, mip::mip_batch_lods_model_kernel<mip::BatchLodChainKey<MIP_LOD_RELATIVE>, false>, a.n_tiles, stream, a);
-  return general ? launch(ctx, mip::mip_batch_lods_model_kernel<mip::BatchLodChainKey<MIP_LOD_DISTANCE>, true>, a.n_tiles, stream, a)
-                 : launch(ctx, mip::mip_batch_lods_model_kernel<mip::BatchLodChainKey<MIP_LOD_DISTANCE>, false>, a.n_tiles, stream, a);
-}
-
 // The argument checks every entry point shares, and the context's device made current.
 int32_t check_call(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipBatchOutputs* out) {
   if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
@@ -105,158 +119,52 @@ int32_t check_call(MipContext* ctx, const MipFrame* frame, const uint32_t* visib
   return MIP_OK;
 }
 
-// mip_batch_draws and mip_batch_draws_lods; policy == null: mip_batch_draws (pick_lod, bucket = mesh * 2 + lod).
-int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+// The three entry points. policy == null: mip_batch_draws (pick_lod, bucket = mesh * 2 + lod); else the whole LOD chain, in
+// draw order (MIP_BATCH_ORDER_DRAW_INDEX: mip_batch_draws_lods) or by key = bucket << 16 | D (NEAR_FIRST / FAR_FIRST).
+int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy, uint32_t order,
                     const MipBatchOutputs* out) {
+  using mip::BatchEntry;
   if (int32_t rc = check_call(ctx, frame, visible_bitmap, out)) return rc;
   // behind the frame issued last: a bitmap that frame writes is ordered before these launches without a wait
   const uint32_t slot = ctx->last_slot;
   hipStream_t stream = ctx->slots[slot].stream;
   const uint32_t n = ctx->n;
+  const BatchEntry entry = !policy ? BatchEntry::draws : order == MIP_BATCH_ORDER_DRAW_INDEX ? BatchEntry::lods : BatchEntry::ordered;
   const unsigned long long buckets = policy ? ctx->lod_buckets : 2ull * ctx->m;
-  if (buckets > 0x80000000ull || (policy && ctx->m > 0x20000000u))
+  if (entry == BatchEntry::ordered) {
+    if (buckets > mip::kBatchOrderedMaxBuckets)
+      return fail(ctx, MIP_ERR_CAPACITY, "%llu buckets: bucket << 16 | depth does not fit a 32-bit key (at most %u)", buckets, mip::kBatchOrderedMaxBuckets);
+  } else if (buckets > 0x80000000ull || (policy && ctx->m > 0x20000000u)) {
     return fail(ctx, MIP_ERR_CAPACITY, "%u meshes, %llu buckets: a bucket does not fit a 32-bit key", ctx->m, buckets);
-
-  if (n == 0 || buckets == 0) {  // nothing to bin: two zeros
-    MIP_HIP(ctx, hipMemsetAsync(out->batch_count, 0, 4, stream));
-    if (out->instance_count) MIP_HIP(ctx, hipMemsetAsync(out->instance_count, 0, 4, stream));
-  } else {
-    const uint32_t bits = key_bits(buckets);
-    const uint32_t passes = (bits + mip::kBatchDigitBits - 1u) / mip::kBatchDigitBits;
-    static_assert(mip::kBatchMaxPasses * mip::kBatchDigitBits >= 32, "a 32-bit key takes at most kBatchMaxPasses digits");
-    const bool several = passes > 1;
-    if (ctx->batch.size() != ctx->slots.size()) ctx->batch.resize(ctx->slots.size());
-    MipContext::BatchScratch& bs = ctx->batch[slot];
-    if (int32_t rc = ensure_scratch(ctx, bs, several, out->batch_model != nullptr)) return rc;
-    // the arithmetic mip_run's `model` comes from: the census decides (frame_plan.hpp, LaunchPlan.general)
-    const bool general = ctx->nonfinite_instances != 0 || ctx->force_general;
-
-    mip::LodBatchArgs a{};  // (mip_batch_draws's kernels take its leading part, BatchArgs)
-    mip::BatchArgs& base = a;
-    const uint32_t mode = policy ? policy->mode : 0u;
-    if (policy) {
-      a.chain = ctx->d_mesh_chain;
-      a.bucket_lod = ctx->d_bucket_lod;
-      std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
-    }
-    a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
-    a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
-    a.bitmap = visible_bitmap;
-    a.n = n;
-    a.n_tiles = batch_tiles_for(n);
-    a.n_buckets = (uint32_t)buckets;
-    a.n_bins = several ? mip::kBatchBins : (uint32_t)buckets;
-    a.first_instance_base = frame->first_instance_base;
-    std::memcpy(a.cam, frame->cam_pos, sizeof a.cam);
-    a.counts = bs.d_counts;
-    a.members = a.members_out = bs.d_totals + mip::kBatchMaxPasses * mip::kBatchBins;
-    a.batch_cmds = static_cast<uint32_t*>(out->batch_cmds);
-    a.batch_count = out->batch_count;
-    a.instance_count = out->instance_count;
-#ifdef MIP_DEBUG_STAMPS
-    DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);  // as fill_kernel_args (api_frame.hip) permutes the frame's tiles
-#endif
-    if (several) MIP_HIP(ctx, hipMemsetAsync(bs.d_bucket_hist, 0, (size_t)buckets * 4, stream));
-
-    for (uint32_t p = 0; p < passes; ++p) {
-      const bool last = p + 1 == passes;
-      a.shift = p * mip::kBatchDigitBits;
-      a.totals = bs.d_totals + p * mip::kBatchBins;
-      a.bucket_hist = (several && p == 0) ? bs.d_bucket_hist : nullptr;
-      a.keys_in = p ? bs.d_keys[(p - 1) & 1u] : nullptr;
-      a.ids_in = p ? bs.d_ids[(p - 1) & 1u] : nullptr;
-      a.keys_out = last ? nullptr : bs.d_keys[p & 1u];
-      a.ids_out = last ? nullptr : bs.d_ids[p & 1u];
-      a.instance_ids = last ? out->instance_ids : nullptr;
-      a.slot_of = (last && several && out->batch_model) ? bs.d_slot_of : nullptr;
-      a.batch_model = (last && !several) ? static_cast<float4*>(out->batch_model) : nullptr;
-      // pass 0 forms keys from the instance columns: the kernels of the call's key policy; the list passes are shared
-      if (int32_t rc = p != 0    ? launch(ctx, mip::mip_batch_count_kernel<true>, a.n_tiles, stream, base)
-                       : !policy ? launch(ctx, mip::mip_batch_count_kernel<false>, a.n_tiles, stream, base)
-                                 : launch_count(ctx, mode, stream, a))
-        return rc;
-      if (int32_t rc = launch(ctx, mip::mip_batch_rowscan_kernel, a.n_bins, stream, base)) return rc;
-      if (p == 0) {  // the scan's epilogue: bucket totals -> commands and the two counts (and the list's length for later passes)
-        a.bucket_totals = several ? bs.d_bucket_hist : a.totals;
-        if (int32_t rc = policy ? launch(ctx, mip::mip_batch_lods_commands_kernel, 1, stream, a)
-                                : launch(ctx, mip::mip_batch_commands_kernel, 1, stream, base))
-          return rc;
-      }
-      int32_t rc;
-      if (p == 0 && policy) {
-        rc = launch_scatter(ctx, mode, last, !a.batch_model ? 0 : general ? 2 : 1, stream, a);
-      } else if (p == 0 && last) {
-        rc = !a.batch_model ? launch(ctx, mip::mip_batch_scatter_kernel<false, true, 0>, a.n_tiles, stream, base)
-             : general      ? launch(ctx, mip::mip_batch_scatter_kernel<false, true, 2>, a.n_tiles, stream, base)
-                            : launch(ctx, mip::mip_batch_scatter_kernel<false, true, 1>, a.n_tiles, stream, base);
-      } else if (p == 0) {
-        rc = launch(ctx, mip::mip_batch_scatter_kernel<false, false, 0>, a.n_tiles, stream, base);
-      } else if (last) {
-        rc = launch(ctx, mip::mip_batch_scatter_kernel<true, true, 0>, a.n_tiles, stream, base);
-      } else {
-        rc = launch(ctx, mip::mip_batch_scatter_kernel<true, false, 0>, a.n_tiles, stream, base);
-      }
-      if (rc) return rc;
-    }
-    if (several && out->batch_model) {
-      a.batch_model = static_cast<float4*>(out->batch_model);
-      if (int32_t rc = policy    ? launch_model(ctx, mode, general, stream, a)
-                       : general ? launch(ctx, mip::mip_batch_model_kernel<true>, a.n_tiles, stream, base)
-                                 : launch(ctx, mip::mip_batch_model_kernel<false>, a.n_tiles, stream, base))
-        return rc;
-    }
   }
-  return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
-}
-
-// The pass-0 kernels of mip_batch_draws_ordered, by the policy's mode.
-int32_t launch_ordered_count(MipContext* ctx, uint32_t mode, hipStream_t stream, mip::OrderedBatchArgs& a) {
-  return mode == MIP_LOD_RELATIVE ? launch(ctx, mip::mip_batch_ordered_count_kernel<mip::BatchOrderedKey<MIP_LOD_RELATIVE>>, a.n_tiles, stream, a)
-                                  : launch(ctx, mip::mip_batch_ordered_count_kernel<mip::BatchOrderedKey<MIP_LOD_DISTANCE>>, a.n_tiles, stream, a);
-}
-int32_t launch_ordered_scatter(MipContext* ctx, uint32_t mode, hipStream_t stream, mip::OrderedBatchArgs& a) {
-  return mode == MIP_LOD_RELATIVE ? launch(ctx, mip::mip_batch_ordered_scatter_kernel<mip::BatchOrderedKey<MIP_LOD_RELATIVE>>, a.n_tiles, stream, a)
-                                  : launch(ctx, mip::mip_batch_ordered_scatter_kernel<mip::BatchOrderedKey<MIP_LOD_DISTANCE>>, a.n_tiles, stream, a);
-}
-
-// mip_batch_draws_ordered, NEAR_FIRST / FAR_FIRST: a stable sort by key = bucket << 16 | D. Pass 0 forms the keys
-// (batch_ordered_kernel.hpp) and counts the buckets; the later digits, the commands and the matrices are the existing kernels.
-int32_t batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
-                            bool far_first, const MipBatchOutputs* out) {
-  if (int32_t rc = check_call(ctx, frame, visible_bitmap, out)) return rc;
-  const uint32_t slot = ctx->last_slot;  // behind the frame issued last, as batch_draws
-  hipStream_t stream = ctx->slots[slot].stream;
-  const uint32_t n = ctx->n;
-  const unsigned long long buckets = ctx->lod_buckets;
-  if (buckets > mip::kBatchOrderedMaxBuckets)
-    return fail(ctx, MIP_ERR_CAPACITY, "%llu buckets: bucket << 16 | depth does not fit a 32-bit key (at most %u)", buckets, mip::kBatchOrderedMaxBuckets);
 
   if (n == 0 || buckets == 0) {  // nothing to bin: two zeros
     MIP_HIP(ctx, hipMemsetAsync(out->batch_count, 0, 4, stream));
     if (out->instance_count) MIP_HIP(ctx, hipMemsetAsync(out->instance_count, 0, 4, stream));
     return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
   }
-  const uint32_t bits = mip::kBatchDepthBits + key_bits(buckets);
-  const uint32_t passes = (bits + mip::kBatchDigitBits - 1u) / mip::kBatchDigitBits;  // 3 up to 256 buckets, 4 up to 65 536
+  // the arithmetic mip_run's `model` comes from: the census decides (frame_plan.hpp, LaunchPlan.general)
+  const bool general = ctx->nonfinite_instances != 0 || ctx->force_general;
+  const mip::BatchPlan plan = mip::plan_batch(entry, policy && policy->mode == MIP_LOD_RELATIVE, buckets, out->batch_model != nullptr, general);
+  const bool several = plan.several();
   if (ctx->batch.size() != ctx->slots.size()) ctx->batch.resize(ctx->slots.size());
   MipContext::BatchScratch& bs = ctx->batch[slot];
-  if (int32_t rc = ensure_scratch(ctx, bs, true, out->batch_model != nullptr)) return rc;
-  const bool general = ctx->nonfinite_instances != 0 || ctx->force_general;
+  if (int32_t rc = ensure_scratch(ctx, bs, several, out->batch_model != nullptr)) return rc;
 
   mip::OrderedBatchArgs a{};
-  mip::LodBatchArgs& lods = a;  // (the command writer and the matrix kernel take this part, the list passes BatchArgs)
-  mip::BatchArgs& base = a;
-  a.depth_flip = far_first ? mip::kBatchDepthMax : 0u;
-  a.chain = ctx->d_mesh_chain;
-  a.bucket_lod = ctx->d_bucket_lod;
-  std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
+  if (policy) {
+    a.chain = ctx->d_mesh_chain;
+    a.bucket_lod = ctx->d_bucket_lod;
+    std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
+  }
+  a.depth_flip = order == MIP_BATCH_ORDER_FAR_FIRST ? mip::kBatchDepthMax : 0u;
   a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
   a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
   a.bitmap = visible_bitmap;
   a.n = n;
   a.n_tiles = batch_tiles_for(n);
   a.n_buckets = (uint32_t)buckets;
-  a.n_bins = mip::kBatchBins;
+  a.n_bins = several ? mip::kBatchBins : (uint32_t)buckets;
   a.first_instance_base = frame->first_instance_base;
   std::memcpy(a.cam, frame->cam_pos, sizeof a.cam);
   a.counts = bs.d_counts;
@@ -264,36 +172,34 @@ int32_t batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const uint32
   a.batch_cmds = static_cast<uint32_t*>(out->batch_cmds);
   a.batch_count = out->batch_count;
   a.instance_count = out->instance_count;
-  a.bucket_totals = bs.d_bucket_hist;
 #ifdef MIP_DEBUG_STAMPS
-  DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);
+  DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);  // as fill_kernel_args (api_frame.hip) permutes the frame's tiles
 #endif
-  MIP_HIP(ctx, hipMemsetAsync(bs.d_bucket_hist, 0, (size_t)buckets * 4, stream));
+  if (several) MIP_HIP(ctx, hipMemsetAsync(bs.d_bucket_hist, 0, (size_t)buckets * 4, stream));
 
-  for (uint32_t p = 0; p < passes; ++p) {
-    const bool last = p + 1 == passes;
+  for (uint32_t p = 0; p < plan.passes; ++p) {
+    const bool last = p + 1 == plan.passes;
     a.shift = p * mip::kBatchDigitBits;
     a.totals = bs.d_totals + p * mip::kBatchBins;
-    a.bucket_hist = p == 0 ? bs.d_bucket_hist : nullptr;
+    a.bucket_hist = (several && p == 0) ? bs.d_bucket_hist : nullptr;
     a.keys_in = p ? bs.d_keys[(p - 1) & 1u] : nullptr;
     a.ids_in = p ? bs.d_ids[(p - 1) & 1u] : nullptr;
     a.keys_out = last ? nullptr : bs.d_keys[p & 1u];
     a.ids_out = last ? nullptr : bs.d_ids[p & 1u];
     a.instance_ids = last ? out->instance_ids : nullptr;
-    a.slot_of = (last && out->batch_model) ? bs.d_slot_of : nullptr;
-    if (int32_t rc = p == 0 ? launch_ordered_count(ctx, policy->mode, stream, a) : launch(ctx, mip::mip_batch_count_kernel<true>, a.n_tiles, stream, base))
-      return rc;
-    if (int32_t rc = launch(ctx, mip::mip_batch_rowscan_kernel, a.n_bins, stream, base)) return rc;
-    if (p == 0)  // bucket totals -> commands, the two counts and the list's length
-      if (int32_t rc = launch(ctx, mip::mip_batch_lods_commands_kernel, 1, stream, lods)) return rc;
-    if (int32_t rc = p == 0 ? launch_ordered_scatter(ctx, policy->mode, stream, a)
-                     : last ? launch(ctx, mip::mip_batch_scatter_kernel<true, true, 0>, a.n_tiles, stream, base)
-                            : launch(ctx, mip::mip_batch_scatter_kernel<true, false, 0>, a.n_tiles, stream, base))
-      return rc;
+    a.slot_of = (last && several && out->batch_model) ? bs.d_slot_of : nullptr;
+    a.batch_model = (last && !several) ? static_cast<float4*>(out->batch_model) : nullptr;
+    if (int32_t rc = launch(ctx, plan.count(p), a.n_tiles, stream, a)) return rc;
+    if (int32_t rc = launch(ctx, mip::BatchKernel::rowscan, a.n_bins, stream, a)) return rc;
+    if (p == 0) {  // the scan's epilogue: bucket totals -> commands and the two counts (and the list's length for later passes)
+      a.bucket_totals = several ? bs.d_bucket_hist : a.totals;
+      if (int32_t rc = launch(ctx, plan.commands, 1, stream, a)) return rc;
+    }
+    if (int32_t rc = launch(ctx, plan.scatter(p), a.n_tiles, stream, a)) return rc;
   }
-  if (out->batch_model) {
+  if (plan.model != mip::BatchKernel::none) {
     a.batch_model = static_cast<float4*>(out->batch_model);
-    if (int32_t rc = launch_model(ctx, policy->mode, general, stream, lods)) return rc;
+    if (int32_t rc = launch(ctx, plan.model, a.n_tiles, stream, a)) return rc;
   }
   return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
 }
@@ -322,14 +228,14 @@ extern "C" {
 
 int32_t mip_batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipBatchOutputs* out) {
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
-  return batch_draws(ctx, frame, visible_bitmap, nullptr, out);
+  return batch_draws(ctx, frame, visible_bitmap, nullptr, MIP_BATCH_ORDER_DRAW_INDEX, out);
 }
 
 int32_t mip_batch_draws_lods(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
                              const MipBatchOutputs* out) {
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
   if (int32_t rc = check_policy(ctx, policy)) return rc;
-  return batch_draws(ctx, frame, visible_bitmap, policy, out);
+  return batch_draws(ctx, frame, visible_bitmap, policy, MIP_BATCH_ORDER_DRAW_INDEX, out);
 }
 
 int32_t mip_batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
@@ -338,8 +244,7 @@ int32_t mip_batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const ui
   if (order != MIP_BATCH_ORDER_DRAW_INDEX && order != MIP_BATCH_ORDER_NEAR_FIRST && order != MIP_BATCH_ORDER_FAR_FIRST)
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown order %u", order);
   if (int32_t rc = check_policy(ctx, policy)) return rc;
-  if (order == MIP_BATCH_ORDER_DRAW_INDEX) return batch_draws(ctx, frame, visible_bitmap, policy, out);
-  return batch_draws_ordered(ctx, frame, visible_bitmap, policy, order == MIP_BATCH_ORDER_FAR_FIRST, out);
+  return batch_draws(ctx, frame, visible_bitmap, policy, order, out);
 }
 
 }  // extern "C"

@@ -21,8 +21,22 @@
 // A tile is kBatchTile = 1024 instances: wave w of the workgroup takes instances [256 w, 256 w + 256) of it in four rounds of
 // 64 CONSECUTIVE instances, aligned as the frame kernel's waves are — so instance_tiered decides for the same 64 instances as in
 // mip_run and batch_model is byte-identical to its `model` output — and four times fewer rows of counts than a 256-instance tile.
+//
+// The stage is written once, over a KEY POLICY that says where a pass's keys come from:
+//
+//   Args                     the kernel's argument block: BatchArgs or a struct derived from it (the host fills the most derived one)
+//   kFromList                the pass reads the (key, instance) list of the pass before it, not the instance columns
+//   kBucketHist              whether count adds every member to bucket_hist[bucket_of(key)]: never / when the pointer is given / always
+//   load(a, idx, list_len)   the key of entry idx, or kBatchNone
+//   id(a, idx)               the instance behind entry idx
+//   bucket_of(key)           the bucket a key belongs to
+//
+// BatchPickLodKey (mip_batch_draws) and BatchListKey (the later passes of any several-pass sort) are below; the policies over
+// the whole LOD chain (mip_batch_draws_lods, mip_batch_draws_ordered) are in batch_lods_kernel.hpp. The command writer takes a
+// policy of its own: how a bucket maps to (indexCount, firstIndex, vertexOffset). Instantiated in api_batch.hip only.
 #pragma once
 
+#include "batch_plan.hpp"
 #include "instance_kernel.hpp"
 
 #pragma clang fp contract(off)
@@ -32,10 +46,9 @@ namespace mip {
 constexpr uint32_t kBatchRounds = 4;
 constexpr uint32_t kBatchTile = kTile * kBatchRounds;
 constexpr uint32_t kBatchBins = 256;
-constexpr uint32_t kBatchDigitBits = 8;
-constexpr uint32_t kBatchMaxPasses = 4;
 constexpr uint32_t kBatchNone = 0xffffffffu;  // the key of an instance that is not a member; a slot that is not stored
 static_assert(kTile == 256 && kWaves == 4, "one thread per bin; four waves of four rounds");
+static_assert(kBatchBins == 1u << kBatchDigitBits, "one bin per value of a digit");
 
 struct BatchArgs {
   // resident inputs
@@ -108,52 +121,75 @@ __device__ __forceinline__ uint32_t batch_block_scan(uint32_t v, uint32_t* s_wav
 // (`pad`, filled by mip_set_mesh_table), which no other kernel reads.
 __device__ __forceinline__ uint32_t mesh_has_lod1(const MeshDraw& md) { return md.pad; }
 
-// The bucket of instance il (mesh_id * 2 + lod), or kBatchNone when it is not a member. The LOD and the length are the
-// frame kernel's: lod_is_far against the frame's reference point, len1 falling back to LOD 0 for a one-LOD mesh — whose
-// bucket is then LOD 0's, as pick_lod returns 0 for it at any distance.
-__device__ __forceinline__ uint32_t batch_key(const BatchArgs& a, uint32_t il, bool active) {
-  const uint32_t word = a.bitmap[il >> 5];
-  const float px = a.pos[3 * (size_t)il + 0], py = a.pos[3 * (size_t)il + 1], pz = a.pos[3 * (size_t)il + 2];
-  const uint32_t mesh = a.mesh_id[il];
-  const MeshEntry mb = load_mesh_entry(a.meshes, mesh);
-  const bool far_lod = lod_is_far(a.cam, px, py, pz);
-  const uint32_t len = far_lod ? mb.len1 : mb.len0;
-  const uint32_t lod = far_lod ? mesh_has_lod1(a.mesh_draw[mesh]) : 0u;
-  const bool member = active && ((word >> (il & 31u)) & 1u) != 0u && len > 0u;
-  return member ? mesh * 2u + lod : kBatchNone;
-}
-
 // Instance (tile, wave, round, lane) of the tiling described at the top.
 __device__ __forceinline__ uint32_t batch_index(uint32_t tile, uint32_t wave, uint32_t round, uint32_t lane) {
   return tile * kBatchTile + wave * (kBatchRounds * 64u) + round * 64u + lane;
 }
 
-template <bool kFromList>
-__device__ __forceinline__ uint32_t batch_load_key(const BatchArgs& a, uint32_t idx, uint32_t list_len) {
-  if constexpr (kFromList) {
-    return idx < list_len ? a.keys_in[idx] : kBatchNone;
-  } else {
-    const bool active = idx < a.n;
-    return batch_key(a, active ? idx : a.n - 1u, active);
-  }
-}
+enum class BatchBucketHist { never, when_given, always };
 
-// ---- count: the tile's histogram of this pass's digit ----
-template <bool kFromList>
-__global__ __launch_bounds__(kTile) void mip_batch_count_kernel(const BatchArgs a) {
+// What the policies that form keys from the instance columns share: Key::key(a, il, active) sees an index in bounds (an idle
+// lane loads the last instance, as in the frame kernel), and an entry IS its instance.
+template <class Key, class A>
+struct BatchInstanceKey {
+  using Args = A;
+  static constexpr bool kFromList = false;
+  static __device__ __forceinline__ uint32_t load(const A& a, uint32_t idx, uint32_t) {
+    const bool active = idx < a.n;
+    return Key::key(a, active ? idx : a.n - 1u, active);
+  }
+  static __device__ __forceinline__ uint32_t id(const A&, uint32_t idx) { return idx; }
+};
+
+// mip_batch_draws: bucket = mesh_id * 2 + lod, or kBatchNone when instance il is not a member. The LOD and the length are the
+// frame kernel's: lod_is_far against the frame's reference point, len1 falling back to LOD 0 for a one-LOD mesh — whose
+// bucket is then LOD 0's, as pick_lod returns 0 for it at any distance.
+struct BatchPickLodKey : BatchInstanceKey<BatchPickLodKey, BatchArgs> {
+  static constexpr BatchBucketHist kBucketHist = BatchBucketHist::when_given;  // pass 0 of several
+  static __device__ __forceinline__ uint32_t key(const BatchArgs& a, uint32_t il, bool active) {
+    const uint32_t word = a.bitmap[il >> 5];
+    const float px = a.pos[3 * (size_t)il + 0], py = a.pos[3 * (size_t)il + 1], pz = a.pos[3 * (size_t)il + 2];
+    const uint32_t mesh = a.mesh_id[il];
+    const MeshEntry mb = load_mesh_entry(a.meshes, mesh);
+    const bool far_lod = lod_is_far(a.cam, px, py, pz);
+    const uint32_t len = far_lod ? mb.len1 : mb.len0;
+    const uint32_t lod = far_lod ? mesh_has_lod1(a.mesh_draw[mesh]) : 0u;
+    const bool member = active && ((word >> (il & 31u)) & 1u) != 0u && len > 0u;
+    return member ? mesh * 2u + lod : kBatchNone;
+  }
+  static __device__ __forceinline__ uint32_t bucket_of(uint32_t key) { return key; }
+};
+
+// The later passes of a several-pass sort, under any policy: the (key, instance) list the pass before wrote.
+struct BatchListKey {
+  using Args = BatchArgs;
+  static constexpr bool kFromList = true;
+  static constexpr BatchBucketHist kBucketHist = BatchBucketHist::never;  // pass 0 counted the buckets
+  static __device__ __forceinline__ uint32_t load(const BatchArgs& a, uint32_t idx, uint32_t list_len) {
+    return idx < list_len ? a.keys_in[idx] : kBatchNone;
+  }
+  static __device__ __forceinline__ uint32_t id(const BatchArgs& a, uint32_t idx) { return a.ids_in[idx]; }
+};
+
+// ---- count: the tile's histogram of this pass's digit; pass 0 of several also counts the members of every bucket ----
+template <class Key>
+__global__ __launch_bounds__(kTile) void mip_batch_count_kernel(const typename Key::Args a) {
   __shared__ uint32_t s_hist[kBatchBins];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t tile = batch_tile(a);
-  const uint32_t list_len = kFromList ? *a.members : 0u;
+  const uint32_t list_len = Key::kFromList ? *a.members : 0u;
   s_hist[tid] = 0u;
   __syncthreads();
 #pragma unroll
   for (uint32_t r = 0; r < kBatchRounds; ++r) {
-    const uint32_t key = batch_load_key<kFromList>(a, batch_index(tile, wave, r, lane), list_len);
+    const uint32_t key = Key::load(a, batch_index(tile, wave, r, lane), list_len);
     if (key != kBatchNone) {
       atomicAdd(&s_hist[(key >> a.shift) & (kBatchBins - 1u)], 1u);
-      if constexpr (!kFromList)
-        if (a.bucket_hist) atomicAdd(&a.bucket_hist[key], 1u);
+      if constexpr (Key::kBucketHist == BatchBucketHist::always) {
+        atomicAdd(&a.bucket_hist[Key::bucket_of(key)], 1u);  // < n_buckets: the host sizes bucket_hist for the table
+      } else if constexpr (Key::kBucketHist == BatchBucketHist::when_given) {
+        if (a.bucket_hist) atomicAdd(&a.bucket_hist[Key::bucket_of(key)], 1u);
+      }
     }
   }
   __syncthreads();
@@ -176,8 +212,27 @@ static __global__ __launch_bounds__(kTile) __attribute__((unused)) void mip_batc
   if (threadIdx.x == 0) a.totals[blockIdx.x] = carry;
 }
 
+// What a bucket draws: the command writer's policy maps a bucket to these three words.
+struct BatchDraw {
+  uint32_t index_count, first_index, vertex_offset;
+};
+
+// mip_batch_draws: bucket = mesh * 2 + lod over MeshEntry / MeshDraw.
+struct BatchPairDraw {
+  using Args = BatchArgs;
+  static __device__ __forceinline__ BatchDraw draw(const BatchArgs& a, uint32_t b) {
+    const uint32_t mesh = b >> 1;
+    const bool far_lod = (b & 1u) != 0u;
+    const MeshEntry mb = load_mesh_entry(a.meshes, mesh);
+    const MeshDraw md = a.mesh_draw[mesh];
+    // firstIndex: the mesh's own range of the consolidated index buffer
+    return {far_lod ? mb.len1 : mb.len0, far_lod ? md.src_offset1 : md.src_offset0, (uint32_t)md.vertex_offset};
+  }
+};
+
 // ---- commands: one per non-empty bucket, ascending, packed; the two counts. One workgroup. ----
-static __global__ __launch_bounds__(kTile) __attribute__((unused)) void mip_batch_commands_kernel(const BatchArgs a) {
+template <class Draw>
+__global__ __launch_bounds__(kTile) void mip_batch_commands_kernel(const typename Draw::Args a) {
   __shared__ uint32_t s_wave[kWaves];
   uint32_t cmds_before = 0, members_before = 0;
   for (uint32_t first = 0; first < a.n_buckets; first += kTile) {  // (wraps only past 2^32 - 256 buckets: the host refuses those)
@@ -187,16 +242,13 @@ static __global__ __launch_bounds__(kTile) __attribute__((unused)) void mip_batc
     const uint32_t slot = members_before + batch_block_scan(c, s_wave, chunk_members);
     const uint32_t at = cmds_before + batch_block_scan(c ? 1u : 0u, s_wave, chunk_cmds);
     if (c) {
-      const uint32_t mesh = b >> 1;
-      const bool far_lod = (b & 1u) != 0u;
-      const MeshEntry mb = load_mesh_entry(a.meshes, mesh);
-      const MeshDraw md = a.mesh_draw[mesh];
+      const BatchDraw d = Draw::draw(a, b);
       uint32_t* o = a.batch_cmds + (size_t)at * kCmdWords;
-      o[0] = far_lod ? mb.len1 : mb.len0;                // indexCount
-      o[1] = c;                                          // instanceCount
-      o[2] = far_lod ? md.src_offset1 : md.src_offset0;  // firstIndex: the mesh's own range of the consolidated index buffer
-      o[3] = (uint32_t)md.vertex_offset;                 // vertexOffset
-      o[4] = slot;                                       // firstInstance: the slot of the bucket's first member
+      o[0] = d.index_count;    // indexCount
+      o[1] = c;                // instanceCount
+      o[2] = d.first_index;    // firstIndex
+      o[3] = d.vertex_offset;  // vertexOffset
+      o[4] = slot;             // firstInstance: the slot of the bucket's first member
     }
     cmds_before += chunk_cmds;
     members_before += chunk_members;
@@ -254,16 +306,17 @@ __device__ __forceinline__ void batch_store_models(const BatchArgs& a, uint32_t 
 }
 
 // ---- scatter: every member of the tile to its slot of this pass ----
+// kLast: the key's last digit — slots are final (instance_ids, slot_of); else the pass writes the next (key, instance) list.
 // kModel: 0 = no matrices, 1 = census-selected arithmetic (every resident instance is separable_safe), 2 = the tiers of kGeneral
-template <bool kFromList, bool kLast, int kModel>
-__global__ __launch_bounds__(kTile) void mip_batch_scatter_kernel(const BatchArgs a) {
-  static_assert(!kModel || (!kFromList && kLast), "matrices go out with the one pass that reads the instances in draw order");
+template <class Key, bool kLast, int kModel>
+__global__ __launch_bounds__(kTile) void mip_batch_scatter_kernel(const typename Key::Args a) {
+  static_assert(!kModel || (!Key::kFromList && kLast), "matrices go out with the one pass that reads the instances in draw order");
   __shared__ uint32_t s_hist[kWaves][kBatchBins];
   __shared__ uint32_t s_wave[kWaves];
   __shared__ __attribute__((aligned(16))) std::conditional_t<kModel != 0, BatchModelStage, uint32_t> s_stage;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t tile = batch_tile(a);
-  const uint32_t list_len = kFromList ? *a.members : 0u;
+  const uint32_t list_len = Key::kFromList ? *a.members : 0u;
 #pragma unroll
   for (uint32_t w = 0; w < kWaves; ++w) s_hist[w][tid] = 0u;
   __syncthreads();
@@ -273,7 +326,7 @@ __global__ __launch_bounds__(kTile) void mip_batch_scatter_kernel(const BatchArg
   uint32_t key[kBatchRounds], rank[kBatchRounds];
 #pragma unroll
   for (uint32_t r = 0; r < kBatchRounds; ++r) {
-    key[r] = batch_load_key<kFromList>(a, batch_index(tile, wave, r, lane), list_len);
+    key[r] = Key::load(a, batch_index(tile, wave, r, lane), list_len);
     const bool valid = key[r] != kBatchNone;
     const uint32_t digit = valid ? (key[r] >> a.shift) & (kBatchBins - 1u) : 0u;
     unsigned long long same = __ballot(valid);
@@ -312,8 +365,8 @@ __global__ __launch_bounds__(kTile) void mip_batch_scatter_kernel(const BatchArg
     const bool valid = key[r] != kBatchNone;
     uint32_t slot = kBatchNone;
     if (valid) {
-      slot = s_hist[wave][(key[r] >> a.shift) & (kBatchBins - 1u)] + rank[r];
-      const uint32_t id = kFromList ? a.ids_in[idx] : idx;
+      slot = s_hist[wave][(key[r] >> a.shift) & (kBatchBins - 1u)] + rank[r];  // < members <= n
+      const uint32_t id = Key::id(a, idx);
       if constexpr (kLast) {
         a.instance_ids[slot] = a.first_instance_base + id;
         if (a.slot_of) a.slot_of[id] = slot;
@@ -327,15 +380,16 @@ __global__ __launch_bounds__(kTile) void mip_batch_scatter_kernel(const BatchArg
 }
 
 // ---- matrices of a frame that took several passes: the instances in draw order, each member to slot_of[instance] ----
-template <bool kGeneral>
-__global__ __launch_bounds__(kTile) void mip_batch_model_kernel(const BatchArgs a) {
+template <class Key, bool kGeneral>
+__global__ __launch_bounds__(kTile) void mip_batch_model_kernel(const typename Key::Args a) {
+  static_assert(!Key::kFromList, "membership is formed from the instance columns");
   __shared__ __attribute__((aligned(16))) BatchModelStage s_stage;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t tile = batch_tile(a);
 #pragma unroll 1
   for (uint32_t r = 0; r < kBatchRounds; ++r) {
     const uint32_t idx = batch_index(tile, wave, r, lane);
-    const bool member = batch_load_key<false>(a, idx, 0u) != kBatchNone;
+    const bool member = Key::load(a, idx, 0u) != kBatchNone;
     batch_store_models<kGeneral>(a, idx, member ? a.slot_of[idx] : kBatchNone, s_stage);
   }
 }

@@ -1,0 +1,77 @@
+// batch_plan.hpp — which kernels a batched-draws call launches: a pure function of the entry point, the policy's mode, the
+// bucket count, whether matrices are wanted and the census decision. Plain C++, no HIP: enumerated on the CPU by
+// tests/native/batch_plan_check.cpp. api_batch.hip maps a BatchKernel to its instantiation and executes the plan.
+#pragma once
+
+#include <cstdint>
+
+namespace mip {
+
+constexpr uint32_t kBatchDigitBits = 8;
+constexpr uint32_t kBatchMaxPasses = 4;
+constexpr uint32_t kBatchDepthBits = 16;  // D's field of the ordered key (batch_lods_kernel.hpp)
+static_assert(kBatchMaxPasses * kBatchDigitBits >= 32, "a 32-bit key takes at most kBatchMaxPasses digits");
+
+enum class BatchEntry : uint32_t { draws, lods, ordered };  // mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered (NEAR / FAR)
+
+// Every instantiation of the stage (batch_kernel.hpp), by key policy. scatter: `mid` = a pass of several, `last` = the one
+// pass, ids only, `model` / `general` = the one pass with matrices (census-selected / general arithmetic).
+enum class BatchKernel : uint32_t {
+  none,
+  count_pick, count_chain_distance, count_chain_relative, count_ordered_distance, count_ordered_relative, count_list,
+  scatter_pick_mid, scatter_pick_last, scatter_pick_model, scatter_pick_general,
+  scatter_chain_distance_mid, scatter_chain_distance_last, scatter_chain_distance_model, scatter_chain_distance_general,
+  scatter_chain_relative_mid, scatter_chain_relative_last, scatter_chain_relative_model, scatter_chain_relative_general,
+  scatter_ordered_distance_mid, scatter_ordered_relative_mid,
+  scatter_list_mid, scatter_list_last,
+  model_pick, model_pick_general, model_chain_distance, model_chain_distance_general, model_chain_relative, model_chain_relative_general,
+  rowscan, commands_pair, commands_chain,
+};
+
+struct BatchPlan {
+  uint32_t passes;         // digits of the key
+  BatchKernel count0;      // pass 0 forms keys from the instance columns; passes 1.. are the list kernels
+  BatchKernel scatter0;
+  BatchKernel commands;
+  BatchKernel model;       // the matrices of a several-pass frame, through slot_of; none when scatter0 stores them or nobody asked
+  constexpr bool several() const { return passes > 1; }
+  constexpr BatchKernel count(uint32_t p) const { return p ? BatchKernel::count_list : count0; }
+  constexpr BatchKernel scatter(uint32_t p) const { return !p ? scatter0 : p + 1 == passes ? BatchKernel::scatter_list_last : BatchKernel::scatter_list_mid; }
+};
+
+// ceil(log2(buckets)), at least 1: the bits of a bucket
+constexpr uint32_t batch_key_bits(unsigned long long buckets) {
+  uint32_t bits = 1;
+  while ((1ull << bits) < buckets) ++bits;
+  return bits;
+}
+
+// `relative`: the policy's mode is MIP_LOD_RELATIVE (ignored by mip_batch_draws, which has no policy). buckets >= 1.
+constexpr BatchPlan plan_batch(BatchEntry entry, bool relative, unsigned long long buckets, bool want_model, bool general) {
+  using K = BatchKernel;
+  // rows: pick_lod, the chain under DISTANCE, under RELATIVE
+  constexpr K scatter[3][4] = {{K::scatter_pick_mid, K::scatter_pick_last, K::scatter_pick_model, K::scatter_pick_general},
+                               {K::scatter_chain_distance_mid, K::scatter_chain_distance_last, K::scatter_chain_distance_model, K::scatter_chain_distance_general},
+                               {K::scatter_chain_relative_mid, K::scatter_chain_relative_last, K::scatter_chain_relative_model, K::scatter_chain_relative_general}};
+  constexpr K count[3] = {K::count_pick, K::count_chain_distance, K::count_chain_relative};
+  constexpr K model[3][2] = {{K::model_pick, K::model_pick_general}, {K::model_chain_distance, K::model_chain_distance_general},
+                             {K::model_chain_relative, K::model_chain_relative_general}};
+  const bool ordered = entry == BatchEntry::ordered;
+  const uint32_t bits = (ordered ? kBatchDepthBits : 0u) + batch_key_bits(buckets);  // ordered: always several passes
+  const uint32_t row = entry == BatchEntry::draws ? 0u : relative ? 2u : 1u;
+  BatchPlan p{};
+  p.passes = (bits + kBatchDigitBits - 1u) / kBatchDigitBits;
+  p.commands = entry == BatchEntry::draws ? K::commands_pair : K::commands_chain;
+  if (ordered) {
+    p.count0 = relative ? K::count_ordered_relative : K::count_ordered_distance;
+    p.scatter0 = relative ? K::scatter_ordered_relative_mid : K::scatter_ordered_distance_mid;
+  } else {
+    p.count0 = count[row];
+    p.scatter0 = scatter[row][p.several() ? 0 : !want_model ? 1 : general ? 3 : 2];
+  }
+  // membership does not depend on the order: the ordered path stores matrices with the chain policy's model kernel
+  p.model = p.several() && want_model ? model[row][general ? 1 : 0] : K::none;
+  return p;
+}
+
+}  // namespace mip

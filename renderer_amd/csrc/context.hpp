@@ -5,8 +5,8 @@
 //   api_sharded.hip   shard merges, the collective-library seam, mip_run_sharded and its collective repair
 //   api_interop.hip   external memory and external semaphores (row f-2)
 //   api_occlusion.hip the occlusion-culling extension: depth pyramid builds, mip_run_occluded (occlusion_kernel.hpp)
-//   api_batch.hip     the batched-draws extension: mip_batch_draws (batch_kernel.hpp), mip_batch_draws_lods (batch_lods_kernel.hpp),
-//                     mip_batch_draws_ordered (batch_ordered_kernel.hpp)
+//   api_batch.hip     the batched-draws extension: mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered — one stage
+//                     (batch_kernel.hpp) under the key policies of batch_lods_kernel.hpp, planned by batch_plan.hpp
 // (round 3 had all of it in one 2 224-line mip_api.hip)
 #pragma once
 

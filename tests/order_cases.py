@@ -1,7 +1,7 @@
 """Scenes for mip_batch_draws_ordered whose slot orders are written out by hand (tests/test_order_cases.py checks the
 restatement against them; tests/test_gpu_batch_ordered.py runs the same scenes on the device).
 
-Both scenes: camera at the origin, every instance a candidate (a bitmap of ones), a table of one-level meshes, so every
+The first two scenes: camera at the origin, every instance a candidate (a bitmap of ones), a table of one-level meshes, so every
 instance selects LOD 0 under any policy and bucket = mesh. K = bits(q) >> 16 of q = |pos|^2 in float32.
 
 edge_scene: n = 1024 + 3 * 64 + 17 instances (a ragged second tile, as lod_cases.edge_scene). Fillers (mesh 0, x = 1) are bucket
@@ -119,3 +119,39 @@ def want_tie_slots(near_first):
     g = tie_groups()
     groups = (0, 1, 2) if near_first else (2, 1, 0)
     return np.concatenate([np.nonzero(g == k)[0] for k in groups]).astype(np.int64)
+
+
+# ---- one class, different K, in one wave round: what the per-bucket count of pass 0 indexes by ----
+# n = 64: one round of one wave. One mesh of two levels, so the buckets are its LODs; under lod_cases.SWITCH at scale 0.5 LOD 1
+# starts beyond x = 2 (DISTANCE) or x = 3 (RELATIVE, b_0 = 4 * 2.25 = 9): x <= 2 is bucket 0 and x >= 5 bucket 1 in both modes.
+#
+#   instance  position   q        bits(q)      K        bucket  NEAR key     FAR key (D = 0x7F80 - K)
+#    3        x = 5.5    30.25    0x41F20000   0x41F2   1       0x000141F2   0x00013D8E
+#    7        x = 1.25   1.5625   0x3FC80000   0x3FC8   0       0x00003FC8   0x00003FB8
+#   40        x = 5      25       0x41C80000   0x41C8   1       0x000141C8   0x00013DB8
+#   others    x = 1      1        0x3F800000   0x3F80   0       0x00003F80   0x00004000
+#
+# Instances 3 and 40 are one bucket and differ only in the key's lowest digit (F2 / C8 near first, 8E / B8 far first);
+# instance 7 has instance 40's lowest digit in BOTH orders, from the other bucket. A stage that counted the members of a
+# bucket by the whole key, by its lowest digit or by any shift but 16 would not put 62 and 2 into the two commands.
+N_DIGIT = 64
+DIGIT_CASES = ((3, 5.5, 0x41F20000, 1), (7, 1.25, 0x3FC80000, 0), (40, 5.0, 0x41C80000, 1))   # (instance, x, bits(q), bucket)
+DIGIT_FILLER_BITS = 0x3F800000
+DIGIT_NEAR_FIRST = tuple(i for i in range(N_DIGIT) if i not in (3, 7, 40)) + (7,) + (40, 3)   # bucket 0: the fillers, then 7; bucket 1: 40, 3
+DIGIT_FAR_FIRST = (7,) + tuple(i for i in range(N_DIGIT) if i not in (3, 7, 40)) + (3, 40)     # bucket 0: 7, then the fillers; bucket 1: 3, 40
+DIGIT_COUNTS = (62, 2)
+
+
+def digit_scene():
+    n = N_DIGIT
+    pos = np.zeros((n, 3), F)
+    pos[:, 0] = 1.0
+    for inst, x, _, _ in DIGIT_CASES:
+        pos[inst, 0] = x
+    rot = np.zeros((n, 4), F)
+    rot[:, 3] = 1.0
+    return dict(n=n, pos=pos, rot=rot, scale=np.full(n, 0.5, F), mesh_id=np.zeros(n, np.uint32), meshes=lc.chain_table([2], seed=5), cam_pos=np.zeros(3, F))
+
+
+def want_digit_slots(near_first):
+    return np.array(DIGIT_NEAR_FIRST if near_first else DIGIT_FAR_FIRST, np.int64)

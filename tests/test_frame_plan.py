@@ -49,10 +49,24 @@ def test_skin_plan_tables_over_every_small_skeleton(tmp_path):
     assert int(last.split()[2]) >= 5913 + 25 * 164    # 8 .. 32 joints: four families + 160 random arrays each: the sweep really ran
 
 
+def test_batch_plan_selects_the_kernels_the_entry_points_selected(tmp_path):
+    """plan_batch (renderer_amd/csrc/batch_plan.hpp), which instantiation of the batched-draws stage every launch of a call is:
+    every entry point, mode, bucket count at the pass boundaries, with and without matrices, both census decisions — against the
+    nested conditions the three entry points held before they shared one plan. A wrong entry is another key policy's kernel."""
+    exe = str(tmp_path / "batch_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "native", "batch_plan_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    last = out.stdout.strip().split("\n")[-1]
+    assert last.startswith("BATCH PLAN OK"), out.stdout[-2000:]
+    assert int(last.split()[3]) == 2 * 2 * 15 * 4 + 2 * 10 * 4   # draws and lods at 15 bucket counts, ordered at the 10 it accepts
+
+
 def test_plan_header_has_no_hip_dependency():
-    """frame_plan.hpp, prefix_tags.hpp and skin_plan.hpp must stay compilable by a plain host compiler: that is what keeps the
-    decision table, the tag rule and the skeleton tables testable here."""
-    for header in ("frame_plan.hpp", "prefix_tags.hpp", "skin_plan.hpp"):
+    """frame_plan.hpp, prefix_tags.hpp, skin_plan.hpp and batch_plan.hpp must stay compilable by a plain host compiler: that is
+    what keeps the decision tables, the tag rule and the skeleton tables testable here."""
+    for header in ("frame_plan.hpp", "prefix_tags.hpp", "skin_plan.hpp", "batch_plan.hpp"):
         text = open(os.path.join(ROOT, "renderer_amd", "csrc", header)).read()
         assert "hip/" not in text and "__device__" not in text and "__global__" not in text, header
     api = open(os.path.join(ROOT, "renderer_amd", "csrc", "api_frame.hip")).read()

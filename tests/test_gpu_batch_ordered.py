@@ -167,6 +167,21 @@ def test_decision_edges_on_the_device(ra, order):
                 assert p.timings()["general_launches"] > 0   # the non-finite instances put batch_model on the literal path
 
 
+@pytest.mark.parametrize("order", ORDERS)
+def test_one_bucket_two_depths_in_one_wave_round(ra, order):
+    """order_cases.digit_scene: 64 instances of one two-level mesh, two members of bucket 1 whose keys differ only in the lowest
+    digit and a member of bucket 0 that shares that digit with one of them. The two commands hold 62 and 2 members only if the
+    count of pass 0 indexes its per-bucket histogram by key >> 16."""
+    s = oc.digit_scene()
+    s["planes"] = ra.scene.default_planes()
+    slots = oc.want_digit_slots(order == orr.NEAR_FIRST)
+    with T._pipeline(ra, s) as p:
+        for mode in MODES:
+            want = _frame_then_ordered(p, s, mode, lc.SWITCH, order, f"digit mode={mode} order={order}", base=5, bitmap=lc.all_bits(s["n"]),
+                                       want_slots=slots)
+            assert want["cmds"]["instanceCount"].tolist() == list(oc.DIGIT_COUNTS) and want["cmds"]["firstInstance"].tolist() == [0, 62]
+
+
 # ---- 5. any dispatch order (the diagnostic library, a child process); a non-finite scene ----
 
 _ORDER_CHILD = r'''

@@ -73,3 +73,37 @@ def test_hand_written_slot_orders_of_the_tie_scene(order):
     want = oc.want_tie_slots(order == orr.NEAR_FIRST)
     assert got["count"] == 1 and got["members"] == s["n"]
     assert got["order"].tolist() == want.tolist()
+
+
+def test_the_digit_scene_is_what_its_table_says():
+    s = oc.digit_scene()
+    q = _q(s["pos"])
+    assert s["n"] == 64 and len(s["meshes"]) == 1 and int(s["meshes"]["n_lods"][0]) == 2     # one round of one wave; the buckets are the LODs
+    bits = q.view(np.uint32)
+    cases = {c[0]: c for c in oc.DIGIT_CASES}
+    for i in range(s["n"]):
+        assert int(bits[i]) == (cases[i][2] if i in cases else oc.DIGIT_FILLER_BITS), i
+    for mode in MODES:
+        lod = lr.select_lods(s["pos"], s["scale"], s["mesh_id"], s["meshes"], s["cam_pos"], mode, lc.SWITCH)
+        assert lod.tolist() == [cases[i][3] if i in cases else 0 for i in range(s["n"])], mode
+    k = {i: c[2] >> 16 for i, c in cases.items()}
+    flip = lambda v: 0x7F80 - v
+    # one bucket, keys that differ only in the lowest digit ...
+    assert cases[3][3] == cases[40][3] == 1 and k[3] >> 8 == k[40] >> 8 and k[3] & 255 != k[40] & 255
+    assert flip(k[3]) >> 8 == flip(k[40]) >> 8 and flip(k[3]) & 255 != flip(k[40]) & 255
+    # ... and a member of the other bucket with the lowest digit of one of them, near first and far first
+    assert cases[7][3] == 0 and k[7] & 255 == k[40] & 255 and flip(k[7]) & 255 == flip(k[40]) & 255
+    assert sorted(oc.DIGIT_NEAR_FIRST) == sorted(oc.DIGIT_FAR_FIRST) == list(range(64))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("order", ORDERS)
+def test_hand_written_slot_orders_of_the_digit_scene(mode, order):
+    s = oc.digit_scene()
+    got = orr.batch_draws_ordered(s["pos"], s["scale"], s["mesh_id"], s["meshes"], s["cam_pos"], lc.all_bits(s["n"]), mode, lc.SWITCH, order,
+                                  first_instance_base=5)
+    want = oc.want_digit_slots(order == orr.NEAR_FIRST)
+    assert got["members"] == 64 and got["count"] == 2
+    assert got["order"].tolist() == want.tolist()
+    assert got["ids"].tolist() == (want + 5).tolist()
+    assert got["cmds"]["instanceCount"].tolist() == list(oc.DIGIT_COUNTS) and got["cmds"]["firstInstance"].tolist() == [0, 62]

@@ -7,21 +7,26 @@ BATCH back-to-back repetitions, median of samples, one JSON line per leg.
   (c) (a)  +  mip_batch_draws with ids only
   (s) mip_batch_draws alone, ids only / with batch_model (over the bitmap of (a))
   (copy) a device-to-device copy of 256 MB: the measured ceiling the fractions refer to
+  (m) mip_batch_draws alone over a table of 300 meshes at 100 k instances: 600 buckets, the several-pass path (a (key,
+      instance) list, the per-bucket histogram, the matrices through slot_of), ids only / with batch_model
 
   python tools/batch_bench.py [n ...] [--samples 40] [--out profiles/batch_draws_bench.jsonl]
 
 --lods: the LOD-chain stage (mip_batch_draws_lods) alone, over the bitmap of (a), beside mip_batch_draws on the same scene:
 the pin policy (the same buckets and outputs as mip_batch_draws), a DISTANCE and a RELATIVE policy that use every level, each
-with ids only and with batch_model. --parent-library PATH adds mip_batch_draws of another build of the library (the parent
-commit's), measured by a child process of this tool in the same session: the yardstick.
+with ids only and with batch_model.
 
-  python tools/batch_bench.py --lods [--parent-library lib.so] [--out profiles/batch_draws_lods_bench.jsonl]
+  python tools/batch_bench.py --lods [--out profiles/batch_draws_lods_bench.jsonl]
 
 --ordered: the depth-ordered stage (mip_batch_draws_ordered, NEAR_FIRST and FAR_FIRST) beside mip_batch_draws_lods of the same
-build under the two example policies, each with ids only and with batch_model. --parent-library PATH adds mip_batch_draws_lods
-of another build (the parent commit's), measured by a child process in the same session.
+build under the two example policies, each with ids only and with batch_model.
 
-  python tools/batch_bench.py --ordered [--parent-library lib.so] [--out profiles/batch_draws_ordered_bench.jsonl]"""
+  python tools/batch_bench.py --ordered [--out profiles/batch_draws_ordered_bench.jsonl]
+
+--parent-library PATH (any of the three): the SAME legs on another build of the library (the parent commit's) as the yardstick,
+in the same session. A library is loaded once per process, so the tool then only starts children of itself, one after the
+other: the parent build, this build, the parent build again. Every row says which (`library`); the two parent runs give each
+leg's noise band: the larger of the difference of its two parent medians and its parent p90 - median."""
 import argparse
 import json
 import os
@@ -54,7 +59,7 @@ def measure(st, fn, batch=20, samples=40, warm=3):
     return dict(median_us=round(float(np.median(us)), 3), min_us=round(float(us.min()), 3), p90_us=round(float(np.percentile(us, 90)), 3))
 
 
-def bench(n, emit, samples=40):
+def bench(n, emit, samples=40, library="this build"):
     import numpy as np
     import torch
 
@@ -105,7 +110,7 @@ def bench(n, emit, samples=40):
         p.wait()
         copy = measure(st, lambda: dst.copy_(src), batch=5, samples=20)
         copy_tbs = 2 * src.numel() * 4 / 1e6 / copy["median_us"]
-        emit(dict(leg="copy", bytes=2 * src.numel() * 4, tb_per_s=round(copy_tbs, 3), **copy))
+        emit(dict(leg="copy", library=library, bytes=2 * src.numel() * 4, tb_per_s=round(copy_tbs, 3), **copy))
         legs = [("a: mip_run, every output", leg_a, None), ("b: mip_run without model + batch_draws with batch_model", leg_b, None),
                 ("c: mip_run, every output + batch_draws ids only", leg_c, None),
                 ("s: batch_draws ids only, alone", lambda: p.batch_draws(frame, bitmap.data_ptr(), **ids_only), False),
@@ -114,7 +119,7 @@ def bench(n, emit, samples=40):
             r = measure(st, fn, samples=samples)
             p.wait()
             draws, batches, members = int(scal[0].item()), int(b_scal[0].item()), int(b_scal[1].item())
-            row = dict(leg=name, n=n, config=config, meshes=m, draw_count=draws, batch_count=batches, members=members, **r)
+            row = dict(leg=name, library=library, n=n, config=config, meshes=m, draw_count=draws, batch_count=batches, members=members, **r)
             if stage_model is not None:  # the stage's algorithmic bytes (one pass): bitmap + mesh_id + pos read, ids written; rot + scale read, matrices written
                 v = members / n
                 per_instance = 0.125 + 16 + 4 * v + ((20 + 64 * v) if stage_model else 0)
@@ -125,12 +130,61 @@ def bench(n, emit, samples=40):
         p.close()
 
 
+def bench_several(emit, samples=40, library="this build", n=100_000, m=300):
+    """Leg (m): a table of m > 128 meshes, built as tests/test_gpu_batch.py builds its many-mesh scenes."""
+    import numpy as np
+    import torch
+
+    import renderer_amd
+    from renderer_amd import scene
+    from renderer_amd.pipeline import MESH_DTYPE, make_frame
+
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.Stream()
+    rng = np.random.default_rng(m)
+    s = scene.make_scene(3, n=n, all_visible=True)
+    meshes = np.zeros(m, MESH_DTYPE)
+    meshes["aabb_min"], meshes["aabb_max"] = -0.5, 0.5
+    meshes["n_lods"] = rng.integers(1, 4, m)
+    meshes["index_len"] = rng.integers(0, 3000, (m, 6)) // 3 * 3
+    meshes["index_len"][rng.random((m, 6)) < 0.1] = 0
+    meshes["index_offset"] = rng.integers(0, 2 ** 31, (m, 6))
+    meshes["vertex_offset"] = rng.integers(-1000, 2 ** 30, m)
+    mesh_id = rng.integers(0, m, n).astype(np.uint32)
+    mesh_id[rng.integers(0, n, n // 8)] = m - 1   # the last bucket is used
+    with torch.cuda.stream(st):
+        p = renderer_amd.InstancePipeline(n, m, stream=st.cuda_stream)
+        p.set_mesh_table(meshes)
+        p.set_instances(s["pos"], s["rot"], s["scale"], mesh_id)
+        bitmap = torch.zeros((n + 31) // 32 + 1, dtype=torch.int32, device=dev)
+        cmds = torch.empty((n, 5), dtype=torch.int32, device=dev)
+        scal = torch.zeros(8, dtype=torch.int32, device=dev)
+        b_cmds = torch.empty((2 * m, 5), dtype=torch.int32, device=dev)
+        b_ids = torch.empty(n, dtype=torch.int32, device=dev)
+        b_scal = torch.zeros(8, dtype=torch.int32, device=dev)
+        b_model = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        frame = p.frame_ref(make_frame(s["planes"], s["cam_pos"]))
+        p.run_prepared(frame, p.prepare_outputs(visible_bitmap=bitmap.data_ptr(), draw_cmds=cmds.data_ptr(), draw_count=scal.data_ptr(),
+                                                draw_index_total=scal.data_ptr() + 4))
+        p.wait()
+        ids_only = dict(batch_cmds=b_cmds.data_ptr(), batch_count=b_scal.data_ptr(), instance_ids=b_ids.data_ptr(),
+                        instance_count=b_scal.data_ptr() + 4, async_=True)
+        with_model = dict(ids_only, batch_model=b_model.data_ptr())
+        for outs, what in ((ids_only, "ids only"), (with_model, "with batch_model")):
+            r = measure(st, lambda: p.batch_draws(frame, bitmap.data_ptr(), **outs), samples=samples)
+            p.wait()
+            emit(dict(leg=f"m: batch_draws {what}, {m} meshes (several passes)", library=library, n=n, config=3, meshes=m, buckets=2 * m,
+                      batch_count=int(b_scal[0].item()), members=int(b_scal[1].item()), **r))
+        p.close()
+
+
 # example policies of the --lods leg (squared metrics): every level of a six-level chain is used in configs 2 and 3
 LODS_DISTANCE_SQ = (100.0, 400.0, 1600.0, 3600.0, 6400.0)   # switches at 10, 20, 40, 60, 80 units
 LODS_RELATIVE_SQ = (9.0, 36.0, 144.0, 400.0, 900.0)         # switches at 3, 6, 12, 20, 30 box diagonals
 
 
-def bench_lods(n, emit, samples=40, only_batch_draws=False, library="this build"):
+def bench_lods(n, emit, samples=40, library="this build"):
     import torch
 
     import renderer_amd
@@ -162,13 +216,11 @@ def bench_lods(n, emit, samples=40, only_batch_draws=False, library="this build"
         ids_only = dict(batch_cmds=b_cmds.data_ptr(), batch_count=b_scal.data_ptr(), instance_ids=b_ids.data_ptr(),
                         instance_count=b_scal.data_ptr() + 4, async_=True)
         with_model = dict(ids_only, batch_model=b_model.data_ptr())
-        legs = [("batch_draws", None)]
-        if not only_batch_draws:
-            from renderer_amd.pipeline import LOD_PIN_SWITCH_SQ, make_lod_policy
+        from renderer_amd.pipeline import LOD_PIN_SWITCH_SQ, make_lod_policy
 
-            legs += [("batch_draws_lods, pin policy", make_lod_policy("distance", LOD_PIN_SWITCH_SQ)),
-                     ("batch_draws_lods, DISTANCE", make_lod_policy("distance", LODS_DISTANCE_SQ)),
-                     ("batch_draws_lods, RELATIVE", make_lod_policy("relative", LODS_RELATIVE_SQ))]
+        legs = [("batch_draws", None), ("batch_draws_lods, pin policy", make_lod_policy("distance", LOD_PIN_SWITCH_SQ)),
+                ("batch_draws_lods, DISTANCE", make_lod_policy("distance", LODS_DISTANCE_SQ)),
+                ("batch_draws_lods, RELATIVE", make_lod_policy("relative", LODS_RELATIVE_SQ))]
         for name, policy in legs:
             for outs, what in ((ids_only, "ids only"), (with_model, "with batch_model")):
                 if policy is None:
@@ -182,7 +234,7 @@ def bench_lods(n, emit, samples=40, only_batch_draws=False, library="this build"
         p.close()
 
 
-def bench_ordered(n, emit, samples=40, only_lods=False, library="this build"):
+def bench_ordered(n, emit, samples=40, library="this build"):
     import torch
 
     import renderer_amd
@@ -214,9 +266,8 @@ def bench_ordered(n, emit, samples=40, only_lods=False, library="this build"):
         ids_only = dict(batch_cmds=b_cmds.data_ptr(), batch_count=b_scal.data_ptr(), instance_ids=b_ids.data_ptr(),
                         instance_count=b_scal.data_ptr() + 4, async_=True)
         with_model = dict(ids_only, batch_model=b_model.data_ptr())
-        orders = [("batch_draws_lods", None)]
-        if not only_lods:
-            orders += [("batch_draws_ordered NEAR_FIRST", _lib.MIP_BATCH_ORDER_NEAR_FIRST), ("batch_draws_ordered FAR_FIRST", _lib.MIP_BATCH_ORDER_FAR_FIRST)]
+        orders = [("batch_draws_lods", None), ("batch_draws_ordered NEAR_FIRST", _lib.MIP_BATCH_ORDER_NEAR_FIRST),
+                  ("batch_draws_ordered FAR_FIRST", _lib.MIP_BATCH_ORDER_FAR_FIRST)]
         for pname, policy in (("DISTANCE", make_lod_policy("distance", LODS_DISTANCE_SQ)), ("RELATIVE", make_lod_policy("relative", LODS_RELATIVE_SQ))):
             for name, order in orders:
                 for outs, what in ((ids_only, "ids only"), (with_model, "with batch_model")):
@@ -238,9 +289,8 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     ap.add_argument("--lods", action="store_true", help="the mip_batch_draws_lods legs instead of (a) .. (s)")
     ap.add_argument("--ordered", action="store_true", help="the mip_batch_draws_ordered legs instead of (a) .. (s)")
-    ap.add_argument("--parent-library", default=None,
-                    help="--lods / --ordered: also measure mip_batch_draws / mip_batch_draws_lods of this build of the library (a child process)")
-    ap.add_argument("--only-batch-draws", default=None, help=argparse.SUPPRESS)  # the child's leg: the label of its library
+    ap.add_argument("--parent-library", default=None, help="also run the same legs on this build of the library: the yardstick (child processes)")
+    ap.add_argument("--library-label", default="this build", help=argparse.SUPPRESS)  # a child's rows: which library it loaded
     a = ap.parse_args()
 
     def emit(row):
@@ -250,19 +300,24 @@ def main():
             with open(a.out, "a") as f:
                 f.write(line + "\n")
 
-    if (a.lods or a.ordered) and a.parent_library:  # fresh processes, before this one opens the GPU: a library is loaded once per process (MIP_LIBRARY, renderer_amd/_lib.py)
+    if a.parent_library:  # a library is loaded once per process (MIP_LIBRARY, renderer_amd/_lib.py): this process starts children and never opens the GPU
         import subprocess
 
-        for n in a.n:
-            cmd = [sys.executable, os.path.abspath(__file__), str(n), "--ordered" if a.ordered else "--lods", "--samples", str(a.samples), "--only-batch-draws", "parent commit"]
-            subprocess.run(cmd + (["--out", a.out] if a.out else []), check=True, env=dict(os.environ, MIP_LIBRARY=os.path.abspath(a.parent_library)))
+        cmd = [sys.executable, os.path.abspath(__file__)] + [str(n) for n in a.n] + ["--samples", str(a.samples)]
+        cmd += (["--lods"] if a.lods else []) + (["--ordered"] if a.ordered else []) + (["--out", a.out] if a.out else [])
+        parent = dict(os.environ, MIP_LIBRARY=os.path.abspath(a.parent_library))
+        for label, env in (("parent commit, first run", parent), ("this build", os.environ), ("parent commit, last run", parent)):
+            subprocess.run(cmd + ["--library-label", label], check=True, env=env)
+        return
     for n in a.n:
         if a.ordered:
-            bench_ordered(n, emit, a.samples, only_lods=a.only_batch_draws is not None, library=a.only_batch_draws or "this build")
+            bench_ordered(n, emit, a.samples, library=a.library_label)
         elif a.lods:
-            bench_lods(n, emit, a.samples, only_batch_draws=a.only_batch_draws is not None, library=a.only_batch_draws or "this build")
+            bench_lods(n, emit, a.samples, library=a.library_label)
         else:
-            bench(n, emit, a.samples)
+            bench(n, emit, a.samples, library=a.library_label)
+    if not (a.ordered or a.lods):
+        bench_several(emit, a.samples, library=a.library_label)
 
 
 if __name__ == "__main__":
