@@ -579,6 +579,59 @@ int32_t mip_batch_draws_lods(MipContext* ctx, const MipFrame* frame, const uint3
 int32_t mip_batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap,
                                 const MipLodPolicy* policy, uint32_t order, const MipBatchOutputs* out);
 
+/* ---- Extension: batched draws for several views in one call -----------------------------------------------------------
+ * mip_batch_draws_lods for n_views views of the resident instances — the lights of a shadow pass, cascades, cube faces,
+ * stereo — in ONE call that reads the instance columns once. NOT a reference behaviour (farnoy/renderer walks every mesh
+ * entity once per light, shadow_mapping.rs:405-478); checked against this repository's restatement
+ * (tests/views_batch_restatement.py), byte for byte. Every output is integer, so every byte is determined.
+ *
+ * VIEWS: 1 <= n_views <= MIP_MAX_VIEWS. View v is frames[v] with visible_bitmaps[v]: `visible_bitmaps` is a HOST array of
+ * n_views DEVICE pointers, each a bitmap in the layout mip_batch_draws documents; a NULL entry means every resident instance
+ * (the unculled shadow pass). Two views may share a bitmap pointer. cam_pos and first_instance_base are per view; the policy
+ * is shared; planes, first_index_base and pv are not read.
+ * MEMBERS, LOD, BUCKET, per view: exactly those of mip_batch_draws_lods(ctx, &frames[v], visible_bitmaps[v], policy, ...):
+ * bucket = lod_base[mesh_id] + lod, B = sum of n_lods buckets.
+ * SLOTS: all members of all views sorted by (view, bucket, draw index) into ONE instance_ids array (room for n_views x N
+ * words). view_first_slot[v] (optional, n_views + 1 words) = the number of members of the views before v, and
+ * view_first_slot[n_views] = all members. instance_ids[s] = frames[v].first_instance_base + i for the member of view v in
+ * slot s. Nothing at or behind the total member count is touched.
+ * COMMANDS: view v's commands are entries [v * cmd_stride, v * cmd_stride + batch_counts[v]) of batch_cmds: one per NON-EMPTY
+ * bucket of that view, in ascending bucket order, with mip_batch_draws_lods' fields except firstInstance, which is the
+ * ABSOLUTE slot in the shared instance_ids (that call's value + view_first_slot[v]). A view without members gets
+ * batch_counts[v] = 0. Every entry of a view's range at or behind its count is left untouched. cmd_stride >= min(B, N).
+ * A consumer issues vkCmdDrawIndexedIndirectCount(batch_cmds, v * cmd_stride * 20, batch_counts, v * 4, cmd_stride, 20) per
+ * view and reads entity_id = instance_ids[gl_InstanceIndex], or model[instance_ids[s] - base] from a frame's `model` output.
+ * N = 0 is legal: n_views zero counts and, if asked for, n_views + 1 zero slots.
+ *
+ * ORDERING: enqueued on the context's first stream, where mip_run_views runs, so bitmaps written by a preceding
+ * mip_run_views need no wait in between. Bitmaps from anywhere else — a mip_run of another frame slot, the caller's own
+ * kernels — need mip_wait or the caller's ordering first, as documented for mip_batch_draws. Without MIP_OUT_ASYNC the call
+ * returns when the outputs are complete. Scratch is the call's own, allocated at first use for the n_views x N asked for
+ * (and grown by a later, larger call); it is not the per-slot scratch of mip_batch_draws / _lods / _ordered, so calls of
+ * those behind any frame slot and this call do not disturb each other.
+ * COST: n_views x B <= 256 sorts in one pass (four launches, whatever n_views); more takes several passes and, at instance
+ * counts in the millions, currently longer than one mip_batch_draws_lods call per view (DESIGN.md section 22 has the figures).
+ * ERRORS, MIP_ERR_INVALID_ARGUMENT: NULL ctx / frames / visible_bitmaps / policy / out / batch_cmds / batch_counts /
+ * instance_ids; a wrong struct_size (MipViewBatchOutputs, MipLodPolicy); reserved != 0; unknown flags; a missing
+ * MIP_OUT_DEVICE; n_views out of range; cmd_stride < min(B, N); a policy mip_batch_draws_lods refuses.
+ * MIP_ERR_NOT_READY as mip_batch_draws. MIP_ERR_CAPACITY: n_views x N >= 2^32, or n_views x B > 2^31 (view * B + bucket is a
+ * 32-bit key). A refused call writes nothing.
+ * OUT OF SCOPE: batch_model (read the frame's `model` through instance_ids); the orders of mip_batch_draws_ordered; shards;
+ * mip_run_many / recorded launch graphs; the per-triangle stage; the wire forms. */
+typedef struct MipViewBatchOutputs {
+  uint32_t struct_size;      /* = sizeof(MipViewBatchOutputs) */
+  uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
+  void* batch_cmds;          /* DEVICE: n_views x cmd_stride MipDrawIndexedIndirectCommand */
+  uint32_t cmd_stride;       /* commands reserved per view; >= min(B, N) */
+  uint32_t reserved;         /* 0 */
+  uint32_t* batch_counts;    /* DEVICE: n_views words: commands written for view v */
+  uint32_t* instance_ids;    /* DEVICE: room for n_views x N words, shared by all views */
+  uint32_t* view_first_slot; /* DEVICE, optional: n_views + 1 words: first slot of view v; [n_views] = all members */
+} MipViewBatchOutputs;       /* 48 B */
+
+int32_t mip_batch_draws_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps,
+                              uint32_t n_views, const MipLodPolicy* policy, const MipViewBatchOutputs* out);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every

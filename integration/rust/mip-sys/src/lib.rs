@@ -125,6 +125,19 @@ pub const MIP_BATCH_ORDER_DRAW_INDEX: u32 = 0;
 pub const MIP_BATCH_ORDER_NEAR_FIRST: u32 = 1;
 pub const MIP_BATCH_ORDER_FAR_FIRST: u32 = 2;
 
+/// Outputs of mip_batch_draws_views: every view's commands in its own range of `batch_cmds`, one shared `instance_ids`.
+#[repr(C)]
+pub struct MipViewBatchOutputs {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub batch_cmds: *mut c_void,
+    pub cmd_stride: u32,
+    pub reserved: u32,
+    pub batch_counts: *mut u32,
+    pub instance_ids: *mut u32,
+    pub view_first_slot: *mut u32,
+}
+
 extern "C" {
     pub fn mip_abi_version() -> u32;
     pub fn mip_create(cfg: *const MipConfig, out: *mut *mut MipContext) -> i32;
@@ -184,6 +197,10 @@ extern "C" {
     /// Extension: mip_batch_draws_lods with the members of every bucket nearest first or farthest first (MIP_BATCH_ORDER_*).
     pub fn mip_batch_draws_ordered(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32,
                                    policy: *const MipLodPolicy, order: u32, out: *const MipBatchOutputs) -> i32;
+    /// Extension: mip_batch_draws_lods for up to MIP_MAX_VIEWS views in one call; `visible_bitmaps` is a host array of
+    /// `n_views` device pointers (null: every resident instance).
+    pub fn mip_batch_draws_views(ctx: *mut MipContext, frames: *const MipFrame, visible_bitmaps: *const *const u32,
+                                 n_views: u32, policy: *const MipLodPolicy, out: *const MipViewBatchOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -197,6 +214,7 @@ const _: () = assert!(std::mem::size_of::<MipDrawIndexedIndirectCommand>() == 20
 // the extension structs, as array lengths (a mismatch is a type error)
 const _: [u8; 48] = [0; std::mem::size_of::<MipBatchOutputs>()];
 const _: [u8; 28] = [0; std::mem::size_of::<MipLodPolicy>()];
+const _: [u8; 48] = [0; std::mem::size_of::<MipViewBatchOutputs>()];
 
 impl Pipeline {
     /// `panic = "abort"` (Cargo.toml:133,138) makes a panic here as final as in the rest of the renderer.

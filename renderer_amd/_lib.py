@@ -49,7 +49,7 @@ MIP_BATCH_ORDER_FAR_FIRST = 2
 EXPORTS = (
     "mip_abi_version", "mip_create", "mip_destroy", "mip_set_mesh_table", "mip_set_instances",
     "mip_set_instances_device", "mip_update_instances", "mip_set_geometry", "mip_set_blas_addresses", "mip_run", "mip_run_many", "mip_wait", "mip_merge_draw_lists", "mip_merge_wire_lists", "mip_merge_wire_lists_packed", "mip_wire_index_bits", "mip_light_draw_lists", "mip_set_skeleton", "mip_set_poses", "mip_run_skinned", "mip_run_views", "mip_comm_unique_id", "mip_comm_init", "mip_comm_destroy", "mip_run_sharded", "mip_import_external_fd", "mip_release_external", "mip_import_external_semaphore_fd", "mip_external_semaphore_on_device", "mip_wait_external", "mip_signal_external", "mip_release_external_semaphore", "mip_last_error",
-    "mip_get_timings", "mip_depth_pyramid_bytes", "mip_build_depth_pyramid", "mip_run_occluded", "mip_batch_draws", "mip_batch_draws_lods", "mip_batch_draws_ordered", "mip_reset_timings", "mip_instance_count",
+    "mip_get_timings", "mip_depth_pyramid_bytes", "mip_build_depth_pyramid", "mip_run_occluded", "mip_batch_draws", "mip_batch_draws_lods", "mip_batch_draws_ordered", "mip_batch_draws_views", "mip_reset_timings", "mip_instance_count",
 )
 
 
@@ -133,6 +133,20 @@ class MipBatchOutputs(C.Structure):
         ("instance_ids", C.c_void_p),
         ("instance_count", C.c_void_p),
         ("batch_model", C.c_void_p),
+    ]
+
+
+class MipViewBatchOutputs(C.Structure):
+    """mip_batch_draws_views' outputs (include/mi_instance_pipeline.h): device pointers and the per-view command stride, 48 B."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("batch_cmds", C.c_void_p),
+        ("cmd_stride", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("batch_counts", C.c_void_p),
+        ("instance_ids", C.c_void_p),
+        ("view_first_slot", C.c_void_p),
     ]
 
 
@@ -270,6 +284,7 @@ def load_library():
     _declare_newer(lib, "mip_batch_draws", [vp, vp, vp, vp])
     _declare_newer(lib, "mip_batch_draws_lods", [vp, vp, vp, vp, vp])
     _declare_newer(lib, "mip_batch_draws_ordered", [vp, vp, vp, vp, C.c_uint32, vp])
+    _declare_newer(lib, "mip_batch_draws_views", [vp, vp, vp, C.c_uint32, vp, vp])
     lib.mip_instance_count.argtypes = [vp]
     lib.mip_instance_count.restype = C.c_uint32
     _lib = lib

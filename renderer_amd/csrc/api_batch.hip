@@ -3,10 +3,13 @@
 // bucket, the entity ids in slot order and, optionally, the members' model matrices in slot order.
 // mip_batch_draws_lods does the same over the whole LOD chain, bucket = lod_base[mesh] + lod, with the caller's thresholds.
 // mip_batch_draws_ordered is mip_batch_draws_lods with the members of a bucket nearest first or farthest first.
-// One stage (batch_kernel.hpp) under the key policies of the three entry points (batch_kernel.hpp, batch_lods_kernel.hpp);
-// batch_plan.hpp says which instantiation a call launches. The kernels are instantiated here and only here.
+// mip_batch_draws_views is mip_batch_draws_lods for several views in one call: key = view * B + bucket, one shared instance_ids.
+// One stage (batch_kernel.hpp) under the key policies of the four entry points (batch_kernel.hpp, batch_lods_kernel.hpp,
+// batch_views_kernel.hpp); batch_plan.hpp says which instantiation a call launches. The kernels are instantiated here and only here.
 #include "context.hpp"
-#include "batch_lods_kernel.hpp"
+#include "batch_views_kernel.hpp"
+
+static_assert(sizeof(MipViewBatchOutputs) == 48, "MipViewBatchOutputs is part of the ABI");
 
 namespace mip_host {
 namespace {
@@ -40,6 +43,8 @@ const void* kernel_address(mip::BatchKernel k) {
   using ChainR = BatchLodChainKey<MIP_LOD_RELATIVE>;
   using OrderedD = BatchOrderedKey<MIP_LOD_DISTANCE>;
   using OrderedR = BatchOrderedKey<MIP_LOD_RELATIVE>;
+  using ViewsD = BatchViewsKey<MIP_LOD_DISTANCE>;
+  using ViewsR = BatchViewsKey<MIP_LOD_RELATIVE>;
   switch (k) {
     case K::none: break;
     case K::count_pick: return (const void*)mip_batch_count_kernel<BatchPickLodKey>;
@@ -73,15 +78,69 @@ const void* kernel_address(mip::BatchKernel k) {
     case K::rowscan: return (const void*)mip_batch_rowscan_kernel;
     case K::commands_pair: return (const void*)mip_batch_commands_kernel<BatchPairDraw>;
     case K::commands_chain: return (const void*)mip_batch_commands_kernel<BatchChainDraw>;
+    case K::count_views_distance: return (const void*)mip_batch_count_kernel<ViewsD>;
+    case K::count_views_relative: return (const void*)mip_batch_count_kernel<ViewsR>;
+    case K::scatter_views_distance_mid: return (const void*)mip_batch_scatter_kernel<ViewsD, false, 0>;
+    case K::scatter_views_distance_last: return (const void*)mip_batch_scatter_kernel<ViewsD, true, 0>;
+    case K::scatter_views_relative_mid: return (const void*)mip_batch_scatter_kernel<ViewsR, false, 0>;
+    case K::scatter_views_relative_last: return (const void*)mip_batch_scatter_kernel<ViewsR, true, 0>;
+    case K::scatter_views_list_last: return (const void*)mip_batch_scatter_kernel<BatchViewsListKey, true, 0>;
+    case K::commands_views: return (const void*)mip_batch_view_commands_kernel;
   }
   return nullptr;
 }
 
-// `a` is the most derived argument block; every kernel takes its own leading part of it (BatchArgs, LodBatchArgs or all of it)
-int32_t launch(MipContext* ctx, mip::BatchKernel kernel, uint32_t blocks, hipStream_t stream, mip::OrderedBatchArgs& a) {
+// `a` is the most derived argument block (OrderedBatchArgs, or ViewBatchArgs for mip_batch_draws_views); every kernel takes
+// its own leading part of it (BatchArgs, LodBatchArgs or all of it)
+int32_t launch(MipContext* ctx, mip::BatchKernel kernel, uint32_t blocks, hipStream_t stream, mip::LodBatchArgs& a) {
   void* params[] = {&a};
   MIP_HIP(ctx, hipLaunchKernel(kernel_address(kernel), dim3(blocks), dim3(mip::kTile), params, 0, stream));
   MIP_HIP(ctx, hipGetLastError());
+  return MIP_OK;
+}
+
+void release_view_scratch(MipContext::ViewBatchScratch& vs) {
+  (void)hipFree(vs.d_counts);
+  (void)hipFree(vs.d_totals);
+  for (int k = 0; k < 2; ++k) {
+    (void)hipFree(vs.d_keys[k]);
+    (void)hipFree(vs.d_ids[k]);
+  }
+  (void)hipFree(vs.d_bucket_hist);
+  vs = MipContext::ViewBatchScratch{};
+}
+
+// mip_batch_draws_views' own scratch, for the entries (n_views x N) and global buckets (n_views x B) of this call: kept while
+// it is large enough, replaced by a larger one otherwise (hipFree waits for the work that still reads the old one).
+int32_t ensure_view_scratch(MipContext* ctx, MipContext::ViewBatchScratch& vs, size_t entries, size_t buckets, bool several_passes) {
+  if (!vs.d_totals) MIP_HIP(ctx, hipMalloc(&vs.d_totals, (mip::kBatchMaxPasses * mip::kBatchBins + 1) * 4));
+  if (entries > vs.entries_cap) {
+    (void)hipFree(vs.d_counts);
+    vs.d_counts = nullptr;
+    vs.entries_cap = 0;
+    MIP_HIP(ctx, hipMalloc(&vs.d_counts, (size_t)mip::kBatchBins * batch_tiles_for((uint32_t)entries) * 4));
+    vs.entries_cap = entries;
+  }
+  if (several_passes && entries > vs.list_cap) {
+    for (int k = 0; k < 2; ++k) {
+      (void)hipFree(vs.d_keys[k]);
+      (void)hipFree(vs.d_ids[k]);
+      vs.d_keys[k] = vs.d_ids[k] = nullptr;
+    }
+    vs.list_cap = 0;
+    for (int k = 0; k < 2; ++k) {
+      MIP_HIP(ctx, hipMalloc(&vs.d_keys[k], entries * 4));
+      MIP_HIP(ctx, hipMalloc(&vs.d_ids[k], entries * 4));
+    }
+    vs.list_cap = entries;
+  }
+  if (several_passes && buckets > vs.hist_cap) {
+    (void)hipFree(vs.d_bucket_hist);
+    vs.d_bucket_hist = nullptr;
+    vs.hist_cap = 0;
+    MIP_HIP(ctx, hipMalloc(&vs.d_bucket_hist, buckets * 4));
+    vs.hist_cap = buckets;
+  }
   return MIP_OK;
 }
 
@@ -99,6 +158,7 @@ void batch_release(MipContext* ctx) {
     (void)hipFree(bs.d_slot_of);
   }
   ctx->batch.clear();
+  release_view_scratch(ctx->view_batch);
 }
 
 namespace {
@@ -219,6 +279,99 @@ int32_t check_policy(MipContext* ctx, const MipLodPolicy* policy) {
   return MIP_OK;
 }
 
+// mip_batch_draws_views: every check first (a refused call writes nothing), then one sort of the n_views x N (instance, view)
+// entries by key = view * B + bucket on the context's first stream, where mip_run_views runs.
+int32_t batch_draws_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps, uint32_t n_views,
+                          const MipLodPolicy* policy, const MipViewBatchOutputs* out) {
+  if (!frames || !visible_bitmaps || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frames/visible_bitmaps/out is NULL");
+  if (out->struct_size != sizeof(MipViewBatchOutputs))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipViewBatchOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipViewBatchOutputs));
+  if (out->reserved != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipViewBatchOutputs.reserved is %u, not 0", out->reserved);
+  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipViewBatchOutputs flags 0x%x", out->flags);
+  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_batch_draws_views needs MIP_OUT_DEVICE outputs");
+  if (!out->batch_cmds || !out->batch_counts || !out->instance_ids)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds/batch_counts/instance_ids is NULL");
+  if ((uintptr_t)out->batch_cmds % 4u != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds is not 4-byte aligned");
+  if (n_views == 0 || n_views > MIP_MAX_VIEWS) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "n_views %u outside 1..%u", n_views, (unsigned)MIP_MAX_VIEWS);
+  if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
+  const uint32_t n = ctx->n;
+  const unsigned long long view_buckets = ctx->lod_buckets, buckets = view_buckets * n_views;
+  if (out->cmd_stride < (view_buckets < n ? view_buckets : n))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cmd_stride %u < min(B = %llu, N = %u)", out->cmd_stride, view_buckets, n);
+  if (!mip::batch_views_entries_fit(n_views, n))
+    return fail(ctx, MIP_ERR_CAPACITY, "%u views x %u instances: the entries do not fit a 32-bit count", n_views, n);
+  if (buckets > 0x80000000ull || ctx->m > 0x20000000u)
+    return fail(ctx, MIP_ERR_CAPACITY, "%u views x %llu buckets: view * B + bucket does not fit a 32-bit key", n_views, view_buckets);
+  if (int32_t rc = bind_device(ctx)) return rc;
+  hipStream_t stream = ctx->stream;
+  const bool async = (out->flags & MIP_OUT_ASYNC) != 0;
+
+  if (n == 0 || view_buckets == 0) {  // nothing to bin: zeros
+    MIP_HIP(ctx, hipMemsetAsync(out->batch_counts, 0, (size_t)n_views * 4, stream));
+    if (out->view_first_slot) MIP_HIP(ctx, hipMemsetAsync(out->view_first_slot, 0, ((size_t)n_views + 1) * 4, stream));
+    return finish(ctx, stream, async);
+  }
+  const mip::BatchPlan plan = mip::plan_batch(mip::BatchEntry::views, policy->mode == MIP_LOD_RELATIVE, buckets, false, false);
+  const bool several = plan.several();
+  const uint32_t entries = n_views * n;
+  // several passes: copies of the bucket histogram, so that concurrent tiles add to different cache lines; at most 2^20 words
+  uint32_t hist_copies = several ? 64u : 1u;
+  while (hist_copies > 1u && hist_copies * buckets > (1ull << 20)) hist_copies >>= 1;
+  const size_t hist_words = (size_t)hist_copies * (size_t)buckets;
+  MipContext::ViewBatchScratch& vs = ctx->view_batch;
+  if (int32_t rc = ensure_view_scratch(ctx, vs, entries, hist_words, several)) return rc;
+
+  mip::ViewBatchArgs a{};
+  a.chain = ctx->d_mesh_chain;
+  a.bucket_lod = ctx->d_bucket_lod;
+  std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
+  a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
+  a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
+  a.n = n;
+  a.n_views = n_views;
+  a.view_buckets = (uint32_t)view_buckets;
+  a.n_entries = entries;
+  a.cmd_stride = out->cmd_stride;
+  a.hist_copies = hist_copies;
+  for (uint32_t v = 0; v < n_views; ++v) {
+    a.view_bitmap[v] = visible_bitmaps[v];
+    std::memcpy(a.view_cam[v], frames[v].cam_pos, sizeof a.view_cam[v]);
+    a.view_base[v] = frames[v].first_instance_base;
+  }
+  a.n_tiles = batch_tiles_for(entries);
+  a.n_buckets = (uint32_t)buckets;
+  a.n_bins = several ? mip::kBatchBins : (uint32_t)buckets;
+  a.counts = vs.d_counts;
+  a.members = a.members_out = vs.d_totals + mip::kBatchMaxPasses * mip::kBatchBins;
+  a.batch_cmds = static_cast<uint32_t*>(out->batch_cmds);
+  a.batch_counts = out->batch_counts;
+  a.view_first_slot = out->view_first_slot;
+#ifdef MIP_DEBUG_STAMPS
+  DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);
+#endif
+  if (several) MIP_HIP(ctx, hipMemsetAsync(vs.d_bucket_hist, 0, hist_words * 4, stream));
+
+  for (uint32_t p = 0; p < plan.passes; ++p) {
+    const bool last = p + 1 == plan.passes;
+    a.shift = p * mip::kBatchDigitBits;
+    a.totals = vs.d_totals + p * mip::kBatchBins;
+    a.bucket_hist = (several && p == 0) ? vs.d_bucket_hist : nullptr;
+    a.keys_in = p ? vs.d_keys[(p - 1) & 1u] : nullptr;
+    a.ids_in = p ? vs.d_ids[(p - 1) & 1u] : nullptr;
+    a.keys_out = last ? nullptr : vs.d_keys[p & 1u];
+    a.ids_out = last ? nullptr : vs.d_ids[p & 1u];
+    a.instance_ids = last ? out->instance_ids : nullptr;
+    if (int32_t rc = launch(ctx, plan.count(p), a.n_tiles, stream, a)) return rc;
+    if (int32_t rc = launch(ctx, mip::BatchKernel::rowscan, a.n_bins, stream, a)) return rc;
+    if (p == 0) {  // global bucket totals -> every view's commands, count and first slot (and the list's length for later passes)
+      a.bucket_totals = several ? vs.d_bucket_hist : a.totals;
+      if (int32_t rc = launch(ctx, plan.commands, 1, stream, a)) return rc;
+    }
+    if (int32_t rc = launch(ctx, plan.scatter(p), a.n_tiles, stream, a)) return rc;
+  }
+  return finish(ctx, stream, async);
+}
+
 }  // namespace
 }  // namespace mip_host
 
@@ -245,6 +398,13 @@ int32_t mip_batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const ui
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown order %u", order);
   if (int32_t rc = check_policy(ctx, policy)) return rc;
   return batch_draws(ctx, frame, visible_bitmap, policy, order, out);
+}
+
+int32_t mip_batch_draws_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps, uint32_t n_views,
+                              const MipLodPolicy* policy, const MipViewBatchOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  return batch_draws_views(ctx, frames, visible_bitmaps, n_views, policy, out);
 }
 
 }  // extern "C"

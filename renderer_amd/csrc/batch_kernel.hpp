@@ -32,7 +32,8 @@
 //   bucket_of(key)           the bucket a key belongs to
 //
 // BatchPickLodKey (mip_batch_draws) and BatchListKey (the later passes of any several-pass sort) are below; the policies over
-// the whole LOD chain (mip_batch_draws_lods, mip_batch_draws_ordered) are in batch_lods_kernel.hpp. The command writer takes a
+// the whole LOD chain (mip_batch_draws_lods, mip_batch_draws_ordered) are in batch_lods_kernel.hpp, the policy over several
+// views (mip_batch_draws_views) and its command writer in batch_views_kernel.hpp. The command writer takes a
 // policy of its own: how a bucket maps to (indexCount, firstIndex, vertexOffset). Instantiated in api_batch.hip only.
 #pragma once
 
@@ -126,6 +127,14 @@ __device__ __forceinline__ uint32_t batch_index(uint32_t tile, uint32_t wave, ui
   return tile * kBatchTile + wave * (kBatchRounds * 64u) + round * 64u + lane;
 }
 
+// What the last scatter adds to an instance to form its entity id. An argument block that holds several views overloads
+// this on its own type (batch_views_kernel.hpp): the base is then the one of the key's view.
+__device__ __forceinline__ uint32_t batch_first_instance(const BatchArgs& a, uint32_t /*key*/) { return a.first_instance_base; }
+
+// Where count adds a member of `bucket`: bucket_hist[bucket]. An argument block that keeps several copies of the histogram
+// (one per residue of the tile number, so that concurrent tiles add to different cache lines) overloads this on its own type.
+__device__ __forceinline__ uint32_t batch_hist_index(const BatchArgs&, uint32_t bucket, uint32_t /*tile*/) { return bucket; }
+
 enum class BatchBucketHist { never, when_given, always };
 
 // What the policies that form keys from the instance columns share: Key::key(a, il, active) sees an index in bounds (an idle
@@ -186,9 +195,9 @@ __global__ __launch_bounds__(kTile) void mip_batch_count_kernel(const typename K
     if (key != kBatchNone) {
       atomicAdd(&s_hist[(key >> a.shift) & (kBatchBins - 1u)], 1u);
       if constexpr (Key::kBucketHist == BatchBucketHist::always) {
-        atomicAdd(&a.bucket_hist[Key::bucket_of(key)], 1u);  // < n_buckets: the host sizes bucket_hist for the table
+        atomicAdd(&a.bucket_hist[batch_hist_index(a, Key::bucket_of(key), tile)], 1u);  // < n_buckets: the host sizes bucket_hist for the table
       } else if constexpr (Key::kBucketHist == BatchBucketHist::when_given) {
-        if (a.bucket_hist) atomicAdd(&a.bucket_hist[Key::bucket_of(key)], 1u);
+        if (a.bucket_hist) atomicAdd(&a.bucket_hist[batch_hist_index(a, Key::bucket_of(key), tile)], 1u);
       }
     }
   }
@@ -368,7 +377,7 @@ __global__ __launch_bounds__(kTile) void mip_batch_scatter_kernel(const typename
       slot = s_hist[wave][(key[r] >> a.shift) & (kBatchBins - 1u)] + rank[r];  // < members <= n
       const uint32_t id = Key::id(a, idx);
       if constexpr (kLast) {
-        a.instance_ids[slot] = a.first_instance_base + id;
+        a.instance_ids[slot] = batch_first_instance(a, key[r]) + id;
         if (a.slot_of) a.slot_of[id] = slot;
       } else {
         a.keys_out[slot] = key[r];

@@ -57,15 +57,17 @@ struct LodChainPick {
   float q;
 };
 
+// `word` is the bitmap word that holds instance il's bit, (cx, cy, cz) the reference point: the frame's own below, a view's in
+// batch_views_kernel.hpp.
 template <uint32_t kMode>
-__device__ __forceinline__ LodChainPick lod_chain_pick(const LodBatchArgs& a, uint32_t il, bool active) {
-  const uint32_t word = a.bitmap[il >> 5];
+__device__ __forceinline__ LodChainPick lod_chain_pick(const LodBatchArgs& a, uint32_t il, bool active, uint32_t word, float cx, float cy,
+                                                       float cz) {
   const float px = a.pos[3 * (size_t)il + 0], py = a.pos[3 * (size_t)il + 1], pz = a.pos[3 * (size_t)il + 2];
   const uint32_t mesh = a.mesh_id[il];
   const uint4* piece = reinterpret_cast<const uint4*>(a.chain + mesh);
   const uint4 c0 = piece[0], c1 = piece[1];
   const uint32_t n_lods = c0.x;
-  const float dx = a.cam[0] - px, dy = a.cam[1] - py, dz = a.cam[2] - pz;
+  const float dx = cx - px, dy = cy - py, dz = cz - pz;
   const float q = dx * dx + dy * dy + dz * dz;  // (dx*dx + dy*dy) + dz*dz: lod_is_far's expression
   float unit = 1.0f;
   if constexpr (kMode == kLodModeRelative) {
@@ -89,6 +91,11 @@ __device__ __forceinline__ LodChainPick lod_chain_pick(const LodBatchArgs& a, ui
   len = lod == 5u ? c1.w : len;
   const bool member = active && ((word >> (il & 31u)) & 1u) != 0u && len > 0u;
   return {c0.y + lod, member, q};
+}
+
+template <uint32_t kMode>
+__device__ __forceinline__ LodChainPick lod_chain_pick(const LodBatchArgs& a, uint32_t il, bool active) {
+  return lod_chain_pick<kMode>(a, il, active, a.bitmap[il >> 5], a.cam[0], a.cam[1], a.cam[2]);
 }
 
 // The bucket of instance il under the policy, or kBatchNone when it is not a member.

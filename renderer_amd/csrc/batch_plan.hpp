@@ -12,7 +12,8 @@ constexpr uint32_t kBatchMaxPasses = 4;
 constexpr uint32_t kBatchDepthBits = 16;  // D's field of the ordered key (batch_lods_kernel.hpp)
 static_assert(kBatchMaxPasses * kBatchDigitBits >= 32, "a 32-bit key takes at most kBatchMaxPasses digits");
 
-enum class BatchEntry : uint32_t { draws, lods, ordered };  // mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered (NEAR / FAR)
+// mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered (NEAR / FAR), mip_batch_draws_views
+enum class BatchEntry : uint32_t { draws, lods, ordered, views };
 
 // Every instantiation of the stage (batch_kernel.hpp), by key policy. scatter: `mid` = a pass of several, `last` = the one
 // pass, ids only, `model` / `general` = the one pass with matrices (census-selected / general arithmetic).
@@ -26,6 +27,11 @@ enum class BatchKernel : uint32_t {
   scatter_list_mid, scatter_list_last,
   model_pick, model_pick_general, model_chain_distance, model_chain_distance_general, model_chain_relative, model_chain_relative_general,
   rowscan, commands_pair, commands_chain,
+  // mip_batch_draws_views (batch_views_kernel.hpp): pass 0 over (instance, view) entries, the last list pass that adds the
+  // base of the key's view, the command writer that packs per view
+  count_views_distance, count_views_relative,
+  scatter_views_distance_mid, scatter_views_distance_last, scatter_views_relative_mid, scatter_views_relative_last,
+  scatter_views_list_last, commands_views,
 };
 
 struct BatchPlan {
@@ -34,9 +40,10 @@ struct BatchPlan {
   BatchKernel scatter0;
   BatchKernel commands;
   BatchKernel model;       // the matrices of a several-pass frame, through slot_of; none when scatter0 stores them or nobody asked
+  BatchKernel list_last;   // the last pass of several: scatter_list_last, or the one that knows the views' bases
   constexpr bool several() const { return passes > 1; }
   constexpr BatchKernel count(uint32_t p) const { return p ? BatchKernel::count_list : count0; }
-  constexpr BatchKernel scatter(uint32_t p) const { return !p ? scatter0 : p + 1 == passes ? BatchKernel::scatter_list_last : BatchKernel::scatter_list_mid; }
+  constexpr BatchKernel scatter(uint32_t p) const { return !p ? scatter0 : p + 1 == passes ? list_last : BatchKernel::scatter_list_mid; }
 };
 
 // ceil(log2(buckets)), at least 1: the bits of a bucket
@@ -46,7 +53,11 @@ constexpr uint32_t batch_key_bits(unsigned long long buckets) {
   return bits;
 }
 
-// `relative`: the policy's mode is MIP_LOD_RELATIVE (ignored by mip_batch_draws, which has no policy). buckets >= 1.
+// mip_batch_draws_views sorts n_views x N (instance, view) entries and keeps their number in a 32-bit word.
+constexpr bool batch_views_entries_fit(unsigned long long n_views, unsigned long long n) { return n_views * n < (1ull << 32); }
+
+// `relative`: the policy's mode is MIP_LOD_RELATIVE (ignored by mip_batch_draws, which has no policy). buckets >= 1; for
+// BatchEntry::views they are the GLOBAL buckets n_views x B (key = view * B + bucket), and no matrices are stored.
 constexpr BatchPlan plan_batch(BatchEntry entry, bool relative, unsigned long long buckets, bool want_model, bool general) {
   using K = BatchKernel;
   // rows: pick_lod, the chain under DISTANCE, under RELATIVE
@@ -62,6 +73,16 @@ constexpr BatchPlan plan_batch(BatchEntry entry, bool relative, unsigned long lo
   BatchPlan p{};
   p.passes = (bits + kBatchDigitBits - 1u) / kBatchDigitBits;
   p.commands = entry == BatchEntry::draws ? K::commands_pair : K::commands_chain;
+  p.list_last = K::scatter_list_last;
+  if (entry == BatchEntry::views) {
+    p.count0 = relative ? K::count_views_relative : K::count_views_distance;
+    p.scatter0 = p.several() ? (relative ? K::scatter_views_relative_mid : K::scatter_views_distance_mid)
+                             : (relative ? K::scatter_views_relative_last : K::scatter_views_distance_last);
+    p.commands = K::commands_views;
+    p.list_last = K::scatter_views_list_last;
+    p.model = K::none;
+    return p;
+  }
   if (ordered) {
     p.count0 = relative ? K::count_ordered_relative : K::count_ordered_distance;
     p.scatter0 = relative ? K::scatter_ordered_relative_mid : K::scatter_ordered_distance_mid;

@@ -5,8 +5,9 @@
 //   api_sharded.hip   shard merges, the collective-library seam, mip_run_sharded and its collective repair
 //   api_interop.hip   external memory and external semaphores (row f-2)
 //   api_occlusion.hip the occlusion-culling extension: depth pyramid builds, mip_run_occluded (occlusion_kernel.hpp)
-//   api_batch.hip     the batched-draws extension: mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered — one stage
-//                     (batch_kernel.hpp) under the key policies of batch_lods_kernel.hpp, planned by batch_plan.hpp
+//   api_batch.hip     the batched-draws extension: mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered,
+//                     mip_batch_draws_views — one stage (batch_kernel.hpp) under the key policies of batch_lods_kernel.hpp and
+//                     batch_views_kernel.hpp, planned by batch_plan.hpp
 // (round 3 had all of it in one 2 224-line mip_api.hip)
 #pragma once
 
@@ -101,6 +102,17 @@ struct MipContext {
     uint32_t* d_slot_of = nullptr;      //   slot of every member by instance (batch_model)
   };
   std::vector<BatchScratch> batch;
+  // mip_batch_draws_views (api_batch.hip): the call's own scratch on the first stream, allocated at first use for the
+  // n_views x N entries asked for and grown by a larger call; never a slot's BatchScratch
+  struct ViewBatchScratch {
+    uint32_t* d_counts = nullptr;       // [256 bins][tiles of entries]
+    uint32_t* d_totals = nullptr;       // kBatchMaxPasses x 256 digit totals + the member count
+    uint32_t* d_keys[2] = {nullptr, nullptr};  // more than 256 global buckets: the (key, instance) lists between passes
+    uint32_t* d_ids[2] = {nullptr, nullptr};
+    uint32_t* d_bucket_hist = nullptr;  //   members per global bucket, n_views x B words in every copy (hist_copies of them)
+    size_t entries_cap = 0, list_cap = 0, hist_cap = 0;  // entries d_counts / the lists hold, words of d_bucket_hist
+  };
+  ViewBatchScratch view_batch;
   std::vector<FrameSlot> view_states;  // mip_run_views: one prefix state per view, all on `stream`
   hipStream_t stream = nullptr;  // = slots[0].stream: uploads, merges, timing
   // resident inputs

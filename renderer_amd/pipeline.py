@@ -6,7 +6,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import MipBatchOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipTimings
+from ._lib import (MipBatchOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipTimings,
+                   MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
     [
@@ -512,6 +513,31 @@ class InstancePipeline:
         out.batch_model = batch_model or None
         self._check(self._lib.mip_batch_draws_ordered(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                       int(order), C.addressof(out)))
+
+    def batch_draws_views(self, frames, visible_bitmap_ptrs, policy, *, batch_cmds, cmd_stride, batch_counts, instance_ids,
+                          view_first_slot=0, async_=False):
+        """mip_batch_draws_views: batch_draws_lods for up to 16 views in one call. frames[v] (make_frame: cam_pos and
+        first_instance_base are read) goes with visible_bitmap_ptrs[v], a device bitmap or 0 / None for every resident
+        instance. View v's commands are entries [v * cmd_stride, v * cmd_stride + batch_counts[v]) of batch_cmds
+        (cmd_stride >= min(sum of n_lods, N)); all views share instance_ids (room for len(frames) x N words), firstInstance is
+        the absolute slot there, view_first_slot (len(frames) + 1 words, optional) the first slot of every view. Device
+        pointers; enqueued on the context's first stream, behind a run_views."""
+        k = len(frames)
+        if len(visible_bitmap_ptrs) != k:
+            raise ValueError("one bitmap pointer (or None) per frame")
+        fr = (MipFrame * max(k, 1))()
+        for v in range(k):
+            C.memmove(C.addressof(fr[v]), C.addressof(frames[v]), C.sizeof(MipFrame))
+        bm = (C.c_void_p * max(k, 1))(*[int(b) if b else None for b in visible_bitmap_ptrs])
+        out = MipViewBatchOutputs()
+        out.struct_size = C.sizeof(MipViewBatchOutputs)
+        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+        out.batch_cmds = batch_cmds or None
+        out.cmd_stride = int(cmd_stride)
+        out.batch_counts = batch_counts or None
+        out.instance_ids = instance_ids or None
+        out.view_first_slot = view_first_slot or None
+        self._check(self._lib.mip_batch_draws_views(self._ctx, C.addressof(fr), C.addressof(bm), k, C.addressof(policy), C.addressof(out)))
 
     # -- diagnostics --
     def timings(self):

@@ -23,7 +23,15 @@ build under the two example policies, each with ids only and with batch_model.
 
   python tools/batch_bench.py --ordered [--out profiles/batch_draws_ordered_bench.jsonl]
 
---parent-library PATH (any of the three): the SAME legs on another build of the library (the parent commit's) as the yardstick,
+--views: mip_batch_draws_views for V = 4 views in one call beside its yardsticks of the same session: four
+mip_batch_draws_lods calls (one per view, back to back, no wait in between: the bitmaps are at rest here, which favours the
+four calls — behind a mip_run_views the caller would have to wait first) and, for the unculled case, mip_light_draw_lists
+with four lights. Culled bitmaps come from one mip_run_views of the four frames; the unculled case passes NULL bitmaps
+(a bitmap of ones to mip_batch_draws_lods). A library without the entry point (the parent commit's) runs the yardsticks only.
+
+  python tools/batch_bench.py --views [--out profiles/batch_draws_views_bench.jsonl]
+
+--parent-library PATH (any of the four): the SAME legs on another build of the library (the parent commit's) as the yardstick,
 in the same session. A library is loaded once per process, so the tool then only starts children of itself, one after the
 other: the parent build, this build, the parent build again. Every row says which (`library`); the two parent runs give each
 leg's noise band: the larger of the difference of its two parent medians and its parent p90 - median."""
@@ -282,6 +290,100 @@ def bench_ordered(n, emit, samples=40, library="this build"):
         p.close()
 
 
+def view_frusta(planes, n_views):
+    """A frustum per view: the scene's own and the same one turned about the axes (columns swapped, signs flipped)."""
+    import numpy as np
+
+    base = np.asarray(planes, np.float32).reshape(6, 4)
+    turns = [(0, 1, 2, 1, 1), (2, 1, 0, 1, 1), (0, 1, 2, -1, 1), (2, 1, 0, -1, 1)]
+    out = []
+    for v in range(n_views):
+        a, b, c, sx, sz = turns[v % len(turns)]
+        t = base[:, [a, b, c, 3]].copy()
+        t[:, 0] *= sx
+        t[:, 2] *= sz
+        out.append(np.ascontiguousarray(t.reshape(-1)))
+    return out
+
+
+def bench_views(n, emit, samples=40, library="this build", n_views=4):
+    import numpy as np
+    import torch
+
+    import renderer_amd
+    from renderer_amd import scene
+    from renderer_amd.pipeline import make_frame, make_lod_policy
+
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.Stream()
+    config = 2 if n <= 100_000 else 3
+    s = scene.make_scene(config, n=n)
+    m = len(s["meshes"])
+    buckets = int(s["meshes"]["n_lods"].sum())
+    stride = min(buckets, n)
+    cam = np.asarray(s["cam_pos"], np.float32)
+    cams = [cam + np.asarray(d, np.float32) for d in ((0, 0, 0), (25, 0, 0), (0, 0, -25), (-20, 5, 20))][:n_views]
+    with torch.cuda.stream(st):
+        p = renderer_amd.InstancePipeline(n, m, stream=st.cuda_stream)
+        p.set_mesh_table(s["meshes"])
+        p.set_instances(s["pos"], s["rot"], s["scale"], s["mesh_id"])
+        words = (n + 31) // 32 + 1
+        bitmaps = torch.zeros((n_views, words), dtype=torch.int32, device=dev)
+        ones = torch.full((words,), -1, dtype=torch.int32, device=dev)
+        cmds = torch.empty((n_views, n, 5), dtype=torch.int32, device=dev)
+        scal = torch.zeros((n_views, 2), dtype=torch.int32, device=dev)
+        one_cmds = torch.empty((n_views, stride, 5), dtype=torch.int32, device=dev)      # four calls: a set of outputs per view
+        one_ids = torch.empty((n_views, n), dtype=torch.int32, device=dev)
+        one_scal = torch.zeros((n_views, 2), dtype=torch.int32, device=dev)
+        v_cmds = torch.empty((n_views * stride, 5), dtype=torch.int32, device=dev)        # one call
+        v_ids = torch.empty(n_views * n, dtype=torch.int32, device=dev)
+        v_counts = torch.zeros(n_views, dtype=torch.int32, device=dev)
+        v_slots = torch.zeros(n_views + 1, dtype=torch.int32, device=dev)
+        light_cmds = torch.empty((n_views * n, 5), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        frames = [make_frame(f, c, first_instance_base=v * n) for v, (f, c) in enumerate(zip(view_frusta(s["planes"], n_views), cams))]
+        p.run_views(frames, [p.prepare_outputs(visible_bitmap=bitmaps[v].data_ptr(), draw_cmds=cmds[v].data_ptr(), draw_count=scal[v].data_ptr(),
+                                               draw_index_total=scal[v].data_ptr() + 4) for v in range(n_views)])
+        p.wait()
+        listed = [int(x) for x in scal[:, 0].cpu()]      # per-instance commands per view: what mip_run_views hands a consumer today
+        policy = make_lod_policy("distance", LODS_DISTANCE_SQ)
+        one_out = [dict(batch_cmds=one_cmds[v].data_ptr(), batch_count=one_scal[v].data_ptr(), instance_ids=one_ids[v].data_ptr(),
+                        instance_count=one_scal[v].data_ptr() + 4, async_=True) for v in range(n_views)]
+        views_out = dict(batch_cmds=v_cmds.data_ptr(), cmd_stride=stride, batch_counts=v_counts.data_ptr(), instance_ids=v_ids.data_ptr(),
+                         view_first_slot=v_slots.data_ptr(), async_=True)
+        have_views = hasattr(p._lib, "mip_batch_draws_views")
+        lights = np.stack(cams)
+
+        def four_calls(ptrs):
+            def fn():
+                for v in range(n_views):
+                    p.batch_draws_lods(frames[v], ptrs[v], policy, **one_out[v])
+            return fn
+
+        culled_ptrs, ones_ptrs = [bitmaps[v].data_ptr() for v in range(n_views)], [ones.data_ptr()] * n_views
+        legs = [("culled", f"{n_views} x batch_draws_lods", four_calls(culled_ptrs), "four"),
+                ("unculled", f"{n_views} x batch_draws_lods", four_calls(ones_ptrs), "four"),
+                ("unculled", f"light_draw_lists, {n_views} lights", lambda: p.light_draw_lists(lights, light_cmds.data_ptr(), async_=True), "lights")]
+        if have_views:
+            legs += [("culled", "batch_draws_views", lambda: p.batch_draws_views(frames, culled_ptrs, policy, **views_out), "one"),
+                     ("unculled", "batch_draws_views", lambda: p.batch_draws_views(frames, [0] * n_views, policy, **views_out), "one")]
+        for case, name, fn, kind in legs:
+            r = measure(st, fn, samples=samples)
+            p.wait()
+            row = dict(leg=f"views: {name}, {case}", library=library, n=n, config=config, meshes=m, views=n_views, buckets=buckets, **r)
+            if kind == "four":
+                row.update(draws_per_view_before=listed if case == "culled" else [n] * n_views, draws_per_view_after=[int(x) for x in one_scal[:, 0].cpu()],
+                           members_per_view=[int(x) for x in one_scal[:, 1].cpu()])
+            elif kind == "one":
+                slots = [int(x) for x in v_slots.cpu()]
+                row.update(draws_per_view_before=listed if case == "culled" else [n] * n_views, draws_per_view_after=[int(x) for x in v_counts.cpu()],
+                           members_per_view=[b - a for a, b in zip(slots, slots[1:])])
+            else:
+                row.update(commands=n_views * n, command_bytes=n_views * n * 20)
+            emit(row)
+        p.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("n", nargs="*", type=int, default=[1_000_000, 100_000])
@@ -289,6 +391,7 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     ap.add_argument("--lods", action="store_true", help="the mip_batch_draws_lods legs instead of (a) .. (s)")
     ap.add_argument("--ordered", action="store_true", help="the mip_batch_draws_ordered legs instead of (a) .. (s)")
+    ap.add_argument("--views", action="store_true", help="the mip_batch_draws_views legs (V = 4) and their yardsticks instead of (a) .. (s)")
     ap.add_argument("--parent-library", default=None, help="also run the same legs on this build of the library: the yardstick (child processes)")
     ap.add_argument("--library-label", default="this build", help=argparse.SUPPRESS)  # a child's rows: which library it loaded
     a = ap.parse_args()
@@ -304,19 +407,21 @@ def main():
         import subprocess
 
         cmd = [sys.executable, os.path.abspath(__file__)] + [str(n) for n in a.n] + ["--samples", str(a.samples)]
-        cmd += (["--lods"] if a.lods else []) + (["--ordered"] if a.ordered else []) + (["--out", a.out] if a.out else [])
+        cmd += (["--lods"] if a.lods else []) + (["--ordered"] if a.ordered else []) + (["--views"] if a.views else []) + (["--out", a.out] if a.out else [])
         parent = dict(os.environ, MIP_LIBRARY=os.path.abspath(a.parent_library))
         for label, env in (("parent commit, first run", parent), ("this build", os.environ), ("parent commit, last run", parent)):
             subprocess.run(cmd + ["--library-label", label], check=True, env=env)
         return
     for n in a.n:
-        if a.ordered:
+        if a.views:
+            bench_views(n, emit, a.samples, library=a.library_label)
+        elif a.ordered:
             bench_ordered(n, emit, a.samples, library=a.library_label)
         elif a.lods:
             bench_lods(n, emit, a.samples, library=a.library_label)
         else:
             bench(n, emit, a.samples, library=a.library_label)
-    if not (a.ordered or a.lods):
+    if not (a.ordered or a.lods or a.views):
         bench_several(emit, a.samples, library=a.library_label)
 
 
