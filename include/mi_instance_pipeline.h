@@ -486,8 +486,9 @@ int32_t mip_run_occluded(MipContext* ctx, const MipFrame* frame, const MipOcclus
  * different frames in flight do not disturb each other; give each its own outputs.
  * ERRORS: NULL ctx / frame / bitmap / batch_cmds / batch_count / instance_ids, a wrong struct_size, a missing MIP_OUT_DEVICE,
  * unknown flags: MIP_ERR_INVALID_ARGUMENT; no instances or no mesh table: MIP_ERR_NOT_READY.
- * OUT OF SCOPE: per-triangle culling of batched draws (culled_index_buffer addresses a per-instance region), merging the
- * batches of several shards, mip_run_many / recorded launch graphs, the wire forms. */
+ * OUT OF SCOPE: per-triangle culling of batched draws (culled_index_buffer addresses a per-instance region), mip_run_many /
+ * recorded launch graphs, the wire forms. The batches of several shards are merged by mip_batch_draws_shard +
+ * mip_merge_batches (below), for mip_batch_draws_lods' buckets and draw order. */
 typedef struct MipBatchOutputs {
   uint32_t struct_size;      /* = sizeof(MipBatchOutputs) */
   uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
@@ -616,8 +617,8 @@ int32_t mip_batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const ui
  * MIP_OUT_DEVICE; n_views out of range; cmd_stride < min(B, N); a policy mip_batch_draws_lods refuses.
  * MIP_ERR_NOT_READY as mip_batch_draws. MIP_ERR_CAPACITY: n_views x N >= 2^32, or n_views x B > 2^31 (view * B + bucket is a
  * 32-bit key). A refused call writes nothing.
- * OUT OF SCOPE: batch_model (read the frame's `model` through instance_ids); the orders of mip_batch_draws_ordered; shards;
- * mip_run_many / recorded launch graphs; the per-triangle stage; the wire forms. */
+ * OUT OF SCOPE: batch_model (read the frame's `model` through instance_ids); the orders of mip_batch_draws_ordered; shards
+ * (mip_merge_batches merges one view's chunks); mip_run_many / recorded launch graphs; the per-triangle stage; the wire forms. */
 typedef struct MipViewBatchOutputs {
   uint32_t struct_size;      /* = sizeof(MipViewBatchOutputs) */
   uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
@@ -631,6 +632,71 @@ typedef struct MipViewBatchOutputs {
 
 int32_t mip_batch_draws_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps,
                               uint32_t n_views, const MipLodPolicy* policy, const MipViewBatchOutputs* out);
+
+/* ---- Extension: batched draws for sharded scenes — shard chunks and their merge ------------------------------------------
+ * mip_batch_draws_lods for a scene cut into contiguous draw-index shards (mip_run_sharded,
+ * renderer_amd/sharded.py): every rank bins its own shard into a CHUNK (mip_batch_draws_shard), one all-gather moves the
+ * chunks, and every rank merges them (mip_merge_batches) into, byte for byte, what ONE mip_batch_draws_lods call writes for
+ * the unsharded scene: buckets are mesh-major over a table every rank holds, ids are global (first_instance_base + i), and
+ * the shards are ranges in rank order, so (bucket, rank, slot) order is (bucket, draw index) order. NOT a reference
+ * behaviour; checked against this repository's restatement (tests/batch_merge_restatement.py). Only integers are
+ * involved, so every byte is determined.
+ *
+ * THE CHUNK, B = sum of n_lods over the mesh table:
+ *   MipBatchChunkHeader { members, n_buckets = B, reserved[2] = 0 }     16 B
+ *   uint32_t bucket_count[B]        dense, zeros included: batch_cmds is packed, so the bucket of a command cannot be recovered
+ *   uint32_t pad[(4 - B % 4) % 4]   zeros: the ids start 16-byte aligned relative to the chunk
+ *   uint32_t ids[capacity]          slots [0, members)
+ * The ids come last on purpose: a rank always writes its complete chunk into a full-size send buffer and the exchange
+ * sends a prefix of it; a tightened chunk that overflows is repaired by gathering again at full capacity. */
+typedef struct MipBatchChunkHeader {
+  uint32_t members;      /* ids the chunk holds */
+  uint32_t n_buckets;    /* B of the emitting rank's mesh table */
+  uint32_t reserved[2];  /* 0 */
+} MipBatchChunkHeader;   /* 16 B */
+#define MIP_MAX_BATCH_CHUNKS 64u
+/* byte offset of a chunk's ids, and bytes of a chunk with room for `capacity` ids, for a table of B buckets */
+#define MIP_BATCH_CHUNK_IDS_OFFSET(B) \
+  ((uint64_t)sizeof(MipBatchChunkHeader) + ((uint64_t)(B) + (4u - (uint64_t)(B) % 4u) % 4u) * 4u)
+#define MIP_BATCH_CHUNK_BYTES(B, capacity) (MIP_BATCH_CHUNK_IDS_OFFSET(B) + (uint64_t)(capacity) * 4u)
+
+/* PRODUCER. Members, LOD, bucket and slot order are exactly those of mip_batch_draws_lods for the same ctx, frame,
+ * visible_bitmap and policy: ids[0, members) are the bytes that call writes to instance_ids, bucket_count[b] is the number of
+ * members of bucket b for every b < B, the header is {members, B, 0, 0} and the pad words are written as 0. Ids at or behind
+ * `members` are not touched. `chunk` is a DEVICE pointer, 16-byte aligned, with room for MIP_BATCH_CHUNK_BYTES(B,
+ * ids_capacity); ids_capacity >= N resident instances, otherwise MIP_ERR_INVALID_ARGUMENT (cutting a chunk is the exchange's
+ * business). flags: MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC. N = 0 writes the header and B zeros. The stream (behind the
+ * frame issued last), the per-slot scratch, the policy checks, MIP_ERR_NOT_READY and MIP_ERR_CAPACITY are those of
+ * mip_batch_draws_lods. A refused call writes nothing. */
+int32_t mip_batch_draws_shard(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap,
+                              const MipLodPolicy* policy, void* chunk, uint32_t ids_capacity, uint32_t flags);
+
+/* CONSUMER. `chunks`: DEVICE memory, 16-byte aligned, holding n_chunks chunks chunk_stride_bytes apart (a multiple of 16,
+ * at least MIP_BATCH_CHUNK_BYTES(B, chunk_capacity); whatever an all-gather leaves behind a chunk is ignored), 1 <= n_chunks
+ * <= MIP_MAX_BATCH_CHUNKS, in rank order. `out`: batch_model must be NULL, flags MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC.
+ * Needs the mesh table only, not instances; enqueued on the context's first stream, like mip_merge_draw_lists.
+ * RESULT, with c[r][b] = chunk r's count of bucket b: total[b] = sum over r of c[r][b]; first[b] = the exclusive prefix sum of
+ * total; the members of (b, r) go to slots [first[b] + sum over r' < r of c[r'][b], ... + c[r][b]), copied from chunk r's ids at
+ * the exclusive prefix of c[r][.]. Commands: one per bucket with total[b] > 0, ascending, packed from entry 0, indexCount /
+ * firstIndex / vertexOffset as mip_batch_draws_lods writes them for that bucket from THIS context's table, instanceCount =
+ * total[b], firstInstance = first[b]. batch_count and instance_count as that call writes them; nothing at or behind either
+ * count is touched. instance_ids needs room for n_chunks x chunk_capacity words and may be only 4-byte aligned; batch_cmds
+ * needs room for min(B, n_chunks x chunk_capacity) commands.
+ * BAD CHUNKS are decided before anything is copied. A chunk is CORRUPT if n_buckets != B, a reserved word is not 0, or its
+ * counts do not sum to `members`: MIP_ERR_DEVICE. If none is corrupt and some chunk has members > chunk_capacity (a tightened
+ * chunk overflowed): MIP_ERR_CAPACITY. Either way batch_count and instance_count are written as 0 and batch_cmds and
+ * instance_ids are not touched; the status is returned by a synchronous call and by mip_wait for an asynchronous one. The
+ * kernels never read outside [chunk, chunk + MIP_BATCH_CHUNK_BYTES(B, chunk_capacity)) and never write outside the room
+ * stated above, whatever the words say.
+ * REFUSED, nothing written: NULL ctx / chunks / out / batch_cmds / batch_count / instance_ids, a wrong struct_size, unknown
+ * flags, a missing MIP_OUT_DEVICE, batch_model != NULL, n_chunks out of range, a misaligned pointer, a stride that is not a
+ * multiple of 16 or too small: MIP_ERR_INVALID_ARGUMENT; no mesh table: MIP_ERR_NOT_READY; n_chunks x B > 2^24 or n_chunks x
+ * chunk_capacity >= 2^32: MIP_ERR_CAPACITY.
+ * OUT OF SCOPE: batch_model across shards (read `model` through the ids on the owning rank, or gather it separately); the
+ * depth orders of mip_batch_draws_ordered (a merge of runs sorted by D is a different kernel); views; a native RCCL entry
+ * point beside mip_run_sharded (renderer_amd/sharded.py, BatchExchange, is the exchange); mip_run_many / recorded graphs. */
+int32_t mip_merge_batches(MipContext* ctx, const void* chunks, uint32_t n_chunks, uint64_t chunk_stride_bytes,
+                          uint32_t chunk_capacity, const MipBatchOutputs* out);
 
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).

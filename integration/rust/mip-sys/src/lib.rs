@@ -125,6 +125,20 @@ pub const MIP_BATCH_ORDER_DRAW_INDEX: u32 = 0;
 pub const MIP_BATCH_ORDER_NEAR_FIRST: u32 = 1;
 pub const MIP_BATCH_ORDER_FAR_FIRST: u32 = 2;
 
+/// What a shard's batch chunk starts with (mip_batch_draws_shard / mip_merge_batches): then `n_buckets` counts, zero words up
+/// to a multiple of 16 bytes, and the ids.
+#[repr(C)]
+pub struct MipBatchChunkHeader {
+    pub members: u32,
+    pub n_buckets: u32,
+    pub reserved: [u32; 2],
+}
+pub const MIP_MAX_BATCH_CHUNKS: u32 = 64;
+/// MIP_BATCH_CHUNK_IDS_OFFSET: bytes in front of the ids of a chunk for a table of `buckets` buckets.
+pub const fn mip_batch_chunk_ids_offset(buckets: u64) -> u64 { 16 + (buckets + (4 - buckets % 4) % 4) * 4 }
+/// MIP_BATCH_CHUNK_BYTES: bytes of a chunk with room for `capacity` ids.
+pub const fn mip_batch_chunk_bytes(buckets: u64, capacity: u64) -> u64 { mip_batch_chunk_ids_offset(buckets) + capacity * 4 }
+
 /// Outputs of mip_batch_draws_views: every view's commands in its own range of `batch_cmds`, one shared `instance_ids`.
 #[repr(C)]
 pub struct MipViewBatchOutputs {
@@ -201,6 +215,10 @@ extern "C" {
     /// `n_views` device pointers (null: every resident instance).
     pub fn mip_batch_draws_views(ctx: *mut MipContext, frames: *const MipFrame, visible_bitmaps: *const *const u32,
                                  n_views: u32, policy: *const MipLodPolicy, out: *const MipViewBatchOutputs) -> i32;
+    pub fn mip_batch_draws_shard(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
+                                 chunk: *mut c_void, ids_capacity: u32, flags: u32) -> i32;
+    pub fn mip_merge_batches(ctx: *mut MipContext, chunks: *const c_void, n_chunks: u32, chunk_stride_bytes: u64, chunk_capacity: u32,
+                             out: *const MipBatchOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -215,6 +233,7 @@ const _: () = assert!(std::mem::size_of::<MipDrawIndexedIndirectCommand>() == 20
 const _: [u8; 48] = [0; std::mem::size_of::<MipBatchOutputs>()];
 const _: [u8; 28] = [0; std::mem::size_of::<MipLodPolicy>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipViewBatchOutputs>()];
+const _: [u8; 16] = [0; std::mem::size_of::<MipBatchChunkHeader>()];
 
 impl Pipeline {
     /// `panic = "abort"` (Cargo.toml:133,138) makes a panic here as final as in the rest of the renderer.

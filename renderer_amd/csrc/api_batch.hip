@@ -4,12 +4,20 @@
 // mip_batch_draws_lods does the same over the whole LOD chain, bucket = lod_base[mesh] + lod, with the caller's thresholds.
 // mip_batch_draws_ordered is mip_batch_draws_lods with the members of a bucket nearest first or farthest first.
 // mip_batch_draws_views is mip_batch_draws_lods for several views in one call: key = view * B + bucket, one shared instance_ids.
+// mip_batch_draws_shard is mip_batch_draws_lods for one shard of a sharded scene: ids and dense bucket counts into a chunk;
+// mip_merge_batches merges the all-gathered chunks into the bytes of the unsharded call (batch_merge_kernel.hpp).
 // One stage (batch_kernel.hpp) under the key policies of the four entry points (batch_kernel.hpp, batch_lods_kernel.hpp,
 // batch_views_kernel.hpp); batch_plan.hpp says which instantiation a call launches. The kernels are instantiated here and only here.
 #include "context.hpp"
 #include "batch_views_kernel.hpp"
+#include "batch_merge_kernel.hpp"
 
 static_assert(sizeof(MipViewBatchOutputs) == 48, "MipViewBatchOutputs is part of the ABI");
+static_assert(sizeof(MipBatchChunkHeader) == mip::kBatchChunkHeaderWords * 4 && MIP_MAX_BATCH_CHUNKS == mip::kMaxBatchChunks,
+              "the batch chunk: header and kernels agree");
+static_assert(MIP_BATCH_CHUNK_IDS_OFFSET(1) == 32 && MIP_BATCH_CHUNK_IDS_OFFSET(4) == 32 && MIP_BATCH_CHUNK_IDS_OFFSET(5) == 48 &&
+              MIP_BATCH_CHUNK_IDS_OFFSET(257) == mip::batch_chunk_ids_offset_words(257) * 4 &&
+              MIP_BATCH_CHUNK_BYTES(200, 1000) == mip::batch_chunk_bytes(200, 1000), "the batch chunk: header and plan agree");
 
 namespace mip_host {
 namespace {
@@ -86,6 +94,7 @@ const void* kernel_address(mip::BatchKernel k) {
     case K::scatter_views_relative_last: return (const void*)mip_batch_scatter_kernel<ViewsR, true, 0>;
     case K::scatter_views_list_last: return (const void*)mip_batch_scatter_kernel<BatchViewsListKey, true, 0>;
     case K::commands_views: return (const void*)mip_batch_view_commands_kernel;
+    case K::commands_shard: return (const void*)mip_batch_shard_chunk_kernel;
   }
   return nullptr;
 }
@@ -159,6 +168,8 @@ void batch_release(MipContext* ctx) {
   }
   ctx->batch.clear();
   release_view_scratch(ctx->view_batch);
+  (void)hipFree(ctx->batch_merge.d_words);
+  ctx->batch_merge = MipContext::BatchMergeScratch{};
 }
 
 namespace {
@@ -179,17 +190,23 @@ int32_t check_call(MipContext* ctx, const MipFrame* frame, const uint32_t* visib
   return MIP_OK;
 }
 
-// The three entry points. policy == null: mip_batch_draws (pick_lod, bucket = mesh * 2 + lod); else the whole LOD chain, in
+// The four entry points. policy == null: mip_batch_draws (pick_lod, bucket = mesh * 2 + lod); else the whole LOD chain, in
 // draw order (MIP_BATCH_ORDER_DRAW_INDEX: mip_batch_draws_lods) or by key = bucket << 16 | D (NEAR_FIRST / FAR_FIRST).
+// shard_chunk != null: mip_batch_draws_shard — mip_batch_draws_lods with the ids going to the chunk (out->instance_ids points
+// at them, out->batch_cmds / batch_count are not written) and the chunk epilogue in the command writer's place.
 int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy, uint32_t order,
-                    const MipBatchOutputs* out) {
+                    const MipBatchOutputs* out, uint32_t* shard_chunk = nullptr, uint32_t shard_ids_capacity = 0) {
   using mip::BatchEntry;
   if (int32_t rc = check_call(ctx, frame, visible_bitmap, out)) return rc;
+  if (shard_chunk && shard_ids_capacity < ctx->n)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "ids_capacity %u < %u resident instances", shard_ids_capacity, ctx->n);
   // behind the frame issued last: a bitmap that frame writes is ordered before these launches without a wait
   const uint32_t slot = ctx->last_slot;
   hipStream_t stream = ctx->slots[slot].stream;
   const uint32_t n = ctx->n;
-  const BatchEntry entry = !policy ? BatchEntry::draws : order == MIP_BATCH_ORDER_DRAW_INDEX ? BatchEntry::lods : BatchEntry::ordered;
+  const BatchEntry entry = shard_chunk ? BatchEntry::shard
+                           : !policy   ? BatchEntry::draws
+                                       : order == MIP_BATCH_ORDER_DRAW_INDEX ? BatchEntry::lods : BatchEntry::ordered;
   const unsigned long long buckets = policy ? ctx->lod_buckets : 2ull * ctx->m;
   if (entry == BatchEntry::ordered) {
     if (buckets > mip::kBatchOrderedMaxBuckets)
@@ -198,6 +215,13 @@ int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visi
     return fail(ctx, MIP_ERR_CAPACITY, "%u meshes, %llu buckets: a bucket does not fit a 32-bit key", ctx->m, buckets);
   }
 
+  if (shard_chunk && (n == 0 || buckets == 0)) {  // nothing to bin: the header and B zeros
+    mip::ShardBatchArgs z{};
+    z.chunk = shard_chunk;
+    z.n_buckets = (uint32_t)buckets;
+    if (int32_t rc = launch(ctx, mip::BatchKernel::commands_shard, 1, stream, z)) return rc;
+    return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
+  }
   if (n == 0 || buckets == 0) {  // nothing to bin: two zeros
     MIP_HIP(ctx, hipMemsetAsync(out->batch_count, 0, 4, stream));
     if (out->instance_count) MIP_HIP(ctx, hipMemsetAsync(out->instance_count, 0, 4, stream));
@@ -211,7 +235,8 @@ int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visi
   MipContext::BatchScratch& bs = ctx->batch[slot];
   if (int32_t rc = ensure_scratch(ctx, bs, several, out->batch_model != nullptr)) return rc;
 
-  mip::OrderedBatchArgs a{};
+  mip::ShardBatchArgs a{};  // the most derived block: every kernel takes its own leading part
+  a.chunk = shard_chunk;
   if (policy) {
     a.chain = ctx->d_mesh_chain;
     a.bucket_lod = ctx->d_bucket_lod;
@@ -372,6 +397,71 @@ int32_t batch_draws_views(MipContext* ctx, const MipFrame* frames, const uint32_
   return finish(ctx, stream, async);
 }
 
+// mip_merge_batches: every check first (a refused call writes nothing), then the offsets kernel and the gather on the
+// context's first stream, where the other merges run.
+int32_t merge_batches(MipContext* ctx, const void* chunks, uint32_t n_chunks, uint64_t stride, uint32_t capacity, const MipBatchOutputs* out) {
+  if (!chunks || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "chunks/out is NULL");
+  if (out->struct_size != sizeof(MipBatchOutputs))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipBatchOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipBatchOutputs));
+  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipBatchOutputs flags 0x%x", out->flags);
+  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_merge_batches needs MIP_OUT_DEVICE outputs");
+  if (!out->batch_cmds || !out->batch_count || !out->instance_ids)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds/batch_count/instance_ids is NULL");
+  if (out->batch_model) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_merge_batches does not merge matrices: batch_model must be NULL");
+  if ((uintptr_t)out->batch_cmds % 4u != 0u || (uintptr_t)out->instance_ids % 4u != 0u || (uintptr_t)out->batch_count % 4u != 0u ||
+      (uintptr_t)out->instance_count % 4u != 0u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "an output is not 4-byte aligned");
+  if ((uintptr_t)chunks % 16u != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch chunks must be 16-byte aligned");
+  if (n_chunks == 0 || n_chunks > MIP_MAX_BATCH_CHUNKS)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "n_chunks %u outside 1..%u", n_chunks, (unsigned)MIP_MAX_BATCH_CHUNKS);
+  if (!ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "the chunks are merged against the mesh table: set it first");
+  const unsigned long long buckets = ctx->lod_buckets;
+  if (stride % 16u != 0u || stride < MIP_BATCH_CHUNK_BYTES(buckets, capacity))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "a chunk of %llu buckets and %u ids takes %llu bytes: the stride of %llu is smaller, or no multiple of 16",
+                buckets, capacity, (unsigned long long)MIP_BATCH_CHUNK_BYTES(buckets, capacity), (unsigned long long)stride);
+  if (!mip::batch_merge_table_fits(n_chunks, buckets))
+    return fail(ctx, MIP_ERR_CAPACITY, "%u chunks x %llu buckets: the offsets table takes at most 2^24 counts", n_chunks, buckets);
+  if (!mip::batch_merge_slots_fit(n_chunks, capacity))
+    return fail(ctx, MIP_ERR_CAPACITY, "%u chunks x %u ids: the merged list does not fit a 32-bit count", n_chunks, capacity);
+  if (int32_t rc = bind_device(ctx)) return rc;
+  hipStream_t stream = ctx->stream;
+
+  const mip::BatchMergePlan plan = mip::plan_batch_merge(n_chunks, buckets, capacity);
+  MipContext::BatchMergeScratch& ms = ctx->batch_merge;
+  if (plan.scratch_words > ms.words_cap) {  // (hipFree waits for the work that still reads the old one)
+    (void)hipFree(ms.d_words);
+    ms.d_words = nullptr;
+    ms.words_cap = 0;
+    MIP_HIP(ctx, hipMalloc(&ms.d_words, (size_t)plan.scratch_words * 4));
+    ms.words_cap = (size_t)plan.scratch_words;
+  }
+  mip::BatchMergeArgs a{};
+  a.chunks = static_cast<const unsigned char*>(chunks);
+  a.stride = stride;
+  a.n_chunks = n_chunks;
+  a.n_buckets = (uint32_t)buckets;
+  a.capacity = capacity;
+  a.ids_offset_words = (uint32_t)mip::batch_chunk_ids_offset_words(buckets);
+  a.chain = ctx->d_mesh_chain;
+  a.bucket_lod = ctx->d_bucket_lod;
+  a.mesh_draw = ctx->d_mesh_draw;
+  a.head = ms.d_words;
+  a.src_start = ms.d_words + plan.src_start;
+  a.seg_dst = ms.d_words + plan.seg_dst;
+  a.seg_src = ms.d_words + plan.seg_src;
+  a.seg_rank = ms.d_words + plan.seg_rank;
+  a.batch_cmds = static_cast<uint32_t*>(out->batch_cmds);
+  a.batch_count = out->batch_count;
+  a.instance_count = out->instance_count;
+  a.instance_ids = out->instance_ids;
+  a.error_flag = ctx->d_error;
+  hipLaunchKernelGGL(mip::mip_batch_merge_offsets_kernel, dim3(1), dim3(mip::kBatchMergeThreads), 0, stream, a);
+  MIP_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(mip::mip_batch_merge_gather_kernel, dim3(plan.gather_blocks), dim3(mip::kBatchMergeThreads), 0, stream, a);
+  MIP_HIP(ctx, hipGetLastError());
+  return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
+}
+
 }  // namespace
 }  // namespace mip_host
 
@@ -405,6 +495,28 @@ int32_t mip_batch_draws_views(MipContext* ctx, const MipFrame* frames, const uin
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
   if (int32_t rc = check_policy(ctx, policy)) return rc;
   return batch_draws_views(ctx, frames, visible_bitmaps, n_views, policy, out);
+}
+
+int32_t mip_batch_draws_shard(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                              void* chunk, uint32_t ids_capacity, uint32_t flags) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  if (!chunk) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "chunk is NULL");
+  if ((uintptr_t)chunk % 16u != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "chunk is not 16-byte aligned");
+  // the stage's outputs as batch_draws() takes them: the ids of the chunk; no commands, no counts, no matrices
+  MipBatchOutputs out{};
+  out.struct_size = sizeof(MipBatchOutputs);
+  out.flags = flags;
+  out.batch_cmds = chunk;                               // (not written: the chunk epilogue takes the command writer's place)
+  out.batch_count = static_cast<uint32_t*>(chunk);
+  out.instance_ids = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(chunk) + MIP_BATCH_CHUNK_IDS_OFFSET(ctx->lod_buckets));
+  return batch_draws(ctx, frame, visible_bitmap, policy, MIP_BATCH_ORDER_DRAW_INDEX, &out, static_cast<uint32_t*>(chunk), ids_capacity);
+}
+
+int32_t mip_merge_batches(MipContext* ctx, const void* chunks, uint32_t n_chunks, uint64_t chunk_stride_bytes, uint32_t chunk_capacity,
+                          const MipBatchOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  return merge_batches(ctx, chunks, n_chunks, chunk_stride_bytes, chunk_capacity, out);
 }
 
 }  // extern "C"

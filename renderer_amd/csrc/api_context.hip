@@ -61,6 +61,10 @@ int32_t check_device_error(MipContext* ctx) {
     return fail(ctx, MIP_ERR_TIMEOUT, "a wait for (or signal of) an external semaphore failed or expired after 10 s; the frame behind it ran anyway");
   if (e & mip::kErrWireRecord)
     return fail(ctx, MIP_ERR_DEVICE, "a wire record names a mesh outside this context's mesh table (corrupt chunk, or the ranks hold different tables)");
+  if (e & mip::kErrBatchChunkCorrupt)
+    return fail(ctx, MIP_ERR_DEVICE, "a batch chunk is corrupt (its n_buckets is not this table's, a reserved word is set, or its counts do not sum to its members); nothing was merged");
+  if (e & mip::kErrBatchChunkOverflow)
+    return fail(ctx, MIP_ERR_CAPACITY, "a shard's batch chunk holds more members than the exchanged chunk_capacity; nothing was merged");
   return repair_rc;
 }
 

@@ -12,8 +12,8 @@ constexpr uint32_t kBatchMaxPasses = 4;
 constexpr uint32_t kBatchDepthBits = 16;  // D's field of the ordered key (batch_lods_kernel.hpp)
 static_assert(kBatchMaxPasses * kBatchDigitBits >= 32, "a 32-bit key takes at most kBatchMaxPasses digits");
 
-// mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered (NEAR / FAR), mip_batch_draws_views
-enum class BatchEntry : uint32_t { draws, lods, ordered, views };
+// mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered (NEAR / FAR), mip_batch_draws_views, mip_batch_draws_shard
+enum class BatchEntry : uint32_t { draws, lods, ordered, views, shard };
 
 // Every instantiation of the stage (batch_kernel.hpp), by key policy. scatter: `mid` = a pass of several, `last` = the one
 // pass, ids only, `model` / `general` = the one pass with matrices (census-selected / general arithmetic).
@@ -32,6 +32,9 @@ enum class BatchKernel : uint32_t {
   count_views_distance, count_views_relative,
   scatter_views_distance_mid, scatter_views_distance_last, scatter_views_relative_mid, scatter_views_relative_last,
   scatter_views_list_last, commands_views,
+  // mip_batch_draws_shard (batch_merge_kernel.hpp): mip_batch_draws_lods' count / rowscan / scatter with the ids going to the
+  // chunk; the epilogue that writes the dense bucket counts and the chunk header in the command writer's place
+  commands_shard,
 };
 
 struct BatchPlan {
@@ -58,6 +61,7 @@ constexpr bool batch_views_entries_fit(unsigned long long n_views, unsigned long
 
 // `relative`: the policy's mode is MIP_LOD_RELATIVE (ignored by mip_batch_draws, which has no policy). buckets >= 1; for
 // BatchEntry::views they are the GLOBAL buckets n_views x B (key = view * B + bucket), and no matrices are stored.
+// BatchEntry::shard is BatchEntry::lods without matrices and with the chunk epilogue for a command writer.
 constexpr BatchPlan plan_batch(BatchEntry entry, bool relative, unsigned long long buckets, bool want_model, bool general) {
   using K = BatchKernel;
   // rows: pick_lod, the chain under DISTANCE, under RELATIVE
@@ -72,7 +76,7 @@ constexpr BatchPlan plan_batch(BatchEntry entry, bool relative, unsigned long lo
   const uint32_t row = entry == BatchEntry::draws ? 0u : relative ? 2u : 1u;
   BatchPlan p{};
   p.passes = (bits + kBatchDigitBits - 1u) / kBatchDigitBits;
-  p.commands = entry == BatchEntry::draws ? K::commands_pair : K::commands_chain;
+  p.commands = entry == BatchEntry::draws ? K::commands_pair : entry == BatchEntry::shard ? K::commands_shard : K::commands_chain;
   p.list_last = K::scatter_list_last;
   if (entry == BatchEntry::views) {
     p.count0 = relative ? K::count_views_relative : K::count_views_distance;
@@ -83,6 +87,7 @@ constexpr BatchPlan plan_batch(BatchEntry entry, bool relative, unsigned long lo
     p.model = K::none;
     return p;
   }
+  if (entry == BatchEntry::shard) want_model = false;
   if (ordered) {
     p.count0 = relative ? K::count_ordered_relative : K::count_ordered_distance;
     p.scatter0 = relative ? K::scatter_ordered_relative_mid : K::scatter_ordered_distance_mid;

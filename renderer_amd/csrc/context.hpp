@@ -6,8 +6,9 @@
 //   api_interop.hip   external memory and external semaphores (row f-2)
 //   api_occlusion.hip the occlusion-culling extension: depth pyramid builds, mip_run_occluded (occlusion_kernel.hpp)
 //   api_batch.hip     the batched-draws extension: mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered,
-//                     mip_batch_draws_views — one stage (batch_kernel.hpp) under the key policies of batch_lods_kernel.hpp and
-//                     batch_views_kernel.hpp, planned by batch_plan.hpp
+//                     mip_batch_draws_views, mip_batch_draws_shard — one stage (batch_kernel.hpp) under the key policies of batch_lods_kernel.hpp and
+//                     batch_views_kernel.hpp, planned by batch_plan.hpp; mip_merge_batches (batch_merge_kernel.hpp,
+//                     batch_merge_plan.hpp)
 // (round 3 had all of it in one 2 224-line mip_api.hip)
 #pragma once
 
@@ -17,6 +18,7 @@
 #include "instance_kernel.hpp"  // rows a-1 .. a-7 (the kernel itself is instantiated in api_frame.hip and stages_tu.hip only)
 #include "stage_args.hpp"      // argument blocks + launchers of everything built in stages_tu.hip
 #include "mesh_chain.hpp"      // the per-mesh LOD chain of mip_batch_draws_lods
+#include "batch_merge_plan.hpp" // the shard chunk of batched draws, mip_merge_batches' plan and its two error bits
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library is opened with dlopen, never linked
@@ -113,6 +115,13 @@ struct MipContext {
     size_t entries_cap = 0, list_cap = 0, hist_cap = 0;  // entries d_counts / the lists hold, words of d_bucket_hist
   };
   ViewBatchScratch view_batch;
+  // mip_merge_batches (api_batch.hip): the offsets kernel's tables on the first stream (batch_merge_plan.hpp says what they
+  // hold), allocated at first use for the n_chunks x B asked for and grown by a larger call
+  struct BatchMergeScratch {
+    uint32_t* d_words = nullptr;
+    size_t words_cap = 0;
+  };
+  BatchMergeScratch batch_merge;
   std::vector<FrameSlot> view_states;  // mip_run_views: one prefix state per view, all on `stream`
   hipStream_t stream = nullptr;  // = slots[0].stream: uploads, merges, timing
   // resident inputs

@@ -112,6 +112,17 @@ def make_lod_policy(mode, switch_sq):
     return p
 
 
+def batch_chunk_ids_offset(n_buckets):
+    """MIP_BATCH_CHUNK_IDS_OFFSET: bytes in front of a batch chunk's ids (the 16-byte header, B counts, the pad to 16 bytes)."""
+    n_buckets = int(n_buckets)
+    return 16 + (n_buckets + (4 - n_buckets % 4) % 4) * 4
+
+
+def batch_chunk_bytes(n_buckets, capacity):
+    """MIP_BATCH_CHUNK_BYTES: bytes of a batch chunk with room for `capacity` ids."""
+    return batch_chunk_ids_offset(n_buckets) + int(capacity) * 4
+
+
 def make_frame(planes, cam_pos, first_instance_base=0, first_index_base=0, pv=None):
     f = MipFrame()
     if pv is not None:
@@ -538,6 +549,31 @@ class InstancePipeline:
         out.instance_ids = instance_ids or None
         out.view_first_slot = view_first_slot or None
         self._check(self._lib.mip_batch_draws_views(self._ctx, C.addressof(fr), C.addressof(bm), k, C.addressof(policy), C.addressof(out)))
+
+    def batch_draws_shard(self, frame, visible_bitmap_ptr, policy, chunk_ptr, ids_capacity, async_=False):
+        """mip_batch_draws_shard: batch_draws_lods of this context's instances — one shard of a sharded scene — into a batch
+        chunk at `chunk_ptr` (device memory, 16-byte aligned, batch_chunk_bytes(B, ids_capacity) bytes): the header {members, B,
+        0, 0}, the dense per-bucket counts, the ids in slot order. ids_capacity >= the resident instances."""
+        flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+        self._check(self._lib.mip_batch_draws_shard(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                    chunk_ptr or None, int(ids_capacity), flags))
+
+    def merge_batches(self, chunks_ptr, n_chunks, chunk_stride_bytes, chunk_capacity, *, batch_cmds, batch_count, instance_ids,
+                      instance_count=0, async_=False):
+        """mip_merge_batches: the batch chunks of n_chunks shards (rank order, chunk_stride_bytes apart, as an all-gather lays
+        them out) merged into what ONE batch_draws_lods call writes for the unsharded scene. instance_ids needs room for
+        n_chunks x chunk_capacity words, batch_cmds for min(B, n_chunks x chunk_capacity) commands. A corrupt chunk is
+        MIP_ERR_DEVICE, a chunk with more members than chunk_capacity MIP_ERR_CAPACITY (from wait() for an async call); both
+        leave two zero counts and nothing else."""
+        out = MipBatchOutputs()
+        out.struct_size = C.sizeof(MipBatchOutputs)
+        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+        out.batch_cmds = batch_cmds or None
+        out.batch_count = batch_count or None
+        out.instance_ids = instance_ids or None
+        out.instance_count = instance_count or None
+        self._check(self._lib.mip_merge_batches(self._ctx, chunks_ptr or None, int(n_chunks), int(chunk_stride_bytes), int(chunk_capacity),
+                                                C.addressof(out)))
 
     # -- diagnostics --
     def timings(self):

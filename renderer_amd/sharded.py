@@ -24,7 +24,7 @@ with world sizes 2 and 3 under gloo on CPU; N = 2/4/8 numbers come from the roun
 import numpy as np
 
 from ._lib import MipError
-from .pipeline import SHARD_HEADER_BYTES, make_frame, wire_body_bytes, wire_form, wire_index_bits
+from .pipeline import SHARD_HEADER_BYTES, batch_chunk_bytes, make_frame, wire_body_bytes, wire_form, wire_index_bits
 
 MIP_ERR_CAPACITY = -4
 
@@ -47,7 +47,69 @@ def chunk_stride_bytes(capacity, wire=False):
     return (stride + 255) // 256 * 256
 
 
-class DrawListExchange:
+def batch_chunk_stride_bytes(n_buckets, capacity):
+    """Bytes between the batch chunks of an all-gather: MIP_BATCH_CHUNK_BYTES(n_buckets, capacity), rounded up to 256."""
+    return (batch_chunk_bytes(n_buckets, capacity) + 255) // 256 * 256
+
+
+class _TightenedExchange:
+    """What the exchanges of this module share: the stream guard and complete(), the collective-safe repair of a tightened
+    chunk that overflowed. A subclass supplies pipe / torch / device / capacity / n_max / retries / _in_flight,
+    set_capacity(), _gather_and_merge() and _largest_gathered() (the largest count any rank's gathered header reports)."""
+
+    def _check_stream(self, what):
+        # kernel -> all-gather -> merge are ordered by ONE stream: the collective goes to torch's current stream, so a
+        # HIP context must have been created on that very stream (the CPU stand-ins of the tests have no `stream`)
+        if self._on_gpu and hasattr(self.pipe, "stream"):
+            current = self.torch.cuda.current_stream(self.device).cuda_stream
+            if self.pipe.stream is None or int(self.pipe.stream) != int(current):
+                raise ValueError(f"{type(self).__name__}.{what}: the pipeline's stream is not torch's current stream — create it with "
+                                 "InstancePipeline(..., stream=torch.cuda.current_stream(device).cuda_stream) and call it "
+                                 "under that stream; the all-gather would otherwise race with the kernels")
+
+    def complete(self):
+        """Block until the frames issued so far are done. If the LAST one overflowed its tightened chunk,
+        repeat its all-gather + merge at full capacity (collective: the overflow is visible in the headers
+        every rank gathered, so every rank takes this branch together). Returns True if it had to."""
+        if self._in_flight:
+            self._check_stream("complete")  # a repair issues an all-gather: it must land on the pipeline's stream
+        in_flight, self._in_flight = self._in_flight, 0
+        err = None
+        try:
+            self.pipe.wait()
+        except MipError as e:
+            err = e
+        if err is None:
+            return False
+        # Whether to repair is decided from data EVERY rank holds — the gathered headers — never from which error code this
+        # rank happened to get: the merge kernel raises the overflow on every rank alike, but a rank with a second, local
+        # error (a corrupt record, an external semaphore that expired) is handed THAT code by mip_wait, and a rank that then
+        # skipped the repair's all-gather would leave its peers blocked in it for good (round-3 advisor finding).
+        overflow = False
+        if in_flight:
+            # the gathered headers are read back through the device: after a FATAL device error that read may itself fail or
+            # return garbage (a count above every shard's size) — then there is nothing to repair, and the error that counts is
+            # the one mip_wait reported (round-4 advisor finding)
+            try:
+                largest = self._largest_gathered()
+            except Exception:  # noqa: BLE001 (torch raises RuntimeError subclasses on a dead device)
+                raise err from None
+            overflow = self.capacity < largest <= self.n_max
+        if not overflow:
+            raise err
+        if in_flight != 1:
+            raise MipError(MIP_ERR_CAPACITY, "a tightened chunk overflowed with several frames in flight: the overflowing "
+                                             "frame's list has been overwritten; call complete() after every frame") from err
+        self.set_capacity(self.n_max)
+        self._gather_and_merge()
+        self.pipe.wait()
+        self.retries += 1
+        if err.code != MIP_ERR_CAPACITY:
+            raise err  # this rank's own error, reported AFTER it has taken part in the collective repair
+        return True
+
+
+class DrawListExchange(_TightenedExchange):
     """Frame driver for one rank of a sharded scene.
 
     `pipe` needs run_device(frame, **ptrs) and merge_draw_lists(...) with the semantics of
@@ -100,16 +162,6 @@ class DrawListExchange:
         self.recv = torch.empty(self.world * words, dtype=torch.int32, device=self.device)
         self.merged = torch.empty((max(self.world * self.capacity, 1), 5), dtype=torch.int32, device=self.device)
 
-    def _check_stream(self, what):
-        # kernel -> all-gather -> merge are ordered by ONE stream: the collective goes to torch's current stream, so a
-        # HIP context must have been created on that very stream (the CPU stand-ins of the tests have no `stream`)
-        if self._on_gpu and hasattr(self.pipe, "stream"):
-            current = self.torch.cuda.current_stream(self.device).cuda_stream
-            if self.pipe.stream is None or int(self.pipe.stream) != int(current):
-                raise ValueError(f"DrawListExchange.{what}: the pipeline's stream is not torch's current stream — create it with "
-                                 "InstancePipeline(..., stream=torch.cuda.current_stream(device).cuda_stream) and call it "
-                                 "under that stream; the all-gather would otherwise race with the kernels")
-
     def step(self, frame, outs=None, model=0, visible_bitmap=0, world_aabb=0, kernel_done=None):
         """One frame on this rank. `outs` (optional) supplies model / bitmap device buffers. `kernel_done`
         (optional, a torch.cuda.Event) is recorded right behind the shard kernel, in front of the all-gather."""
@@ -135,47 +187,9 @@ class DrawListExchange:
             self.pipe.merge_draw_lists(self.recv.data_ptr(), self.world, self.stride, self.merged.data_ptr(), self.merged_count.data_ptr(),
                                        async_=True, chunk_capacity=self.capacity)
 
-    def complete(self):
-        """Block until the frames issued so far are done. If the LAST one overflowed its tightened chunk,
-        repeat its all-gather + merge at full capacity (collective: the overflow is visible in the headers
-        every rank gathered, so every rank takes this branch together). Returns True if it had to."""
-        if self._in_flight:
-            self._check_stream("complete")  # a repair issues an all-gather: it must land on the pipeline's stream
-        in_flight, self._in_flight = self._in_flight, 0
-        err = None
-        try:
-            self.pipe.wait()
-        except MipError as e:
-            err = e
-        if err is None:
-            return False
-        # Whether to repair is decided from data EVERY rank holds — the gathered headers — never from which error code this
-        # rank happened to get: the merge kernel raises the overflow on every rank alike, but a rank with a second, local
-        # error (a corrupt record, an external semaphore that expired) is handed THAT code by mip_wait, and a rank that then
-        # skipped the repair's all-gather would leave its peers blocked in it for good (round-3 advisor finding).
-        overflow = False
-        if in_flight:
-            # the gathered headers are read back through the device: after a FATAL device error that read may itself fail or
-            # return garbage (a count above every shard's size) — then there is nothing to repair, and the error that counts is
-            # the one mip_wait reported (round-4 advisor finding)
-            try:
-                counts, _ = self.counts()
-                largest = int(counts.max())
-            except Exception:  # noqa: BLE001 (torch raises RuntimeError subclasses on a dead device)
-                raise err from None
-            overflow = self.capacity < largest <= self.n_max
-        if not overflow:
-            raise err
-        if in_flight != 1:
-            raise MipError(MIP_ERR_CAPACITY, "a tightened chunk overflowed with several frames in flight: the overflowing "
-                                             "frame's list has been overwritten; call complete() after every frame") from err
-        self.set_capacity(self.n_max)
-        self._gather_and_merge()
-        self.pipe.wait()
-        self.retries += 1
-        if err.code != MIP_ERR_CAPACITY:
-            raise err  # this rank's own error, reported AFTER it has taken part in the collective repair
-        return True
+    def _largest_gathered(self):
+        counts, _ = self.counts()
+        return int(counts.max())
 
     # -- host-side views (synchronising) --
     def local_count(self):
@@ -201,6 +215,86 @@ class DrawListExchange:
         total, index_total = (int(x) & 0xFFFFFFFF for x in self.merged_count.cpu().tolist())
         cmds = self.merged[:total].cpu().numpy().view(np.uint32).reshape(-1).view(DRAW_CMD_DTYPE)
         return cmds.copy(), total, index_total
+
+
+class BatchExchange(_TightenedExchange):
+    """Batched draws of a sharded scene, one rank's side: batch_draws_shard into a full-size send buffer, ONE all-gather of
+    the first `stride` bytes of every rank's chunk, merge_batches — all on the pipeline's stream. The merged commands, counts
+    and ids are, byte for byte, what batch_draws_lods writes for the unsharded scene (include/mi_instance_pipeline.h,
+    mip_merge_batches). A chunk is [16-byte header | n_buckets counts | pad | ids]: the ids come last, so a tightened exchange
+    sends a prefix, and a frame that overflows it is repaired by complete() exactly as DrawListExchange repairs a draw list.
+
+    `pipe` needs batch_draws_shard / merge_batches / wait with the semantics of renderer_amd.InstancePipeline; `n_buckets`
+    is the sum of n_lods over the mesh table every rank holds."""
+
+    def __init__(self, pipe, n_local, world, rank, device, n_buckets, dist=None, torch=None, group=None, capacity=None):
+        if torch is None:
+            import torch
+        if dist is None:
+            import torch.distributed as dist
+        self.torch, self.dist, self.group = torch, dist, group
+        self.pipe, self.n_local, self.world, self.rank, self.device = pipe, int(n_local), int(world), int(rank), device
+        self.n_buckets = int(n_buckets)
+        self._on_gpu = getattr(torch.device(device), "type", "cpu") == "cuda"
+        # every rank sizes its chunk by the LARGEST shard (DrawListExchange says why): one tiny all-reduce, collective
+        nmax = torch.tensor([self.n_local], dtype=torch.int64, device=device)
+        if self.world > 1:
+            dist.all_reduce(nmax, op=dist.ReduceOp.MAX, group=group)
+        self.n_max = int(nmax.item())
+        self._send_full = torch.zeros(batch_chunk_stride_bytes(self.n_buckets, self.n_max) // 4, dtype=torch.int32, device=device)
+        self.merged_counts = torch.zeros(2, dtype=torch.int32, device=device)   # batch_count, instance_count
+        self.retries = 0
+        self._in_flight = 0
+        self.set_capacity(self.n_max if capacity is None else capacity)
+
+    def set_capacity(self, capacity):
+        torch = self.torch
+        self.capacity = int(min(max(capacity, 0), self.n_max))  # the same number on every rank
+        self.stride = batch_chunk_stride_bytes(self.n_buckets, self.capacity)
+        words = self.stride // 4
+        self.send = self._send_full[:words]
+        self.recv = torch.empty(self.world * words, dtype=torch.int32, device=self.device)
+        slots = self.world * self.capacity
+        self.merged_ids = torch.empty(max(slots, 1), dtype=torch.int32, device=self.device)
+        self.merged_cmds = torch.empty((max(min(self.n_buckets, slots), 1), 5), dtype=torch.int32, device=self.device)
+
+    def step(self, frame, visible_bitmap, policy):
+        """One frame on this rank: `visible_bitmap` is a device pointer to the shard's bitmap (a mip_run of the same frame
+        enqueued in front needs no wait), `policy` from make_lod_policy, the same on every rank."""
+        self._check_stream("step")
+        self.pipe.batch_draws_shard(frame, visible_bitmap, policy, self._send_full.data_ptr(), self.n_max, async_=True)
+        self._gather_and_merge()
+        self._in_flight += 1
+
+    def _gather_and_merge(self):
+        self.dist.all_gather_into_tensor(self.recv, self.send, group=self.group)
+        self.pipe.merge_batches(self.recv.data_ptr(), self.world, self.stride, self.capacity, batch_cmds=self.merged_cmds.data_ptr(),
+                                batch_count=self.merged_counts.data_ptr(), instance_ids=self.merged_ids.data_ptr(),
+                                instance_count=self.merged_counts.data_ptr() + 4, async_=True)
+
+    # -- host-side views (synchronising) --
+    def members(self):
+        """Per-rank member counts of the last frame, from the gathered headers."""
+        return self.recv.view(self.world, self.stride // 4)[:, 0].cpu().numpy().view(np.uint32).copy()
+
+    def _largest_gathered(self):
+        return int(self.members().max())
+
+    def tighten(self, margin=1.0625):
+        """Shrink the exchanged chunk to the ids the last frame needed (max over ranks) plus a margin."""
+        cap = int(np.ceil(int(self.members().max()) * margin / 256.0) * 256)
+        self.set_capacity(max(cap, 256))
+        return self.capacity
+
+    def merged_batches(self):
+        """(commands, batch_count, ids, members) of the last frame on the host; completes — and if need be repairs — it first."""
+        from .pipeline import DRAW_CMD_DTYPE
+
+        self.complete()
+        count, members = (int(x) & 0xFFFFFFFF for x in self.merged_counts.cpu().tolist())
+        cmds = self.merged_cmds[:count].cpu().numpy().view(np.uint32).reshape(-1).view(DRAW_CMD_DTYPE)
+        ids = self.merged_ids[:members].cpu().numpy().view(np.uint32)
+        return cmds.copy(), count, ids.copy(), members
 
 
 class PipelinedExchange:

@@ -31,7 +31,15 @@ with four lights. Culled bitmaps come from one mip_run_views of the four frames;
 
   python tools/batch_bench.py --views [--out profiles/batch_draws_views_bench.jsonl]
 
---parent-library PATH (any of the four): the SAME legs on another build of the library (the parent commit's) as the yardstick,
+--sharded: batched draws of a sharded scene on ONE GPU: the scene as 8 contiguous shards (config 3 at 1 M, config 2 at 100 k;
+culled by the scene's frustum, and unculled), every shard's chunk written straight into the receive buffer. Times
+mip_batch_draws_shard beside mip_batch_draws_lods on the same shard, and mip_merge_batches beside two yardsticks of the same
+process: a device-to-device copy of the same members x 4 bytes, and mip_merge_wire_lists_packed over the same frame's eight
+draw lists. No all-gather is timed: no box with more than one GPU.
+
+  python tools/batch_bench.py --sharded [--out profiles/batch_merge_bench.jsonl]
+
+--parent-library PATH (any of the first four): the SAME legs on another build of the library (the parent commit's) as the yardstick,
 in the same session. A library is loaded once per process, so the tool then only starts children of itself, one after the
 other: the parent build, this build, the parent build again. Every row says which (`library`); the two parent runs give each
 leg's noise band: the larger of the difference of its two parent medians and its parent p90 - median."""
@@ -384,6 +392,73 @@ def bench_views(n, emit, samples=40, library="this build", n_views=4):
         p.close()
 
 
+def bench_sharded(n, emit, samples=40, library="this build", world=8):
+    import numpy as np
+    import torch
+
+    import renderer_amd
+    from renderer_amd import scene
+    from renderer_amd.pipeline import make_frame, make_lod_policy
+    from renderer_amd.sharded import batch_chunk_stride_bytes, chunk_stride_bytes, shard_range
+
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.Stream()
+    config = 2 if n <= 100_000 else 3
+    policy = make_lod_policy("distance", LODS_DISTANCE_SQ)
+    for culled in (True, False):
+        s = scene.make_scene(config, n=n, all_visible=not culled)
+        m = len(s["meshes"])
+        buckets = int(s["meshes"]["n_lods"].sum())
+        per = shard_range(n, world, 0)[1]
+        stride, wire_stride = batch_chunk_stride_bytes(buckets, per), chunk_stride_bytes(per, "packed")
+        with torch.cuda.stream(st):
+            p = renderer_amd.InstancePipeline(per, m, stream=st.cuda_stream)
+            p.set_mesh_table(s["meshes"])
+            recv = torch.zeros(world * stride // 4, dtype=torch.int32, device=dev)
+            wire_recv = torch.zeros(world * wire_stride // 4, dtype=torch.int32, device=dev)
+            bitmap = torch.zeros((per + 31) // 32 + 1, dtype=torch.int32, device=dev)
+            m_cmds = torch.empty((max(buckets, 1), 5), dtype=torch.int32, device=dev)
+            m_ids = torch.empty(world * per, dtype=torch.int32, device=dev)
+            m_scal = torch.zeros(8, dtype=torch.int32, device=dev)
+            l_cmds = torch.empty((world * per, 5), dtype=torch.int32, device=dev)
+            l_scal = torch.zeros(8, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            for rank in range(world):   # the last shard stays resident: the shard call is timed on it
+                lo, hi = shard_range(n, world, rank)
+                p.set_instances(s["pos"][lo:hi], s["rot"][lo:hi], s["scale"][lo:hi], s["mesh_id"][lo:hi])
+                frame = make_frame(s["planes"], s["cam_pos"], first_instance_base=lo)
+                w = wire_recv.data_ptr() + rank * wire_stride
+                p.run_device(frame, visible_bitmap=bitmap.data_ptr(), draw_cmds=w + 32, draw_count=w, draw_index_total=w + 4, wire=2)
+                p.batch_draws_shard(frame, bitmap.data_ptr(), policy, recv.data_ptr() + rank * stride, per)
+            members = int(recv.view(world, stride // 4)[:, 0].sum().item())
+            draws = int(wire_recv.view(world, wire_stride // 4)[:, 0].sum().item())
+            row = dict(library=library, n=n, config=config, world=world, culled=culled, buckets=buckets, shard_instances=per, members=members)
+
+            outs = dict(batch_cmds=m_cmds.data_ptr(), batch_count=m_scal.data_ptr(), instance_ids=m_ids.data_ptr(), instance_count=m_scal.data_ptr() + 4)
+            r = measure(st, lambda: p.batch_draws_lods(frame, bitmap.data_ptr(), policy, async_=True, **outs), samples=samples)
+            p.wait()
+            emit(dict(leg="sharded: batch_draws_lods on one shard, ids only", **row, **r))
+            scratch_chunk = torch.empty(stride // 4, dtype=torch.int32, device=dev)
+            r = measure(st, lambda: p.batch_draws_shard(frame, bitmap.data_ptr(), policy, scratch_chunk.data_ptr(), per, async_=True), samples=samples)
+            p.wait()
+            emit(dict(leg="sharded: batch_draws_shard on one shard", shard_members=int(scratch_chunk[0].item()), **row, **r))
+
+            r = measure(st, lambda: p.merge_batches(recv.data_ptr(), world, stride, per, async_=True, **outs), samples=samples)
+            p.wait()
+            assert int(m_scal[1].item()) == members
+            emit(dict(leg="sharded: merge_batches", batch_count=int(m_scal[0].item()), bytes_moved=8 * members, **row, **r))
+            src = torch.empty(max(members, 1), dtype=torch.int32, device=dev)
+            dst = torch.empty(max(members, 1), dtype=torch.int32, device=dev)
+            r = measure(st, lambda: dst.copy_(src), samples=samples)
+            emit(dict(leg="sharded: device-to-device copy of members x 4 bytes", bytes_moved=8 * members, **row, **r))
+            r = measure(st, lambda: p.merge_wire_lists(wire_recv.data_ptr(), world, wire_stride, l_cmds.data_ptr(), l_scal.data_ptr(), async_=True,
+                                                       chunk_capacity=per, packed=True), samples=samples)
+            p.wait()
+            assert int(l_scal[0].item()) == draws
+            emit(dict(leg="sharded: merge_wire_lists_packed of the same frame's draw lists", draws=draws, bytes_moved=draws * 24, **row, **r))
+            p.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("n", nargs="*", type=int, default=[1_000_000, 100_000])
@@ -392,6 +467,7 @@ def main():
     ap.add_argument("--lods", action="store_true", help="the mip_batch_draws_lods legs instead of (a) .. (s)")
     ap.add_argument("--ordered", action="store_true", help="the mip_batch_draws_ordered legs instead of (a) .. (s)")
     ap.add_argument("--views", action="store_true", help="the mip_batch_draws_views legs (V = 4) and their yardsticks instead of (a) .. (s)")
+    ap.add_argument("--sharded", action="store_true", help="mip_batch_draws_shard and mip_merge_batches over 8 shards, and their yardsticks")
     ap.add_argument("--parent-library", default=None, help="also run the same legs on this build of the library: the yardstick (child processes)")
     ap.add_argument("--library-label", default="this build", help=argparse.SUPPRESS)  # a child's rows: which library it loaded
     a = ap.parse_args()
@@ -413,7 +489,9 @@ def main():
             subprocess.run(cmd + ["--library-label", label], check=True, env=env)
         return
     for n in a.n:
-        if a.views:
+        if a.sharded:
+            bench_sharded(n, emit, a.samples, library=a.library_label)
+        elif a.views:
             bench_views(n, emit, a.samples, library=a.library_label)
         elif a.ordered:
             bench_ordered(n, emit, a.samples, library=a.library_label)
@@ -421,7 +499,7 @@ def main():
             bench_lods(n, emit, a.samples, library=a.library_label)
         else:
             bench(n, emit, a.samples, library=a.library_label)
-    if not (a.ordered or a.lods or a.views):
+    if not (a.ordered or a.lods or a.views or a.sharded):
         bench_several(emit, a.samples, library=a.library_label)
 
 
