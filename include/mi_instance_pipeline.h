@@ -571,14 +571,65 @@ int32_t mip_batch_draws_lods(MipContext* ctx, const MipFrame* frame, const uint3
  * returns MIP_ERR_CAPACITY and writes nothing. DRAW_INDEX has the limits of mip_batch_draws_lods.
  * ERRORS: an unknown order is MIP_ERR_INVALID_ARGUMENT. Every other error, the ordering on the stream behind the frame issued
  * last, the scratch per frame slot and the out-of-scope list are mip_batch_draws_lods's. A refused call writes nothing.
- * OUT OF SCOPE, besides that list: an order ACROSS buckets (one globally depth-sorted per-instance list); view-space depth
- * (the metric is the radial distance the LOD rule already forms, not the distance along the view direction); sharded
- * scenes, mip_run_many and the per-triangle stage. */
+ * OUT OF SCOPE, besides that list: sharded scenes, mip_run_many and the per-triangle stage. An order ACROSS buckets and a depth
+ * along the view direction are mip_batch_draws_sorted's (below). */
 #define MIP_BATCH_ORDER_DRAW_INDEX 0u  /* mip_batch_draws_lods, byte for byte */
 #define MIP_BATCH_ORDER_NEAR_FIRST 1u
 #define MIP_BATCH_ORDER_FAR_FIRST  2u
 int32_t mip_batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap,
                                 const MipLodPolicy* policy, uint32_t order, const MipBatchOutputs* out);
+
+/* ---- Extension: globally depth-sorted batched draws ---------------------------------------------------------------------
+ * The transparent pass: the members of mip_batch_draws_lods in ONE depth order across all buckets, and one instanced command
+ * per maximal RUN of neighbouring slots that draw the same bucket. A scene with several blended meshes is drawn back to front
+ * across meshes (FAR_FIRST), or front to back (NEAR_FIRST), by vkCmdDrawIndexedIndirectCount(batch_cmds, batch_count) as the
+ * other batches are. NOT a reference behaviour; checked against this repository's restatement (tests/sorted_restatement.py),
+ * byte for byte.
+ *
+ * MEMBERS, LOD, BUCKET: exactly mip_batch_draws_lods for the same ctx, frame, bitmap and policy: the members, every member's
+ * lod and its bucket lod_base[mesh_id] + lod. instance_count holds the bytes that call writes.
+ * DEPTH KEY of instance i, in float32 with contraction off, every product and sum rounded once:
+ *   MIP_DEPTH_RADIAL:    d = cam_pos - pos; q = (d.x*d.x + d.y*d.y) + d.z*d.z          (the q of the selection rule)
+ *                        U = 0x7F800000 if q is NaN, else bits(q);                      Umax = 0x7F800000
+ *   MIP_DEPTH_VIEW_AXIS: e = pos - cam_pos; z = (e.x*axis.x + e.y*axis.y) + e.z*axis.z  (axis = MipSortPolicy.axis)
+ *                        if z is NaN: U = 0xFF800000 (as +inf); otherwise
+ *                        u = 0 if z == 0 (either zero), else bits(z)
+ *                        U = u ^ 0x80000000 if the sign bit of u is clear, else ~u;     Umax = 0xFF800000
+ * U is monotone (non-decreasing) in q and in z; under VIEW_AXIS it lies in [0x007FFFFF (-inf), 0xFF800000 (+inf)]. `axis`
+ * need not be a unit vector: z is then the distance times its length. A zero axis gives z = 0 for every finite e.
+ *   s = 32 - depth_bits;  K = U >> s
+ *   D = K                MIP_BATCH_ORDER_NEAR_FIRST
+ *   D = (Umax >> s) - K  MIP_BATCH_ORDER_FAR_FIRST
+ * depth_bits = 16 keeps the sign, the exponent and 7 mantissa bits (a step of about 0.4 % in distance under RADIAL), 24 keeps
+ * 15 mantissa bits, 32 the whole float. With RADIAL and depth_bits = 16, D is exactly the D of mip_batch_draws_ordered. No D
+ * equals 0xFFFFFFFF. A member whose depth is NaN sorts with +inf: last under NEAR_FIRST, first under FAR_FIRST.
+ * SLOTS: the members sorted by (D, draw index), ascending. Equal D keeps draw order: the sort is stable. instance_ids[s] =
+ * first_instance_base + the instance of slot s; batch_model[s] (optional) = the 64 bytes mip_run's `model` holds for that
+ * instance, as mip_batch_draws_ordered stores them. Nothing at or behind `members` is touched.
+ * COMMANDS: b(s) is the bucket of the member in slot s. Slot s is a HEAD if s == 0 or b(s) != b(s-1). Command r belongs to the
+ * r-th head, in slot order, packed from entry 0: indexCount, firstIndex and vertexOffset are the ones mip_batch_draws_lods
+ * writes for bucket b(head); firstInstance = the head's slot; instanceCount = the distance to the next head, or to `members`
+ * for the last head. *batch_count = the number of heads. batch_cmds needs room for N commands: a well-mixed scene has nearly
+ * as many runs as members. Entries at or behind *batch_count are not touched. N = 0 writes the two zeros.
+ * ORDERING, SCRATCH, ERRORS: the stream behind the frame issued last, the scratch per frame slot and the errors are
+ * mip_batch_draws_ordered's. Also MIP_ERR_INVALID_ARGUMENT: a NULL sort, a wrong MipSortPolicy.struct_size, an unknown
+ * metric, an order other than NEAR_FIRST / FAR_FIRST (DRAW_INDEX is refused: that is mip_batch_draws_lods), depth_bits not in
+ * {16, 24, 32}, a non-finite axis component under VIEW_AXIS (RADIAL ignores axis). The bucket is not part of the key, so there
+ * is no 65 536-bucket limit: the bucket limits are those of mip_batch_draws_lods. A refused call writes nothing.
+ * OUT OF SCOPE: views, shards, mip_run_many and recorded graphs; a command capacity below N with an overflow status; the
+ * per-triangle stage. */
+#define MIP_DEPTH_RADIAL    0u  /* q, the squared distance the LOD rule forms */
+#define MIP_DEPTH_VIEW_AXIS 1u  /* signed distance along a caller's axis */
+typedef struct MipSortPolicy {
+  uint32_t struct_size;   /* = sizeof(MipSortPolicy), 28 */
+  uint32_t metric;        /* MIP_DEPTH_* */
+  uint32_t order;         /* MIP_BATCH_ORDER_NEAR_FIRST | MIP_BATCH_ORDER_FAR_FIRST */
+  uint32_t depth_bits;    /* 16, 24 or 32: the leading bits of the key that are sorted */
+  float axis[3];          /* VIEW_AXIS: the view direction, need not be unit; ignored by RADIAL */
+} MipSortPolicy;
+
+int32_t mip_batch_draws_sorted(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap,
+                               const MipLodPolicy* policy, const MipSortPolicy* sort, const MipBatchOutputs* out);
 
 /* ---- Extension: batched draws for several views in one call -----------------------------------------------------------
  * mip_batch_draws_lods for n_views views of the resident instances — the lights of a shadow pass, cascades, cube faces,

@@ -125,6 +125,21 @@ pub const MIP_BATCH_ORDER_DRAW_INDEX: u32 = 0;
 pub const MIP_BATCH_ORDER_NEAR_FIRST: u32 = 1;
 pub const MIP_BATCH_ORDER_FAR_FIRST: u32 = 2;
 
+/// The depth metric of mip_batch_draws_sorted.
+pub const MIP_DEPTH_RADIAL: u32 = 0;
+pub const MIP_DEPTH_VIEW_AXIS: u32 = 1;
+
+/// The depth key of mip_batch_draws_sorted: metric, order (NEAR_FIRST / FAR_FIRST), the leading bits that are sorted (16, 24 or
+/// 32) and, for MIP_DEPTH_VIEW_AXIS, the view direction.
+#[repr(C)]
+pub struct MipSortPolicy {
+    pub struct_size: u32,
+    pub metric: u32,
+    pub order: u32,
+    pub depth_bits: u32,
+    pub axis: [f32; 3],
+}
+
 /// What a shard's batch chunk starts with (mip_batch_draws_shard / mip_merge_batches): then `n_buckets` counts, zero words up
 /// to a multiple of 16 bytes, and the ids.
 #[repr(C)]
@@ -211,6 +226,9 @@ extern "C" {
     /// Extension: mip_batch_draws_lods with the members of every bucket nearest first or farthest first (MIP_BATCH_ORDER_*).
     pub fn mip_batch_draws_ordered(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32,
                                    policy: *const MipLodPolicy, order: u32, out: *const MipBatchOutputs) -> i32;
+    /// Extension: the members of mip_batch_draws_lods in one depth order across all buckets, one command per run of equal bucket.
+    pub fn mip_batch_draws_sorted(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32,
+                                  policy: *const MipLodPolicy, sort: *const MipSortPolicy, out: *const MipBatchOutputs) -> i32;
     /// Extension: mip_batch_draws_lods for up to MIP_MAX_VIEWS views in one call; `visible_bitmaps` is a host array of
     /// `n_views` device pointers (null: every resident instance).
     pub fn mip_batch_draws_views(ctx: *mut MipContext, frames: *const MipFrame, visible_bitmaps: *const *const u32,
@@ -232,6 +250,7 @@ const _: () = assert!(std::mem::size_of::<MipDrawIndexedIndirectCommand>() == 20
 // the extension structs, as array lengths (a mismatch is a type error)
 const _: [u8; 48] = [0; std::mem::size_of::<MipBatchOutputs>()];
 const _: [u8; 28] = [0; std::mem::size_of::<MipLodPolicy>()];
+const _: [u8; 28] = [0; std::mem::size_of::<MipSortPolicy>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipViewBatchOutputs>()];
 const _: [u8; 16] = [0; std::mem::size_of::<MipBatchChunkHeader>()];
 

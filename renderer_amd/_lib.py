@@ -44,6 +44,8 @@ MIP_LOD_RELATIVE = 1
 MIP_BATCH_ORDER_DRAW_INDEX = 0
 MIP_BATCH_ORDER_NEAR_FIRST = 1
 MIP_BATCH_ORDER_FAR_FIRST = 2
+MIP_DEPTH_RADIAL = 0
+MIP_DEPTH_VIEW_AXIS = 1
 MIP_MAX_BATCH_CHUNKS = 64
 MIP_BATCH_CHUNK_HEADER_BYTES = 16
 
@@ -51,7 +53,7 @@ MIP_BATCH_CHUNK_HEADER_BYTES = 16
 EXPORTS = (
     "mip_abi_version", "mip_create", "mip_destroy", "mip_set_mesh_table", "mip_set_instances",
     "mip_set_instances_device", "mip_update_instances", "mip_set_geometry", "mip_set_blas_addresses", "mip_run", "mip_run_many", "mip_wait", "mip_merge_draw_lists", "mip_merge_wire_lists", "mip_merge_wire_lists_packed", "mip_wire_index_bits", "mip_light_draw_lists", "mip_set_skeleton", "mip_set_poses", "mip_run_skinned", "mip_run_views", "mip_comm_unique_id", "mip_comm_init", "mip_comm_destroy", "mip_run_sharded", "mip_import_external_fd", "mip_release_external", "mip_import_external_semaphore_fd", "mip_external_semaphore_on_device", "mip_wait_external", "mip_signal_external", "mip_release_external_semaphore", "mip_last_error",
-    "mip_get_timings", "mip_depth_pyramid_bytes", "mip_build_depth_pyramid", "mip_run_occluded", "mip_batch_draws", "mip_batch_draws_lods", "mip_batch_draws_ordered", "mip_batch_draws_views", "mip_batch_draws_shard", "mip_merge_batches", "mip_reset_timings", "mip_instance_count",
+    "mip_get_timings", "mip_depth_pyramid_bytes", "mip_build_depth_pyramid", "mip_run_occluded", "mip_batch_draws", "mip_batch_draws_lods", "mip_batch_draws_ordered", "mip_batch_draws_sorted", "mip_batch_draws_views", "mip_batch_draws_shard", "mip_merge_batches", "mip_reset_timings", "mip_instance_count",
 )
 
 
@@ -167,6 +169,17 @@ class MipLodPolicy(C.Structure):
         ("struct_size", C.c_uint32),
         ("mode", C.c_uint32),
         ("switch_sq", C.c_float * (MIP_MAX_LODS - 1)),
+    ]
+
+
+class MipSortPolicy(C.Structure):
+    """mip_batch_draws_sorted's depth key (include/mi_instance_pipeline.h): metric, order, depth_bits and the view axis, 28 B."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("metric", C.c_uint32),
+        ("order", C.c_uint32),
+        ("depth_bits", C.c_uint32),
+        ("axis", C.c_float * 3),
     ]
 
 
@@ -295,6 +308,7 @@ def load_library():
     _declare_newer(lib, "mip_batch_draws", [vp, vp, vp, vp])
     _declare_newer(lib, "mip_batch_draws_lods", [vp, vp, vp, vp, vp])
     _declare_newer(lib, "mip_batch_draws_ordered", [vp, vp, vp, vp, C.c_uint32, vp])
+    _declare_newer(lib, "mip_batch_draws_sorted", [vp, vp, vp, vp, vp, vp])
     _declare_newer(lib, "mip_batch_draws_views", [vp, vp, vp, C.c_uint32, vp, vp])
     _declare_newer(lib, "mip_batch_draws_shard", [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32])
     _declare_newer(lib, "mip_merge_batches", [vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, vp])

@@ -6,12 +6,16 @@
 // mip_batch_draws_views is mip_batch_draws_lods for several views in one call: key = view * B + bucket, one shared instance_ids.
 // mip_batch_draws_shard is mip_batch_draws_lods for one shard of a sharded scene: ids and dense bucket counts into a chunk;
 // mip_merge_batches merges the all-gathered chunks into the bytes of the unsharded call (batch_merge_kernel.hpp).
-// One stage (batch_kernel.hpp) under the key policies of the four entry points (batch_kernel.hpp, batch_lods_kernel.hpp,
-// batch_views_kernel.hpp); batch_plan.hpp says which instantiation a call launches. The kernels are instantiated here and only here.
+// mip_batch_draws_sorted sorts the members of mip_batch_draws_lods by depth across buckets (key = D alone) and writes one
+// command per run of equal bucket in the sorted slots (batch_sorted_kernel.hpp: the key policy and the run stage).
+// One stage (batch_kernel.hpp) under the key policies of the entry points (batch_kernel.hpp, batch_lods_kernel.hpp,
+// batch_views_kernel.hpp, batch_sorted_kernel.hpp); batch_plan.hpp says which instantiation a call launches. The kernels are instantiated here and only here.
 #include "context.hpp"
 #include "batch_views_kernel.hpp"
+#include "batch_sorted_kernel.hpp"
 #include "batch_merge_kernel.hpp"
 
+static_assert(sizeof(MipSortPolicy) == 28, "MipSortPolicy is part of the ABI");
 static_assert(sizeof(MipViewBatchOutputs) == 48, "MipViewBatchOutputs is part of the ABI");
 static_assert(sizeof(MipBatchChunkHeader) == mip::kBatchChunkHeaderWords * 4 && MIP_MAX_BATCH_CHUNKS == mip::kMaxBatchChunks,
               "the batch chunk: header and kernels agree");
@@ -95,6 +99,18 @@ const void* kernel_address(mip::BatchKernel k) {
     case K::scatter_views_list_last: return (const void*)mip_batch_scatter_kernel<BatchViewsListKey, true, 0>;
     case K::commands_views: return (const void*)mip_batch_view_commands_kernel;
     case K::commands_shard: return (const void*)mip_batch_shard_chunk_kernel;
+    case K::count_sorted_distance_radial: return (const void*)mip_batch_count_kernel<BatchSortedKey<MIP_LOD_DISTANCE, MIP_DEPTH_RADIAL>>;
+    case K::count_sorted_distance_axis: return (const void*)mip_batch_count_kernel<BatchSortedKey<MIP_LOD_DISTANCE, MIP_DEPTH_VIEW_AXIS>>;
+    case K::count_sorted_relative_radial: return (const void*)mip_batch_count_kernel<BatchSortedKey<MIP_LOD_RELATIVE, MIP_DEPTH_RADIAL>>;
+    case K::count_sorted_relative_axis: return (const void*)mip_batch_count_kernel<BatchSortedKey<MIP_LOD_RELATIVE, MIP_DEPTH_VIEW_AXIS>>;
+    case K::scatter_sorted_distance_radial_mid: return (const void*)mip_batch_scatter_kernel<BatchSortedKey<MIP_LOD_DISTANCE, MIP_DEPTH_RADIAL>, false, 0>;
+    case K::scatter_sorted_distance_axis_mid: return (const void*)mip_batch_scatter_kernel<BatchSortedKey<MIP_LOD_DISTANCE, MIP_DEPTH_VIEW_AXIS>, false, 0>;
+    case K::scatter_sorted_relative_radial_mid: return (const void*)mip_batch_scatter_kernel<BatchSortedKey<MIP_LOD_RELATIVE, MIP_DEPTH_RADIAL>, false, 0>;
+    case K::scatter_sorted_relative_axis_mid: return (const void*)mip_batch_scatter_kernel<BatchSortedKey<MIP_LOD_RELATIVE, MIP_DEPTH_VIEW_AXIS>, false, 0>;
+    case K::sorted_members: return (const void*)mip_batch_sorted_members_kernel;
+    case K::run_heads: return (const void*)mip_batch_run_heads_kernel;
+    case K::run_commands: return (const void*)mip_batch_run_commands_kernel;
+    case K::run_counts: return (const void*)mip_batch_run_counts_kernel;
   }
   return nullptr;
 }
@@ -165,6 +181,7 @@ void batch_release(MipContext* ctx) {
     }
     (void)hipFree(bs.d_bucket_hist);
     (void)hipFree(bs.d_slot_of);
+    (void)hipFree(bs.d_bucket_of);
   }
   ctx->batch.clear();
   release_view_scratch(ctx->view_batch);
@@ -302,6 +319,107 @@ int32_t check_policy(MipContext* ctx, const MipLodPolicy* policy) {
     if (k && t < policy->switch_sq[k - 1]) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "switch_sq[%u] = %g decreases", k, (double)t);
   }
   return MIP_OK;
+}
+
+// MipSortPolicy as the header states it
+int32_t check_sort(MipContext* ctx, const MipSortPolicy* sort) {
+  if (!sort) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "sort is NULL");
+  if (sort->struct_size != sizeof(MipSortPolicy))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipSortPolicy.struct_size %u != %zu", sort->struct_size, sizeof(MipSortPolicy));
+  if (sort->metric != MIP_DEPTH_RADIAL && sort->metric != MIP_DEPTH_VIEW_AXIS)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipSortPolicy.metric %u", sort->metric);
+  if (sort->order != MIP_BATCH_ORDER_NEAR_FIRST && sort->order != MIP_BATCH_ORDER_FAR_FIRST)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipSortPolicy.order %u is neither NEAR_FIRST nor FAR_FIRST", sort->order);
+  if (sort->depth_bits != 16u && sort->depth_bits != 24u && sort->depth_bits != 32u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipSortPolicy.depth_bits %u is not 16, 24 or 32", sort->depth_bits);
+  if (sort->metric == MIP_DEPTH_VIEW_AXIS)
+    for (uint32_t k = 0; k < 3; ++k)
+      if (!std::isfinite(sort->axis[k])) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipSortPolicy.axis[%u] = %g is not finite", k, (double)sort->axis[k]);
+  return MIP_OK;
+}
+
+// mip_batch_draws_sorted: the stage of batch_draws() under BatchSortedKey — depth_bits / 8 passes over D alone, the members sum
+// in the command writer's place — then the run stage over the final slots, then the matrices through slot_of.
+int32_t batch_draws_sorted(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                           const MipSortPolicy* sort, const MipBatchOutputs* out) {
+  if (int32_t rc = check_call(ctx, frame, visible_bitmap, out)) return rc;
+  const uint32_t slot = ctx->last_slot;
+  hipStream_t stream = ctx->slots[slot].stream;
+  const uint32_t n = ctx->n;
+  const unsigned long long buckets = ctx->lod_buckets;
+  if (buckets > 0x80000000ull || ctx->m > 0x20000000u)
+    return fail(ctx, MIP_ERR_CAPACITY, "%u meshes, %llu buckets: a bucket does not fit a 32-bit word", ctx->m, buckets);
+  const bool async = (out->flags & MIP_OUT_ASYNC) != 0;
+  if (n == 0 || buckets == 0) {  // nothing to sort: two zeros
+    MIP_HIP(ctx, hipMemsetAsync(out->batch_count, 0, 4, stream));
+    if (out->instance_count) MIP_HIP(ctx, hipMemsetAsync(out->instance_count, 0, 4, stream));
+    return finish(ctx, stream, async);
+  }
+  const bool general = ctx->nonfinite_instances != 0 || ctx->force_general;
+  const bool axis = sort->metric == MIP_DEPTH_VIEW_AXIS;
+  const mip::BatchPlan plan = mip::plan_batch_sorted(policy->mode == MIP_LOD_RELATIVE, axis, sort->depth_bits, out->batch_model != nullptr, general);
+  if (ctx->batch.size() != ctx->slots.size()) ctx->batch.resize(ctx->slots.size());
+  MipContext::BatchScratch& bs = ctx->batch[slot];
+  if (int32_t rc = ensure_scratch(ctx, bs, true, out->batch_model != nullptr)) return rc;
+  if (!bs.d_bucket_of) MIP_HIP(ctx, hipMalloc(&bs.d_bucket_of, instance_cap(ctx) * 4));
+
+  mip::SortedBatchArgs a{};
+  a.chain = ctx->d_mesh_chain;
+  a.bucket_lod = ctx->d_bucket_lod;
+  std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
+  a.depth_shift = 32u - sort->depth_bits;
+  a.depth_flip = sort->order == MIP_BATCH_ORDER_FAR_FIRST ? (axis ? mip::kSortedUmaxAxis : mip::kSortedUmaxRadial) >> a.depth_shift : 0u;
+  if (axis) std::memcpy(a.axis, sort->axis, sizeof a.axis);
+  a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
+  a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
+  a.bitmap = visible_bitmap;
+  a.n = n;
+  a.n_tiles = batch_tiles_for(n);
+  a.n_buckets = (uint32_t)buckets;
+  a.n_bins = mip::kBatchBins;
+  a.first_instance_base = frame->first_instance_base;
+  std::memcpy(a.cam, frame->cam_pos, sizeof a.cam);
+  a.counts = bs.d_counts;
+  a.members = a.members_out = bs.d_totals + mip::kBatchMaxPasses * mip::kBatchBins;
+  a.batch_cmds = static_cast<uint32_t*>(out->batch_cmds);
+  a.batch_count = out->batch_count;
+  a.instance_count = out->instance_count;
+#ifdef MIP_DEBUG_STAMPS
+  DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);
+#endif
+
+  for (uint32_t p = 0; p < plan.passes; ++p) {
+    const bool last = p + 1 == plan.passes;
+    a.shift = p * mip::kBatchDigitBits;
+    a.totals = bs.d_totals + p * mip::kBatchBins;
+    a.keys_in = p ? bs.d_keys[(p - 1) & 1u] : nullptr;
+    a.ids_in = p ? bs.d_ids[(p - 1) & 1u] : nullptr;
+    a.keys_out = last ? nullptr : bs.d_keys[p & 1u];
+    a.ids_out = last ? nullptr : bs.d_ids[p & 1u];
+    a.instance_ids = last ? out->instance_ids : nullptr;
+    a.slot_of = (last && out->batch_model) ? bs.d_slot_of : nullptr;
+    a.bucket_out = p == 0 ? bs.d_bucket_of : nullptr;  // the count of pass 0 stores the buckets; its scatter does not store them again
+    if (int32_t rc = launch(ctx, plan.count(p), a.n_tiles, stream, a)) return rc;
+    a.bucket_out = nullptr;
+    if (int32_t rc = launch(ctx, mip::BatchKernel::rowscan, a.n_bins, stream, a)) return rc;
+    if (p == 0)  // the scan's epilogue: the digit totals -> the list's length and instance_count
+      if (int32_t rc = launch(ctx, plan.commands, 1, stream, a)) return rc;
+    if (int32_t rc = launch(ctx, plan.scatter(p), a.n_tiles, stream, a)) return rc;
+  }
+  // the run stage: the tile rows reuse `counts` (row 0), the slots' buckets a list buffer the last pass did not read, and the
+  // row's sum — the number of heads — is batch_count
+  a.bucket_in = bs.d_bucket_of;
+  a.slot_bucket = bs.d_keys[(plan.passes - 1) & 1u];
+  a.totals = out->batch_count;
+  for (uint32_t k = 0; k < mip::kBatchRunStageLaunches; ++k) {
+    const mip::BatchKernel kernel = mip::batch_run_stage(k);
+    if (int32_t rc = launch(ctx, kernel, kernel == mip::BatchKernel::rowscan ? 1u : a.n_tiles, stream, a)) return rc;
+  }
+  if (plan.model != mip::BatchKernel::none) {
+    a.batch_model = static_cast<float4*>(out->batch_model);
+    if (int32_t rc = launch(ctx, plan.model, a.n_tiles, stream, a)) return rc;
+  }
+  return finish(ctx, stream, async);
 }
 
 // mip_batch_draws_views: every check first (a refused call writes nothing), then one sort of the n_views x N (instance, view)
@@ -488,6 +606,14 @@ int32_t mip_batch_draws_ordered(MipContext* ctx, const MipFrame* frame, const ui
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown order %u", order);
   if (int32_t rc = check_policy(ctx, policy)) return rc;
   return batch_draws(ctx, frame, visible_bitmap, policy, order, out);
+}
+
+int32_t mip_batch_draws_sorted(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                               const MipSortPolicy* sort, const MipBatchOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_sort(ctx, sort)) return rc;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  return batch_draws_sorted(ctx, frame, visible_bitmap, policy, sort, out);
 }
 
 int32_t mip_batch_draws_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps, uint32_t n_views,

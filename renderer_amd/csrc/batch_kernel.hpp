@@ -33,7 +33,8 @@
 //
 // BatchPickLodKey (mip_batch_draws) and BatchListKey (the later passes of any several-pass sort) are below; the policies over
 // the whole LOD chain (mip_batch_draws_lods, mip_batch_draws_ordered) are in batch_lods_kernel.hpp, the policy over several
-// views (mip_batch_draws_views) and its command writer in batch_views_kernel.hpp. The command writer takes a
+// views (mip_batch_draws_views) and its command writer in batch_views_kernel.hpp, the policy that sorts by depth across
+// buckets (mip_batch_draws_sorted) and the run stage behind it in batch_sorted_kernel.hpp. The command writer takes a
 // policy of its own: how a bucket maps to (indexCount, firstIndex, vertexOffset). Instantiated in api_batch.hip only.
 #pragma once
 

@@ -1,6 +1,8 @@
 // batch_plan.hpp — which kernels a batched-draws call launches: a pure function of the entry point, the policy's mode, the
-// bucket count, whether matrices are wanted and the census decision. Plain C++, no HIP: enumerated on the CPU by
-// tests/native/batch_plan_check.cpp. api_batch.hip maps a BatchKernel to its instantiation and executes the plan.
+// bucket count, whether matrices are wanted and the census decision (plan_batch), or, for mip_batch_draws_sorted, of the mode,
+// the depth metric, depth_bits, whether matrices are wanted and the census decision (plan_batch_sorted). Plain C++, no HIP:
+// enumerated on the CPU by tests/native/batch_plan_check.cpp and tests/native/batch_sorted_plan_check.cpp. api_batch.hip maps
+// a BatchKernel to its instantiation and executes the plan.
 #pragma once
 
 #include <cstdint>
@@ -12,8 +14,9 @@ constexpr uint32_t kBatchMaxPasses = 4;
 constexpr uint32_t kBatchDepthBits = 16;  // D's field of the ordered key (batch_lods_kernel.hpp)
 static_assert(kBatchMaxPasses * kBatchDigitBits >= 32, "a 32-bit key takes at most kBatchMaxPasses digits");
 
-// mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered (NEAR / FAR), mip_batch_draws_views, mip_batch_draws_shard
-enum class BatchEntry : uint32_t { draws, lods, ordered, views, shard };
+// mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered (NEAR / FAR), mip_batch_draws_views, mip_batch_draws_shard,
+// mip_batch_draws_sorted (planned by plan_batch_sorted, not plan_batch)
+enum class BatchEntry : uint32_t { draws, lods, ordered, views, shard, sorted };
 
 // Every instantiation of the stage (batch_kernel.hpp), by key policy. scatter: `mid` = a pass of several, `last` = the one
 // pass, ids only, `model` / `general` = the one pass with matrices (census-selected / general arithmetic).
@@ -35,6 +38,11 @@ enum class BatchKernel : uint32_t {
   // mip_batch_draws_shard (batch_merge_kernel.hpp): mip_batch_draws_lods' count / rowscan / scatter with the ids going to the
   // chunk; the epilogue that writes the dense bucket counts and the chunk header in the command writer's place
   commands_shard,
+  // mip_batch_draws_sorted (batch_sorted_kernel.hpp): pass 0 under the depth key, by LOD mode and depth metric; the sum that
+  // gives the list its length in the command writer's place; the run stage behind the last scatter
+  count_sorted_distance_radial, count_sorted_distance_axis, count_sorted_relative_radial, count_sorted_relative_axis,
+  scatter_sorted_distance_radial_mid, scatter_sorted_distance_axis_mid, scatter_sorted_relative_radial_mid, scatter_sorted_relative_axis_mid,
+  sorted_members, run_heads, run_commands, run_counts,
 };
 
 struct BatchPlan {
@@ -98,6 +106,35 @@ constexpr BatchPlan plan_batch(BatchEntry entry, bool relative, unsigned long lo
   // membership does not depend on the order: the ordered path stores matrices with the chain policy's model kernel
   p.model = p.several() && want_model ? model[row][general ? 1 : 0] : K::none;
   return p;
+}
+
+// mip_batch_draws_sorted: the key is D alone, depth_bits (16, 24 or 32) wide, so the sort always takes several passes and the
+// matrices go through slot_of with the chain policy's model kernel (membership does not depend on the order). `commands` is
+// the sum of pass 0's digit totals: no bucket is counted. `axis`: the metric is MIP_DEPTH_VIEW_AXIS, else MIP_DEPTH_RADIAL.
+constexpr BatchPlan plan_batch_sorted(bool relative, bool axis, uint32_t depth_bits, bool want_model, bool general) {
+  using K = BatchKernel;
+  constexpr K count[2][2] = {{K::count_sorted_distance_radial, K::count_sorted_distance_axis},
+                             {K::count_sorted_relative_radial, K::count_sorted_relative_axis}};
+  constexpr K scatter[2][2] = {{K::scatter_sorted_distance_radial_mid, K::scatter_sorted_distance_axis_mid},
+                               {K::scatter_sorted_relative_radial_mid, K::scatter_sorted_relative_axis_mid}};
+  BatchPlan p{};
+  p.passes = depth_bits / kBatchDigitBits;
+  p.count0 = count[relative][axis];
+  p.scatter0 = scatter[relative][axis];
+  p.commands = K::sorted_members;
+  p.list_last = K::scatter_list_last;
+  p.model = !want_model ? K::none
+            : relative  ? (general ? K::model_chain_relative_general : K::model_chain_relative)
+                        : (general ? K::model_chain_distance_general : K::model_chain_distance);
+  return p;
+}
+
+// The run stage of mip_batch_draws_sorted, in launch order, behind the last scatter (and in front of the model kernel):
+// per-tile head counts, their scan over the tiles (one row), the heads' commands, instanceCount of every command.
+constexpr uint32_t kBatchRunStageLaunches = 4;
+constexpr BatchKernel batch_run_stage(uint32_t i) {
+  constexpr BatchKernel k[kBatchRunStageLaunches] = {BatchKernel::run_heads, BatchKernel::rowscan, BatchKernel::run_commands, BatchKernel::run_counts};
+  return k[i];
 }
 
 }  // namespace mip

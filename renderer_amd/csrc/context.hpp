@@ -102,6 +102,7 @@ struct MipContext {
     uint32_t* d_ids[2] = {nullptr, nullptr};
     uint32_t* d_bucket_hist = nullptr;  //   members per bucket, MIP_MAX_LODS x max_meshes words
     uint32_t* d_slot_of = nullptr;      //   slot of every member by instance (batch_model)
+    uint32_t* d_bucket_of = nullptr;    // mip_batch_draws_sorted: bucket of every member by instance (the run stage)
   };
   std::vector<BatchScratch> batch;
   // mip_batch_draws_views (api_batch.hip): the call's own scratch on the first stream, allocated at first use for the

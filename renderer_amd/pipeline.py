@@ -6,8 +6,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipTimings,
-                   MipViewBatchOutputs)
+from ._lib import (MipBatchOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+                   MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
     [
@@ -109,6 +109,23 @@ def make_lod_policy(mode, switch_sq):
     p.struct_size = C.sizeof(MipLodPolicy)
     p.mode = int(mode)
     p.switch_sq[:] = sw
+    return p
+
+
+def make_sort_policy(metric, order, depth_bits=16, axis=(0.0, 0.0, 0.0)):
+    """A MipSortPolicy for batch_draws_sorted: metric MIP_DEPTH_RADIAL / MIP_DEPTH_VIEW_AXIS (or "radial" / "view_axis"), order
+    MIP_BATCH_ORDER_NEAR_FIRST / FAR_FIRST (or "near_first" / "far_first"), depth_bits 16, 24 or 32 (the leading bits of the
+    depth that are sorted) and, for VIEW_AXIS, the view direction (need not be unit). The library checks the values."""
+    if isinstance(metric, str):
+        metric = {"radial": _lib.MIP_DEPTH_RADIAL, "view_axis": _lib.MIP_DEPTH_VIEW_AXIS}[metric]
+    if isinstance(order, str):
+        order = {"near_first": _lib.MIP_BATCH_ORDER_NEAR_FIRST, "far_first": _lib.MIP_BATCH_ORDER_FAR_FIRST}[order]
+    p = MipSortPolicy()
+    p.struct_size = C.sizeof(MipSortPolicy)
+    p.metric = int(metric)
+    p.order = int(order)
+    p.depth_bits = int(depth_bits)
+    p.axis[:] = [float(v) for v in np.asarray(axis, dtype=np.float32).reshape(3)]
     return p
 
 
@@ -524,6 +541,23 @@ class InstancePipeline:
         out.batch_model = batch_model or None
         self._check(self._lib.mip_batch_draws_ordered(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                       int(order), C.addressof(out)))
+
+    def batch_draws_sorted(self, frame, visible_bitmap_ptr, policy, sort, *, batch_cmds, batch_count, instance_ids, instance_count=0,
+                           batch_model=0, async_=False):
+        """mip_batch_draws_sorted: the members of batch_draws_lods in one depth order across all buckets (`sort` from
+        make_sort_policy: radial or view-axis depth, near or far first, 16 / 24 / 32 key bits; ties in draw order) and one
+        instanced command per run of neighbouring slots that draw the same bucket — the transparent pass. batch_cmds needs room
+        for N commands; everything else as batch_draws_ordered."""
+        out = MipBatchOutputs()
+        out.struct_size = C.sizeof(MipBatchOutputs)
+        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+        out.batch_cmds = batch_cmds or None
+        out.batch_count = batch_count or None
+        out.instance_ids = instance_ids or None
+        out.instance_count = instance_count or None
+        out.batch_model = batch_model or None
+        self._check(self._lib.mip_batch_draws_sorted(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                     C.addressof(sort), C.addressof(out)))
 
     def batch_draws_views(self, frames, visible_bitmap_ptrs, policy, *, batch_cmds, cmd_stride, batch_counts, instance_ids,
                           view_first_slot=0, async_=False):

@@ -39,6 +39,12 @@ draw lists. No all-gather is timed: no box with more than one GPU.
 
   python tools/batch_bench.py --sharded [--out profiles/batch_merge_bench.jsonl]
 
+--sorted: the globally depth-sorted stage (mip_batch_draws_sorted, FAR_FIRST: RADIAL at 16, 24 and 32 key bits, VIEW_AXIS at 32)
+beside mip_batch_draws_ordered FAR_FIRST of the same build and policy, each with ids only and with batch_model. The run stage
+alone is not a leg: its four kernels are read from a kernel trace of this leg (rocprofv3 --kernel-trace --stats).
+
+  python tools/batch_bench.py --sorted [--out profiles/batch_sorted_bench.jsonl]
+
 --parent-library PATH (any of the first four): the SAME legs on another build of the library (the parent commit's) as the yardstick,
 in the same session. A library is loaded once per process, so the tool then only starts children of itself, one after the
 other: the parent build, this build, the parent build again. Every row says which (`library`); the two parent runs give each
@@ -298,6 +304,58 @@ def bench_ordered(n, emit, samples=40, library="this build"):
         p.close()
 
 
+def bench_sorted(n, emit, samples=40, library="this build"):
+    import numpy as np
+    import torch
+
+    import renderer_amd
+    from renderer_amd import _lib, scene
+    from renderer_amd.pipeline import make_frame, make_lod_policy, make_sort_policy
+
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.Stream()
+    config = 2 if n <= 100_000 else 3
+    s = scene.make_scene(config, n=n)
+    m = len(s["meshes"])
+    buckets = int(s["meshes"]["n_lods"].sum())
+    with torch.cuda.stream(st):
+        p = renderer_amd.InstancePipeline(n, m, stream=st.cuda_stream)
+        p.set_mesh_table(s["meshes"])
+        p.set_instances(s["pos"], s["rot"], s["scale"], s["mesh_id"])
+        bitmap = torch.zeros((n + 31) // 32 + 1, dtype=torch.int32, device=dev)
+        cmds = torch.empty((n, 5), dtype=torch.int32, device=dev)
+        scal = torch.zeros(8, dtype=torch.int32, device=dev)
+        b_cmds = torch.empty((n, 5), dtype=torch.int32, device=dev)   # a run per member at worst
+        b_ids = torch.empty(n, dtype=torch.int32, device=dev)
+        b_scal = torch.zeros(8, dtype=torch.int32, device=dev)
+        b_model = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        frame = p.frame_ref(make_frame(s["planes"], s["cam_pos"]))
+        p.run_prepared(frame, p.prepare_outputs(visible_bitmap=bitmap.data_ptr(), draw_cmds=cmds.data_ptr(), draw_count=scal.data_ptr(),
+                                                draw_index_total=scal.data_ptr() + 4))
+        p.wait()
+        ids_only = dict(batch_cmds=b_cmds.data_ptr(), batch_count=b_scal.data_ptr(), instance_ids=b_ids.data_ptr(),
+                        instance_count=b_scal.data_ptr() + 4, async_=True)
+        with_model = dict(ids_only, batch_model=b_model.data_ptr())
+        policy = make_lod_policy("distance", LODS_DISTANCE_SQ)
+        far = _lib.MIP_BATCH_ORDER_FAR_FIRST
+        axis = -np.asarray(s["cam_pos"], np.float32)   # towards the origin of the scene
+        legs = [("batch_draws_ordered FAR_FIRST", None)]
+        legs += [(f"batch_draws_sorted FAR_FIRST RADIAL {bits} bits", make_sort_policy("radial", far, bits)) for bits in (16, 24, 32)]
+        legs += [("batch_draws_sorted FAR_FIRST VIEW_AXIS 32 bits", make_sort_policy("view_axis", far, 32, axis))]
+        for name, sort in legs:
+            for outs, what in ((ids_only, "ids only"), (with_model, "with batch_model")):
+                if sort is None:
+                    fn = lambda: p.batch_draws_ordered(frame, bitmap.data_ptr(), policy, far, **outs)
+                else:
+                    fn = lambda: p.batch_draws_sorted(frame, bitmap.data_ptr(), policy, sort, **outs)
+                r = measure(st, fn, samples=samples)
+                p.wait()
+                emit(dict(leg=f"sorted: {name}, DISTANCE, {what}", library=library, n=n, config=config, meshes=m, buckets=buckets,
+                          batch_count=int(b_scal[0].item()), members=int(b_scal[1].item()), **r))
+        p.close()
+
+
 def view_frusta(planes, n_views):
     """A frustum per view: the scene's own and the same one turned about the axes (columns swapped, signs flipped)."""
     import numpy as np
@@ -466,6 +524,7 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     ap.add_argument("--lods", action="store_true", help="the mip_batch_draws_lods legs instead of (a) .. (s)")
     ap.add_argument("--ordered", action="store_true", help="the mip_batch_draws_ordered legs instead of (a) .. (s)")
+    ap.add_argument("--sorted", action="store_true", help="the mip_batch_draws_sorted legs beside mip_batch_draws_ordered instead of (a) .. (s)")
     ap.add_argument("--views", action="store_true", help="the mip_batch_draws_views legs (V = 4) and their yardsticks instead of (a) .. (s)")
     ap.add_argument("--sharded", action="store_true", help="mip_batch_draws_shard and mip_merge_batches over 8 shards, and their yardsticks")
     ap.add_argument("--parent-library", default=None, help="also run the same legs on this build of the library: the yardstick (child processes)")
@@ -483,7 +542,7 @@ def main():
         import subprocess
 
         cmd = [sys.executable, os.path.abspath(__file__)] + [str(n) for n in a.n] + ["--samples", str(a.samples)]
-        cmd += (["--lods"] if a.lods else []) + (["--ordered"] if a.ordered else []) + (["--views"] if a.views else []) + (["--out", a.out] if a.out else [])
+        cmd += (["--lods"] if a.lods else []) + (["--ordered"] if a.ordered else []) + (["--sorted"] if a.sorted else []) + (["--views"] if a.views else []) + (["--out", a.out] if a.out else [])
         parent = dict(os.environ, MIP_LIBRARY=os.path.abspath(a.parent_library))
         for label, env in (("parent commit, first run", parent), ("this build", os.environ), ("parent commit, last run", parent)):
             subprocess.run(cmd + ["--library-label", label], check=True, env=env)
@@ -495,11 +554,13 @@ def main():
             bench_views(n, emit, a.samples, library=a.library_label)
         elif a.ordered:
             bench_ordered(n, emit, a.samples, library=a.library_label)
+        elif a.sorted:
+            bench_sorted(n, emit, a.samples, library=a.library_label)
         elif a.lods:
             bench_lods(n, emit, a.samples, library=a.library_label)
         else:
             bench(n, emit, a.samples, library=a.library_label)
-    if not (a.ordered or a.lods or a.views or a.sharded):
+    if not (a.ordered or a.lods or a.sorted or a.views or a.sharded):
         bench_several(emit, a.samples, library=a.library_label)
 
 
