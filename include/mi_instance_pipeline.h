@@ -414,7 +414,9 @@ int32_t mip_run_views(MipContext* ctx, const MipFrame* frames, const MipOutputs*
  *   3. any clip coordinate non-finite, or any w <= 0: NOT occluded;
  *   4. r = 1.0f / w (correctly rounded), ndc = clip.xyz * r;
  *   5. u = (ndc.x*0.5f + 0.5f) * W, v = (0.5f - ndc.y*0.5f) * H   (the flipped viewport);
- *   6. x0..x1 = floor(min u), floor(max u) over the corners clamped to [0, W-1], y0..y1 the same on v, H;
+ *   6. x0..x1 = floor(min u), floor(max u) over the corners clamped to [0, W-1], y0..y1 the same on v, H; min and max
+ *      are fminf / fmaxf folds from +inf / -inf, so a NaN u or v (0 * inf, where w is so small that r overflows) is
+ *      ignored and +-inf takes the clamp; if every corner's is NaN the start values stand: x0 = W-1, x1 = 0;
  *   7. k = the smallest level with (x1>>(k+1)) - (x0>>(k+1)) <= 1 and the same for y;
  *   8. d = max of the (at most 4) level-k texels covering the rectangle;
  *   9. occluded iff d < 1.0f and min over corners of ndc.z > d (a texel at 1.0 — cleared — never occludes).

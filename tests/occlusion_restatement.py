@@ -34,10 +34,13 @@ def pyramid_flat(levels):
     return np.concatenate([l.reshape(-1) for l in levels]).astype(F32)
 
 
-def occluded(world_aabb, pv, levels, width, height):
-    """Steps 1-9 of the header's test for every box (n x 6: min xyz, max xyz): True = occluded by the pyramid (the frustum
-    test and the candidate set are the caller's). Same float32 operations in the same order as the kernel; min / max fold
-    like C fminf / fmaxf (a NaN operand is ignored)."""
+TERMS = ("ok", "umin", "umax", "vmin", "vmax", "zmin", "x0", "x1", "y0", "y1", "k", "d", "occluded")
+
+
+def occlusion_terms(world_aabb, pv, levels, width, height):
+    """Steps 1-9 of the header's test for every box (n x 6: min xyz, max xyz), every intermediate term kept: a dict of TERMS —
+    ok (step 3), umin .. vmax and zmin (steps 4-5), x0 .. y1 (step 6), k (step 7), d (step 8), occluded (step 9). Same float32
+    operations in the same order as the kernel; min / max fold like C fminf / fmaxf (a NaN operand is ignored)."""
     b = np.asarray(world_aabb, F32).reshape(-1, 6)
     m = np.asarray(pv, F32).reshape(16)
     wf, hf = F32(width), F32(height)
@@ -77,7 +80,13 @@ def occluded(world_aabb, pv, levels, width, height):
         s = int(lvl) + 1
         tx0, tx1, ty0, ty1 = x0[sel] >> s, x1[sel] >> s, y0[sel] >> s, y1[sel] >> s
         d[sel] = np.fmax(np.fmax(t[ty0, tx0], t[ty0, tx1]), np.fmax(t[ty1, tx0], t[ty1, tx1]))
-    return ok & (d < F32(1.0)) & (zmin > d)
+    result = ok & (d < F32(1.0)) & (zmin > d)
+    return dict(ok=ok, umin=umin, umax=umax, vmin=vmin, vmax=vmax, zmin=zmin, x0=x0, x1=x1, y0=y0, y1=y1, k=k, d=d, occluded=result)
+
+
+def occluded(world_aabb, pv, levels, width, height):
+    """Step 9's answer for every box: True = occluded by the pyramid (the frustum test and the candidate set are the caller's)."""
+    return occlusion_terms(world_aabb, pv, levels, width, height)["occluded"]
 
 
 def bits_of(bitmap, n):
