@@ -751,10 +751,84 @@ int32_t mip_batch_draws_shard(MipContext* ctx, const MipFrame* frame, const uint
 int32_t mip_merge_batches(MipContext* ctx, const void* chunks, uint32_t n_chunks, uint64_t chunk_stride_bytes,
                           uint32_t chunk_capacity, const MipBatchOutputs* out);
 
+/* ---- Extension: cluster culling — the frustum and Hi-Z tests per 64-triangle cluster ----------------------------------
+ * The level between whole instances (mip_run, mip_run_occluded) and single triangles (the per-triangle stage): every level
+ * of every mesh is cut into clusters of MIP_CLUSTER_TRIANGLES triangles with a box each; per frame, every cluster of every
+ * member is tested like an instance and the survivors are drawn by range from the source index buffer. NOT a reference
+ * behaviour; checked against this repository's restatement (tests/cluster_restatement.py) only.
+ *
+ * CLUSTER TABLE (mip_build_clusters). Buckets are mip_batch_draws_lods': b = lod_base[mesh] + lod, B = sum of n_lods. Bucket b
+ * has T(b) = floor(index_len[lod] / 3) triangles — triangle t is indices[index_offset[lod] + 3t .. + 3), a tail of one or two
+ * indices belongs to no cluster — and C(b) = ceil(T(b) / 64) clusters; cluster c holds triangles [64c, min(64c + 64, T)).
+ * Its BOX is, per axis, an fminf / fmaxf fold from +inf / -inf over vertices[vertex_offset + index] of every corner of its
+ * triangles: a NaN coordinate is ignored; min and max are exact, so the box is the same numbers in any order of reduction; as
+ * with world_aabb the sign of a zero is not specified and nothing downstream depends on it. Boxes are kept bucket-major,
+ * cluster c of bucket b at cluster_base[b] + c, cluster_base = the exclusive prefix sum of C. The table is built on the
+ * device from the resident geometry, all n_lods levels of every mesh; the call returns when it is complete. It needs the
+ * mesh table and mip_set_geometry (MIP_ERR_NOT_READY); every level's range must lie inside the uploaded indices and every
+ * vertex its triangles name inside the uploaded vertices (MIP_ERR_INVALID_ARGUMENT, checked on the host); more than 2^31
+ * clusters are MIP_ERR_CAPACITY. A later mip_set_mesh_table or mip_set_geometry makes the table STALE: mip_cull_clusters
+ * returns MIP_ERR_NOT_READY until it is built again. mip_cluster_count: the clusters of a valid table, else 0.
+ * mip_read_cluster_boxes copies 6 floats per cluster (min xyz, max xyz), bucket-major, to HOST memory with room for
+ * capacity_clusters of them (fewer than the table holds: MIP_ERR_CAPACITY); it exists so that the build is tested on its own.
+ *
+ * PER FRAME (mip_cull_clusters). frame, visible_bitmap (DEVICE) and policy (required) are mip_batch_draws_lods'; here
+ * frame->planes IS read. occ is NULL or a MipOcclusion of which pyramid, width, height and pv are read; its candidates and
+ * occluded_bitmap must be NULL and its flags 0.
+ * MEMBERS: instance i is a member iff bit i is set and T(bucket_i) > 0, lod_i selected exactly as mip_batch_draws_lods does.
+ * WORK ITEMS: (i, c) for every member i in draw-index order and every c < C(bucket_i) in order; W is their number.
+ * SURVIVES(i, c): the world box is what world_aabb would hold for instance i if its mesh box were the cluster's box — the
+ * same chain under the instance's model matrix, identical as numbers, non-finite instances and non-finite cluster boxes
+ * through the literal chain. The item survives iff that box is not culled by the plane test against frame->planes AND
+ * (occ is NULL or the box is not occluded by steps 1-9 of the occlusion test above).
+ * COMMANDS: a surviving item is a HEAD if c == 0 or (i, c - 1) does not survive; a run never crosses an instance. One
+ * command per head, in (i, c) order, packed from entry 0: indexCount = 3 x the triangles of the run's clusters (the last
+ * cluster of a bucket may be short), instanceCount = 1, firstIndex = index_offset[lod] + 192 x c_head (the source mesh's own
+ * range, as the batches address it; first_index_base is not read), vertexOffset = the mesh's, firstInstance =
+ * first_instance_base + i. An instance whose clusters all survive gets one command with the level's 3 x T indices; one
+ * none of whose clusters survive gets none. cmd_count = min(heads, cmd_capacity); entries at or behind it are never touched.
+ * stats (optional, 4 words): {heads, surviving clusters, W, members}.
+ * OVERFLOW. Heads > cmd_capacity: the first cmd_capacity commands are written exactly as they would be with room, cmd_count =
+ * cmd_capacity, stats holds the true values, and the status is MIP_ERR_CAPACITY — from the call, or from mip_wait for an
+ * asynchronous one (below). W > work_capacity (0 = the library's own bound, N x the largest C of the table), or W >= 2^32:
+ * MIP_ERR_CAPACITY, cmd_count = 0, stats = {0, 0, W mod 2^32, members}, no command written. The context stays usable.
+ * WHO REPORTS AN OVERFLOW: a synchronous call returns the status of ITSELF alone, once, whatever else of the context is in
+ * flight — an overflow of an earlier asynchronous call is never charged to it. The overflow of an asynchronous call is
+ * returned by the next mip_wait that has no other error to return, once for all asynchronous calls since the last such
+ * mip_wait; when mip_wait returns another error first, the overflow is kept and the mip_wait after it returns it. Which
+ * call overflowed is read from the calls' own cmd_count and stats.
+ * N = 0 writes a zero count (and zero stats). REFUSED, nothing written: NULL ctx / frame / bitmap / out / cluster_cmds /
+ * cmd_count, a wrong struct_size of any struct, unknown flags, a missing MIP_OUT_DEVICE, a misaligned output, a policy
+ * mip_batch_draws_lods refuses, a MipOcclusion with candidates, occluded_bitmap or flags, a depth extent out of range or a
+ * NULL pyramid: MIP_ERR_INVALID_ARGUMENT; no instances, no mesh table, no valid cluster table: MIP_ERR_NOT_READY.
+ * ORDERING: enqueued on the stream of the frame issued last, like mip_batch_draws; a bitmap that frame writes and a pyramid
+ * built (mip_build_depth_pyramid) for the next run need no wait. Scratch is the call's own, per frame slot, allocated at
+ * first use and grown by a larger call; with work_capacity = 0 it is sized for N x the largest C (16 bytes per 64 work
+ * items), so a scene of large meshes should state its bound.
+ * OUT OF SCOPE: a normal-cone back-face test; feeding the per-triangle stage from surviving clusters; views, shards, skinned
+ * instances, mip_run_many and recorded graphs; batch_model. */
+#define MIP_CLUSTER_TRIANGLES 64u
+typedef struct MipClusterOutputs {
+  uint32_t struct_size;      /* = sizeof(MipClusterOutputs) */
+  uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
+  void* cluster_cmds;        /* DEVICE: room for cmd_capacity MipDrawIndexedIndirectCommand */
+  uint32_t cmd_capacity;     /* commands that fit */
+  uint32_t work_capacity;    /* the caller's bound on W; 0 = N x the largest C of the table */
+  uint32_t* cmd_count;       /* DEVICE: commands written = min(heads, cmd_capacity) */
+  uint32_t* stats;           /* DEVICE, optional, 4 words: heads, surviving clusters, W, members */
+} MipClusterOutputs;         /* 40 B */
+
+int32_t mip_build_clusters(MipContext* ctx);
+uint32_t mip_cluster_count(const MipContext* ctx);
+int32_t mip_read_cluster_boxes(MipContext* ctx, float* host_out, uint32_t capacity_clusters);
+int32_t mip_cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                          const MipOcclusion* occ, const MipClusterOutputs* out);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every
- * frames_in_flight frames): it is where their errors surface. */
+ * frames_in_flight frames): it is where their errors surface. The MIP_ERR_CAPACITY of an asynchronous
+ * mip_cull_clusters is returned when there is no other error to return; otherwise by the mip_wait after. */
 int32_t mip_wait(MipContext* ctx);
 
 /* Merge `n_chunks` shard draw lists (each: MipShardHeader followed by its commands,

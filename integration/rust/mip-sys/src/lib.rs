@@ -167,6 +167,34 @@ pub struct MipViewBatchOutputs {
     pub view_first_slot: *mut u32,
 }
 
+/// Triangles per cluster of mip_build_clusters.
+pub const MIP_CLUSTER_TRIANGLES: u32 = 64;
+
+/// Outputs of mip_cull_clusters: one command per run of surviving clusters, device pointers (see the header).
+#[repr(C)]
+pub struct MipClusterOutputs {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub cluster_cmds: *mut c_void,
+    pub cmd_capacity: u32,
+    pub work_capacity: u32,
+    pub cmd_count: *mut u32,
+    pub stats: *mut u32,
+}
+
+/// Per-frame parameters of the occlusion test (mip_cull_clusters reads pyramid, width, height and pv).
+#[repr(C)]
+pub struct MipOcclusion {
+    pub struct_size: u32,
+    pub width: u32,
+    pub height: u32,
+    pub flags: u32,
+    pub pyramid: *const c_void,
+    pub candidates: *const u32,
+    pub occluded_bitmap: *mut u32,
+    pub pv: [f32; 16],
+}
+
 extern "C" {
     pub fn mip_abi_version() -> u32;
     pub fn mip_create(cfg: *const MipConfig, out: *mut *mut MipContext) -> i32;
@@ -237,6 +265,13 @@ extern "C" {
                                  chunk: *mut c_void, ids_capacity: u32, flags: u32) -> i32;
     pub fn mip_merge_batches(ctx: *mut MipContext, chunks: *const c_void, n_chunks: u32, chunk_stride_bytes: u64, chunk_capacity: u32,
                              out: *const MipBatchOutputs) -> i32;
+    /// Extension: cluster culling. The table of 64-triangle clusters of every level, built on the device from the resident geometry.
+    pub fn mip_build_clusters(ctx: *mut MipContext) -> i32;
+    pub fn mip_cluster_count(ctx: *const MipContext) -> u32;
+    pub fn mip_read_cluster_boxes(ctx: *mut MipContext, host_out: *mut f32, capacity_clusters: u32) -> i32;
+    /// The frustum test and (occ non-null) the Hi-Z test per cluster of every member; one command per run of survivors.
+    pub fn mip_cull_clusters(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
+                             occ: *const MipOcclusion, out: *const MipClusterOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -253,6 +288,8 @@ const _: [u8; 28] = [0; std::mem::size_of::<MipLodPolicy>()];
 const _: [u8; 28] = [0; std::mem::size_of::<MipSortPolicy>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipViewBatchOutputs>()];
 const _: [u8; 16] = [0; std::mem::size_of::<MipBatchChunkHeader>()];
+const _: [u8; 40] = [0; std::mem::size_of::<MipClusterOutputs>()];
+const _: [u8; 104] = [0; std::mem::size_of::<MipOcclusion>()];
 
 impl Pipeline {
     /// `panic = "abort"` (Cargo.toml:133,138) makes a panic here as final as in the rest of the renderer.

@@ -306,7 +306,9 @@ int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visi
   return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
 }
 
-// MipLodPolicy as the header states it
+}  // namespace
+
+// MipLodPolicy as the header states it (mip_cull_clusters, api_cluster.hip, takes the same policies)
 int32_t check_policy(MipContext* ctx, const MipLodPolicy* policy) {
   if (!policy) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "policy is NULL");
   if (policy->struct_size != sizeof(MipLodPolicy))
@@ -320,6 +322,8 @@ int32_t check_policy(MipContext* ctx, const MipLodPolicy* policy) {
   }
   return MIP_OK;
 }
+
+namespace {
 
 // MipSortPolicy as the header states it
 int32_t check_sort(MipContext* ctx, const MipSortPolicy* sort) {

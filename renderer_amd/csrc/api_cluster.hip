@@ -1,0 +1,310 @@
+// api_cluster.hip — C ABI of the instance pipeline, part 7 of 7: cluster culling (extension, not reference behaviour).
+// mip_build_clusters cuts every level of every mesh into clusters of MIP_CLUSTER_TRIANGLES triangles and builds their boxes on
+// the device from the resident geometry; mip_cull_clusters runs the frustum test and (optionally) the Hi-Z test of the
+// instance level on every cluster of every member of a bitmap and writes one command per run of surviving clusters.
+// cluster_plan.hpp holds the arithmetic and the launch plan; the kernels (cluster_kernel.hpp) are instantiated here and only here.
+#include "context.hpp"
+#include "cluster_kernel.hpp"
+
+static_assert(sizeof(MipClusterOutputs) == 40, "MipClusterOutputs is part of the ABI");
+static_assert(MIP_CLUSTER_TRIANGLES == mip::kClusterTriangles, "cluster_plan.hpp restates the header");
+
+namespace mip_host {
+namespace {
+
+// Room for `want` elements of `bytes_each` bytes at *p: kept while it is large enough, replaced by a larger allocation otherwise
+// (hipFree waits for the work that still reads the old one). *cap is the number of elements *p holds.
+template <class T>
+int32_t grow(MipContext* ctx, T** p, size_t* cap, size_t want, size_t bytes_each) {
+  if (*p && want <= *cap) return MIP_OK;
+  (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  MIP_HIP(ctx, hipMalloc(reinterpret_cast<void**>(p), (want ? want : 1) * bytes_each));
+  *cap = want;
+  return MIP_OK;
+}
+
+// The overflow words (pinned, device-visible): two per frame slot. [2 slot] is raised by the asynchronous calls of the slot and
+// collected by mip_wait; [2 slot + 1] by a synchronous call, which drains its stream and collects the word itself — so a call
+// that fitted is never blamed for another's overflow, and no overflow is reported twice.
+constexpr uint32_t kStatusWords = 2 * MIP_MAX_FRAMES_IN_FLIGHT;
+
+// Every level of every mesh against the host copies of the geometry, as check_geometry (api_frame.hip) checks LODs 0 and 1:
+// the level's range inside the uploaded indices, every vertex its triangles name inside the uploaded vertices.
+int32_t check_levels(MipContext* ctx) {
+  for (uint32_t k = 0; k < ctx->h_meshes.size(); ++k) {
+    const MipMesh& m = ctx->h_meshes[k];
+    for (uint32_t l = 0; l < m.n_lods; ++l) {
+      const uint64_t off = m.index_offset[l], len = m.index_len[l];
+      if (off + len > ctx->n_indices)
+        return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mesh %u LOD %u: indices [%llu, %llu) outside the %u uploaded indices", k, l,
+                    (unsigned long long)off, (unsigned long long)(off + len), ctx->n_indices);
+      const uint64_t used = 3ull * mip::cluster_level_triangles((uint32_t)len);
+      uint32_t mx = 0;
+      for (uint64_t j = off; j < off + used; ++j) mx = ctx->h_indices[j] > mx ? ctx->h_indices[j] : mx;
+      if (used && (m.vertex_offset < 0 || (uint64_t)m.vertex_offset + mx >= ctx->n_vertices))
+        return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mesh %u LOD %u: vertex_offset %d + largest index %u outside the %u uploaded vertices", k, l,
+                    m.vertex_offset, mx, ctx->n_vertices);
+    }
+  }
+  return MIP_OK;
+}
+
+int32_t build_clusters(MipContext* ctx) {
+  if (!ctx->have_meshes || !ctx->have_geometry) return fail(ctx, MIP_ERR_NOT_READY, "mip_build_clusters needs the mesh table and mip_set_geometry");
+  if (int32_t rc = check_levels(ctx)) return rc;
+  // bucket b = lod_base[mesh] + lod, as mip_set_mesh_table numbers them
+  std::vector<uint32_t> base;
+  base.reserve((size_t)ctx->lod_buckets + 1);
+  unsigned long long total = 0;
+  uint32_t max_clusters = 0;
+  for (const MipMesh& m : ctx->h_meshes)
+    for (uint32_t l = 0; l < m.n_lods; ++l) {
+      const uint32_t c = mip::cluster_level_clusters(m.index_len[l]);
+      base.push_back((uint32_t)total);
+      total += c;
+      if (c > max_clusters) max_clusters = c;
+      if (total > mip::kClusterMaxTotal) return fail(ctx, MIP_ERR_CAPACITY, "more than 2^31 clusters in the table");
+    }
+  base.push_back((uint32_t)total);
+  if (int32_t rc = bind_device(ctx)) return rc;
+  if (int32_t rc = sync_all(ctx)) return rc;  // a cull in flight reads the table this call replaces
+  MipContext::ClusterTable& t = ctx->clusters;
+  t.valid = false;
+  if (int32_t rc = grow(ctx, &t.d_boxes, &t.boxes_cap, (size_t)total, 2 * sizeof(float4))) return rc;
+  if (int32_t rc = grow(ctx, &t.d_cluster_base, &t.base_cap, base.size(), 4)) return rc;
+  MIP_HIP(ctx, hipMemcpyAsync(t.d_cluster_base, base.data(), base.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (total) {
+    mip::ClusterBuildArgs a{};
+    a.vertices = ctx->d_vertices;
+    a.indices = ctx->d_indices;
+    a.chain = ctx->d_mesh_chain;
+    a.mesh_draw = ctx->d_mesh_draw;
+    a.bucket_lod = ctx->d_bucket_lod;
+    a.cluster_base = t.d_cluster_base;
+    a.boxes = t.d_boxes;
+    a.n_buckets = (uint32_t)ctx->lod_buckets;
+    a.total = (uint32_t)total;
+    const uint32_t blocks = (uint32_t)((total + mip::kWaves - 1u) / mip::kWaves);
+    hipLaunchKernelGGL(mip::mip_cluster_build_kernel, dim3(blocks), dim3(mip::kClusterThreads), 0, ctx->stream, a);
+    MIP_HIP(ctx, hipGetLastError());
+  }
+  MIP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `base` is a local; the call is synchronous
+  t.total = (uint32_t)total;
+  t.max_clusters = max_clusters;
+  t.valid = true;
+  return MIP_OK;
+}
+
+int32_t ensure_scratch(MipContext* ctx, MipContext::ClusterScratch& cs, const mip::ClusterPlan& plan) {
+  const size_t cap = instance_cap(ctx);
+  if (!cs.d_instances) {
+    MIP_HIP(ctx, hipMalloc(&cs.d_instances, (4 * cap + 1) * 4));
+    const size_t tiles = (cap + mip::kClusterInstanceTile - 1) / mip::kClusterInstanceTile;
+    MIP_HIP(ctx, hipMalloc(&cs.d_tile_items, tiles * 8));
+    MIP_HIP(ctx, hipMalloc(&cs.d_tile_members, tiles * 4));
+    MIP_HIP(ctx, hipMalloc(&cs.d_scalars, mip::kClusterScWords * 4));
+  }
+  if (int32_t rc = grow(ctx, &cs.d_words, &cs.words_cap, (size_t)plan.survive_words, 16)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_tile_heads, &cs.head_tiles_cap, (size_t)plan.head_tiles, 4)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_tile_survivors, &cs.survivor_tiles_cap, (size_t)plan.head_tiles, 4)) return rc;
+  return MIP_OK;
+}
+
+template <class Kernel>
+int32_t launch(MipContext* ctx, Kernel kernel, uint32_t blocks, hipStream_t stream, const mip::ClusterArgs& a) {
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(mip::kClusterThreads), 0, stream, a);
+  MIP_HIP(ctx, hipGetLastError());
+  return MIP_OK;
+}
+
+// Every check first (a refused call writes nothing), then the seven launches on the stream of the frame issued last.
+int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy, const MipOcclusion* occ,
+                      const MipClusterOutputs* out) {
+  if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
+  if (out->struct_size != sizeof(MipClusterOutputs))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipClusterOutputs));
+  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipClusterOutputs flags 0x%x", out->flags);
+  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_cull_clusters needs MIP_OUT_DEVICE outputs");
+  if (!out->cluster_cmds || !out->cmd_count) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cluster_cmds/cmd_count is NULL");
+  if ((uintptr_t)out->cluster_cmds % 4u != 0u || (uintptr_t)out->cmd_count % 4u != 0u || (uintptr_t)out->stats % 4u != 0u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "an output is not 4-byte aligned");
+  if (occ) {
+    if (occ->struct_size != sizeof(MipOcclusion))
+      return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipOcclusion.struct_size %u != %zu", occ->struct_size, sizeof(MipOcclusion));
+    if (occ->width < 1u || occ->height < 1u || occ->width > MIP_MAX_DEPTH_EXTENT || occ->height > MIP_MAX_DEPTH_EXTENT)
+      return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "depth extent %ux%u outside 1..%u", occ->width, occ->height, (unsigned)MIP_MAX_DEPTH_EXTENT);
+    if (!occ->pyramid) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "pyramid is NULL");
+    if (occ->flags || occ->candidates || occ->occluded_bitmap)
+      return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_cull_clusters takes no MipOcclusion flags, candidates or occluded_bitmap");
+  }
+  if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
+  if (!ctx->clusters.valid) return fail(ctx, MIP_ERR_NOT_READY, "no cluster table, or the mesh table / geometry changed since mip_build_clusters");
+  if (int32_t rc = bind_device(ctx)) return rc;
+
+  const uint32_t slot = ctx->last_slot;
+  hipStream_t stream = ctx->slots[slot].stream;
+  const bool async = (out->flags & MIP_OUT_ASYNC) != 0;
+  const uint32_t n = ctx->n;
+  if (n == 0) {  // nothing to test: zeros
+    MIP_HIP(ctx, hipMemsetAsync(out->cmd_count, 0, 4, stream));
+    if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, 16, stream));
+    return finish(ctx, stream, async);
+  }
+  if (!ctx->h_cluster_status) {
+    MIP_HIP(ctx, hipHostMalloc(&ctx->h_cluster_status, kStatusWords * 4, hipHostMallocMapped));
+    std::memset(ctx->h_cluster_status, 0, kStatusWords * 4);
+  }
+  const MipContext::ClusterTable& table = ctx->clusters;
+  const unsigned long long bound = mip::cluster_work_bound(n, table.max_clusters, out->work_capacity);
+  const mip::ClusterPlan plan = mip::plan_cluster_cull(n, bound);
+  if (ctx->cluster_scratch.size() != ctx->slots.size()) ctx->cluster_scratch.resize(ctx->slots.size());
+  MipContext::ClusterScratch& cs = ctx->cluster_scratch[slot];
+  if (int32_t rc = ensure_scratch(ctx, cs, plan)) return rc;
+  if (occ && ctx->next_slot != slot) {
+    // a pyramid built for the next run sits on that slot's stream: this call goes behind what that stream holds now
+    if (!ctx->cluster_pyramid_ready) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_pyramid_ready, hipEventDisableTiming));
+    MIP_HIP(ctx, hipEventRecord(ctx->cluster_pyramid_ready, ctx->slots[ctx->next_slot].stream));
+    MIP_HIP(ctx, hipStreamWaitEvent(stream, ctx->cluster_pyramid_ready, 0));
+  }
+
+  mip::ClusterArgs a{};
+  a.lods.chain = ctx->d_mesh_chain;
+  a.lods.bucket_lod = ctx->d_bucket_lod;
+  std::memcpy(a.lods.switch_sq, policy->switch_sq, sizeof a.lods.switch_sq);
+  a.lods.pos = ctx->d_pos; a.lods.rot = ctx->d_rot; a.lods.scale = ctx->d_scale; a.lods.mesh_id = ctx->d_mesh_id;
+  a.lods.meshes = ctx->d_meshes; a.lods.mesh_draw = ctx->d_mesh_draw;
+  a.lods.bitmap = visible_bitmap;
+  a.lods.n = n;
+  a.lods.n_tiles = plan.instance_tiles;
+  a.lods.n_buckets = (uint32_t)ctx->lod_buckets;
+  a.lods.first_instance_base = frame->first_instance_base;
+  std::memcpy(a.lods.cam, frame->cam_pos, sizeof a.lods.cam);
+  a.cluster_base = table.d_cluster_base;
+  a.boxes = table.d_boxes;
+  std::memcpy(a.planes, frame->planes, sizeof a.planes);
+  if (occ) {
+    std::memcpy(a.pv, occ->pv, sizeof a.pv);
+    a.pyramid = static_cast<const float*>(occ->pyramid);
+    a.width = occ->width;
+    a.height = occ->height;
+  }
+  a.bound = bound;
+  const size_t cap = instance_cap(ctx);
+  a.items = cs.d_instances;
+  a.bucket = cs.d_instances + cap;
+  a.member_inst = cs.d_instances + 2 * cap;
+  a.member_first = cs.d_instances + 3 * cap;  // cap + 1 words
+  a.tile_items = cs.d_tile_items;
+  a.tile_members = cs.d_tile_members;
+  a.scalars = cs.d_scalars;
+  a.words = static_cast<ulonglong2*>(cs.d_words);
+  a.tile_heads = cs.d_tile_heads;
+  a.tile_survivors = cs.d_tile_survivors;
+  a.cmds = static_cast<uint32_t*>(out->cluster_cmds);
+  a.cmd_capacity = out->cmd_capacity;
+  a.cmd_count = out->cmd_count;
+  a.stats = out->stats;
+  volatile uint32_t* status = ctx->h_cluster_status + 2u * slot + (async ? 0u : 1u);  // slot < MIP_MAX_FRAMES_IN_FLIGHT
+  MIP_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&a.status), const_cast<uint32_t*>(status), 0));
+  if (!async) *status = 0;  // (no synchronous call of the slot is in flight: each one drains its stream)
+#ifdef MIP_DEBUG_STAMPS
+  const DebugSwitches sw;
+  sw.tile_order(a.lods.n_tiles, a.lods.debug_tile_mult, a.lods.debug_tile_add);
+  a.debug_order = sw.reverse() ? mip::kClusterOrderReverse
+                  : (sw.order && std::strcmp(sw.order, "scramble") == 0) ? mip::kClusterOrderScramble : mip::kClusterOrderNone;
+#endif
+  const bool relative = policy->mode == MIP_LOD_RELATIVE;
+  if (int32_t rc = relative ? launch(ctx, mip::mip_cluster_count_kernel<MIP_LOD_RELATIVE>, plan.instance_tiles, stream, a)
+                            : launch(ctx, mip::mip_cluster_count_kernel<MIP_LOD_DISTANCE>, plan.instance_tiles, stream, a))
+    return rc;
+  if (int32_t rc = launch(ctx, mip::mip_cluster_scan_kernel, 1, stream, a)) return rc;
+  if (int32_t rc = launch(ctx, mip::mip_cluster_members_kernel, plan.instance_tiles, stream, a)) return rc;
+  if (int32_t rc = launch(ctx, mip::mip_cluster_cull_kernel, plan.cull_blocks, stream, a)) return rc;
+  if (int32_t rc = launch(ctx, mip::mip_cluster_heads_kernel, plan.head_blocks, stream, a)) return rc;
+  if (int32_t rc = launch(ctx, mip::mip_cluster_epilogue_kernel, 1, stream, a)) return rc;
+  if (int32_t rc = launch(ctx, mip::mip_cluster_commands_kernel, plan.head_blocks, stream, a)) return rc;
+  if (int32_t rc = finish(ctx, stream, async)) return rc;
+  if (!async && *status) {  // this call's own word, and its stream has drained
+    *status = 0;
+    return fail(ctx, MIP_ERR_CAPACITY, "mip_cull_clusters: more runs than cmd_capacity (the first cmd_capacity commands are written), or more work items than work_capacity / 2^32 - 1 (nothing is written); stats holds the counts");
+  }
+  return MIP_OK;
+}
+
+}  // namespace
+
+// mip_wait, after every stream has drained. An overflow of an asynchronous call is reported when nothing else is: while `rc`
+// is another error the words stay as they are, and the mip_wait after it reports the overflow — it is never lost.
+int32_t cluster_wait_status(MipContext* ctx, int32_t rc) {
+  if (!ctx->h_cluster_status || rc != MIP_OK) return rc;
+  uint32_t raised = 0;
+  for (uint32_t k = 0; k < kStatusWords; k += 2) {
+    raised |= ((volatile uint32_t*)ctx->h_cluster_status)[k];
+    ((volatile uint32_t*)ctx->h_cluster_status)[k] = 0;
+  }
+  if (!raised) return MIP_OK;
+  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters had more runs than cmd_capacity, or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
+}
+
+void cluster_release(MipContext* ctx) {
+  (void)hipFree(ctx->clusters.d_boxes);
+  (void)hipFree(ctx->clusters.d_cluster_base);
+  ctx->clusters = MipContext::ClusterTable{};
+  for (auto& cs : ctx->cluster_scratch) {
+    (void)hipFree(cs.d_instances);
+    (void)hipFree(cs.d_tile_items);
+    (void)hipFree(cs.d_tile_members);
+    (void)hipFree(cs.d_scalars);
+    (void)hipFree(cs.d_words);
+    (void)hipFree(cs.d_tile_heads);
+    (void)hipFree(cs.d_tile_survivors);
+  }
+  ctx->cluster_scratch.clear();
+  if (ctx->h_cluster_status) (void)hipHostFree(ctx->h_cluster_status);
+  ctx->h_cluster_status = nullptr;
+  if (ctx->cluster_pyramid_ready) (void)hipEventDestroy(ctx->cluster_pyramid_ready);
+  ctx->cluster_pyramid_ready = nullptr;
+}
+
+}  // namespace mip_host
+
+using namespace mip_host;
+
+extern "C" {
+
+int32_t mip_build_clusters(MipContext* ctx) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  return build_clusters(ctx);
+}
+
+uint32_t mip_cluster_count(const MipContext* ctx) { return ctx && ctx->clusters.valid ? ctx->clusters.total : 0u; }
+
+int32_t mip_read_cluster_boxes(MipContext* ctx, float* host_out, uint32_t capacity_clusters) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (!ctx->clusters.valid) return fail(ctx, MIP_ERR_NOT_READY, "no cluster table, or the mesh table / geometry changed since mip_build_clusters");
+  const uint32_t total = ctx->clusters.total;
+  if (capacity_clusters < total) return fail(ctx, MIP_ERR_CAPACITY, "%u clusters, room for %u", total, capacity_clusters);
+  if (!total) return MIP_OK;
+  if (!host_out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "host_out is NULL");
+  if (int32_t rc = bind_device(ctx)) return rc;
+  std::vector<float4> boxes((size_t)total * 2);
+  MIP_HIP(ctx, hipMemcpy(boxes.data(), ctx->clusters.d_boxes, boxes.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  for (size_t g = 0; g < total; ++g) {
+    const float4 lo = boxes[2 * g], hi = boxes[2 * g + 1];
+    float* o = host_out + 6 * g;
+    o[0] = lo.x; o[1] = lo.y; o[2] = lo.z;
+    o[3] = hi.x; o[4] = hi.y; o[5] = hi.z;
+  }
+  return MIP_OK;
+}
+
+int32_t mip_cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                          const MipOcclusion* occ, const MipClusterOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  return cull_clusters(ctx, frame, visible_bitmap, policy, occ, out);
+}
+
+}  // extern "C"

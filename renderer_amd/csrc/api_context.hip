@@ -105,6 +105,7 @@ void free_all(MipContext* ctx) {
   interop_release(ctx);
   comm_release(ctx);
   batch_release(ctx);
+  cluster_release(ctx);
   (void)hipFree(ctx->d_pos);
   (void)hipFree(ctx->d_rot);
   (void)hipFree(ctx->d_scale);
@@ -343,6 +344,7 @@ int32_t mip_set_mesh_table(MipContext* ctx, const MipMesh* meshes, uint32_t m) {
   ctx->have_meshes = true;
   ctx->h_meshes.assign(meshes, meshes + m);
   ctx->geometry_checked = 0;
+  ctx->clusters.valid = false;  // (mip_build_clusters cut the old table's levels)
   ctx->max_lod_tris = 0;
   for (uint32_t k = 0; k < m; ++k)
     for (uint32_t l = 0; l < meshes[k].n_lods && l < 2u; ++l)
@@ -404,6 +406,7 @@ int32_t mip_set_geometry(MipContext* ctx, const float* vertex_xyz, uint32_t n_ve
   ctx->have_geometry = true;
   ctx->h_indices.assign(indices, indices + n_indices);
   ctx->geometry_checked = 0;
+  ctx->clusters.valid = false;  // (mip_build_clusters read the old geometry)
   return MIP_OK;
 }
 

@@ -848,7 +848,7 @@ int32_t mip_wait(MipContext* ctx) {
   ctx->pending_async = false;
   int32_t rc = check_device_error(ctx);
   ctx->sharded_pending = 0;
-  return rc;
+  return cluster_wait_status(ctx, rc);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// context.hpp — the state behind a MipContext and the helpers the six host translation units share.
+// context.hpp — the state behind a MipContext and the helpers the seven host translation units share.
 //   api_context.hip   create / destroy, uploads (mesh table, instances, geometry, skeleton, poses), census, diagnostics
 //   api_frame.hip     one frame: plan (frame_plan.hpp) -> tag (prefix_tags.hpp) -> launches; the per-triangle stage's host side;
 //                     recorded launch graphs; views; light lists; mip_wait
@@ -9,6 +9,7 @@
 //                     mip_batch_draws_views, mip_batch_draws_shard — one stage (batch_kernel.hpp) under the key policies of batch_lods_kernel.hpp and
 //                     batch_views_kernel.hpp, planned by batch_plan.hpp; mip_merge_batches (batch_merge_kernel.hpp,
 //                     batch_merge_plan.hpp)
+//   api_cluster.hip   the cluster-culling extension: mip_build_clusters, mip_cull_clusters (cluster_kernel.hpp, cluster_plan.hpp)
 // (round 3 had all of it in one 2 224-line mip_api.hip)
 #pragma once
 
@@ -123,6 +124,30 @@ struct MipContext {
     size_t words_cap = 0;
   };
   BatchMergeScratch batch_merge;
+  // cluster culling (api_cluster.hip): the table mip_build_clusters makes from the resident geometry — stale (valid = false)
+  // after mip_set_mesh_table / mip_set_geometry until it is built again — and mip_cull_clusters' scratch per frame slot,
+  // allocated at first use and grown by a larger call
+  struct ClusterTable {
+    float4* d_boxes = nullptr;          // two per cluster, bucket-major: {min xyz, -}, {max xyz, -}
+    uint32_t* d_cluster_base = nullptr; // B + 1 words: the exclusive prefix sum of C over the buckets, and the total
+    size_t boxes_cap = 0, base_cap = 0; // clusters / words the two hold
+    uint32_t total = 0, max_clusters = 0;  // clusters in the table; the largest C of a bucket
+    bool valid = false;
+  };
+  ClusterTable clusters;
+  struct ClusterScratch {
+    uint32_t* d_instances = nullptr;    // items, bucket, member_first (+1), member_inst: 4 x instance_cap + 1 words
+    unsigned long long* d_tile_items = nullptr;  // per instance tile
+    uint32_t* d_tile_members = nullptr;
+    uint32_t* d_scalars = nullptr;
+    void* d_words = nullptr;            // 16 bytes per 64 work items: the survive word and the start word
+    uint32_t* d_tile_heads = nullptr;   // per head tile: heads
+    uint32_t* d_tile_survivors = nullptr;  //              survivors
+    size_t words_cap = 0, head_tiles_cap = 0, survivor_tiles_cap = 0;
+  };
+  std::vector<ClusterScratch> cluster_scratch;
+  uint32_t* h_cluster_status = nullptr;  // pinned, device-visible, two words per frame slot: an asynchronous / a synchronous cull of the slot overflowed
+  hipEvent_t cluster_pyramid_ready = nullptr;  // orders a cull behind a pyramid built on another slot's stream
   std::vector<FrameSlot> view_states;  // mip_run_views: one prefix state per view, all on `stream`
   hipStream_t stream = nullptr;  // = slots[0].stream: uploads, merges, timing
   // resident inputs
@@ -309,6 +334,10 @@ int32_t interop_drain(MipContext* ctx);                // api_interop.hip: every
 int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out, bool skinned, void* palette,
                   const MipOcclusion* occ = nullptr);  // api_frame.hip
 void batch_release(MipContext* ctx);                  // api_batch.hip: the batched-draws scratch, for mip_destroy
+int32_t check_policy(MipContext* ctx, const MipLodPolicy* policy);  // api_batch.hip: MipLodPolicy as the header states it
+void cluster_release(MipContext* ctx);                // api_cluster.hip: the cluster table and the culls' scratch, for mip_destroy
+// api_cluster.hip: the status mip_wait returns — `rc`, or MIP_ERR_CAPACITY when an asynchronous mip_cull_clusters overflowed
+int32_t cluster_wait_status(MipContext* ctx, int32_t rc);
 int32_t launch_occluded_frame(MipContext* ctx, const MipOcclusion* occ, mip::KernelArgs& a, const mip::LaunchPlan& plan, hipStream_t stream);  // api_occlusion.hip
 
 }  // namespace mip_host

@@ -44,6 +44,9 @@ struct PyramidArgs {
 // A depth pixel as the pyramid counts it: NaN is 1.0 (cleared), a zero is +0 (so that max is exact in any order).
 __device__ __forceinline__ float pyramid_pixel(float v) { return v != v ? 1.0f : v + 0.0f; }
 
+// (cluster_kernel.hpp includes this header for box_occluded alone, under MIP_OCCLUSION_DEVICE_HELPERS_ONLY: the pyramid kernel
+// is not a template, so it is defined in api_occlusion.hip's translation unit only)
+#ifndef MIP_OCCLUSION_DEVICE_HELPERS_ONLY
 // Levels 0-5 of block (bx, by) by its own workgroup (the first level through 16-byte loads where the pitch allows), then — in
 // the workgroup that finishes LAST — the levels above from level 5. Texels outside a level hold -inf in LDS: max ignores them.
 __global__ __launch_bounds__(256) void mip_depth_pyramid_kernel(const PyramidArgs a) {
@@ -214,6 +217,8 @@ __global__ __launch_bounds__(256) void mip_depth_pyramid_kernel(const PyramidArg
     }
   }
 }
+
+#endif  // MIP_OCCLUSION_DEVICE_HELPERS_ONLY
 
 // ---------------------------------------------------------------------------------------
 // the occluded frame

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+from ._lib import (MipBatchOutputs, MipClusterOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
                    MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
@@ -138,6 +138,21 @@ def batch_chunk_ids_offset(n_buckets):
 def batch_chunk_bytes(n_buckets, capacity):
     """MIP_BATCH_CHUNK_BYTES: bytes of a batch chunk with room for `capacity` ids."""
     return batch_chunk_ids_offset(n_buckets) + int(capacity) * 4
+
+
+def make_cluster_outputs(cluster_cmds, cmd_capacity, cmd_count, stats=0, work_capacity=0, async_=False):
+    """A MipClusterOutputs for cull_clusters: device pointers to room for cmd_capacity commands, to the count and (optional) to
+    the four stats words {heads, surviving clusters, W, members}; work_capacity bounds the (instance, cluster) work items of the
+    call (0 = N x the largest cluster count of a level, which is also what the call's scratch is sized by)."""
+    o = MipClusterOutputs()
+    o.struct_size = C.sizeof(MipClusterOutputs)
+    o.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+    o.cluster_cmds = cluster_cmds or None
+    o.cmd_capacity = int(cmd_capacity)
+    o.work_capacity = int(work_capacity)
+    o.cmd_count = cmd_count or None
+    o.stats = stats or None
+    return o
 
 
 def make_frame(planes, cam_pos, first_instance_base=0, first_index_base=0, pv=None):
@@ -608,6 +623,31 @@ class InstancePipeline:
         out.instance_count = instance_count or None
         self._check(self._lib.mip_merge_batches(self._ctx, chunks_ptr or None, int(n_chunks), int(chunk_stride_bytes), int(chunk_capacity),
                                                 C.addressof(out)))
+
+    # -- cluster culling (extension) --
+    def build_clusters(self):
+        """mip_build_clusters: cuts every level of every mesh into clusters of 64 triangles and builds their boxes on the device
+        from the resident geometry (set_mesh_table and set_geometry first; either of them makes the table stale again)."""
+        self._check(self._lib.mip_build_clusters(self._ctx))
+
+    def cluster_count(self):
+        """Clusters in the table, 0 without a valid one."""
+        return int(self._lib.mip_cluster_count(self._ctx))
+
+    def read_cluster_boxes(self):
+        """The table's boxes as a (clusters, 6) float32 array (min xyz, max xyz), bucket-major: the build, on its own."""
+        boxes = np.zeros((self.cluster_count(), 6), np.float32)
+        self._check(self._lib.mip_read_cluster_boxes(self._ctx, boxes.ctypes.data, len(boxes)))
+        return boxes
+
+    def cull_clusters(self, frame, visible_bitmap_ptr, policy, outputs, occlusion=None):
+        """mip_cull_clusters: the frustum test (frame's planes) and, with `occlusion` (make_occlusion: pyramid, extent and pv),
+        the Hi-Z test on every 64-triangle cluster of every member of `visible_bitmap_ptr` under `policy` (make_lod_policy);
+        one command per run of surviving clusters of an instance into `outputs` (make_cluster_outputs), drawn from the source
+        mesh's own index range. Enqueued behind the frame this context issued last. MIP_ERR_CAPACITY (from wait() for an
+        asynchronous call) when the runs do not fit cmd_capacity or the work items exceed work_capacity."""
+        self._check(self._lib.mip_cull_clusters(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                C.addressof(occlusion) if occlusion is not None else None, C.addressof(outputs)))
 
     # -- diagnostics --
     def timings(self):
