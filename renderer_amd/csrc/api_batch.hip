@@ -9,7 +9,10 @@
 // mip_batch_draws_sorted sorts the members of mip_batch_draws_lods by depth across buckets (key = D alone) and writes one
 // command per run of equal bucket in the sorted slots (batch_sorted_kernel.hpp: the key policy and the run stage).
 // One stage (batch_kernel.hpp) under the key policies of the entry points (batch_kernel.hpp, batch_lods_kernel.hpp,
-// batch_views_kernel.hpp, batch_sorted_kernel.hpp); batch_plan.hpp says which instantiation a call launches. The kernels are instantiated here and only here.
+// batch_views_kernel.hpp, batch_sorted_kernel.hpp); batch_plan.hpp says which instantiation a call launches and what every
+// pass reads and writes. The kernels are instantiated here and only here. On the host one function fills the argument fields
+// every entry shares (fill_common) and one runs the passes of a plan (run_passes) on one scratch type (ensure_scratch);
+// batch_draws, batch_draws_sorted and batch_draws_views keep their checks, their early-outs and their own argument fields.
 #include "context.hpp"
 #include "batch_views_kernel.hpp"
 #include "batch_sorted_kernel.hpp"
@@ -28,23 +31,42 @@ namespace {
 
 uint32_t batch_tiles_for(uint32_t n) { return (n + mip::kBatchTile - 1u) / mip::kBatchTile; }
 
-// The slot's scratch, sized from the context's capacities at first use: the tile x bin counts and the digit totals for every
-// frame; the (key, instance) lists, the bucket histogram and the slot map only once a frame needs more than one pass.
-int32_t ensure_scratch(MipContext* ctx, MipContext::BatchScratch& bs, bool several_passes, bool slot_map) {
-  const size_t cap = instance_cap(ctx);
-  if (!bs.d_counts) {
-    MIP_HIP(ctx, hipMalloc(&bs.d_counts, (size_t)mip::kBatchBins * batch_tiles_for((uint32_t)cap) * 4));
-    MIP_HIP(ctx, hipMalloc(&bs.d_totals, (mip::kBatchMaxPasses * mip::kBatchBins + 1) * 4));
-  }
-  if (several_passes && !bs.d_keys[0]) {
-    for (int k = 0; k < 2; ++k) {
-      MIP_HIP(ctx, hipMalloc(&bs.d_keys[k], cap * 4));
-      MIP_HIP(ctx, hipMalloc(&bs.d_ids[k], cap * 4));
+// Room in `bs` for a call over `entries` entries: the tile x bin counts and the digit totals always; with `lists` (a call of
+// several passes) the two (key, instance) lists and `hist_words` of bucket histogram; the slot map and the bucket map when asked
+// for. Every buffer is kept while it is large enough and replaced by a larger one otherwise (grow, context.hpp), in the order
+// a slot's scratch always allocated them.
+int32_t ensure_scratch(MipContext* ctx, MipContext::BatchScratch& bs, size_t entries, size_t hist_words, bool lists, bool slot_map,
+                       bool bucket_map) {
+  if (int32_t rc = grow(ctx, &bs.d_counts, &bs.tiles_cap, batch_tiles_for((uint32_t)entries), (size_t)mip::kBatchBins * 4)) return rc;
+  if (!bs.d_totals) MIP_HIP(ctx, hipMalloc(&bs.d_totals, (mip::kBatchMaxPasses * mip::kBatchBins + 1) * 4));
+  if (lists && (!bs.d_ids[1] || entries > bs.list_cap)) {  // the four hold the same number of entries: replaced together
+    bs.list_cap = 0;
+    for (uint32_t** list : {&bs.d_keys[0], &bs.d_ids[0], &bs.d_keys[1], &bs.d_ids[1]}) {
+      size_t none = 0;
+      if (int32_t rc = grow(ctx, list, &none, entries, 4)) return rc;
     }
-    MIP_HIP(ctx, hipMalloc(&bs.d_bucket_hist, (size_t)(ctx->max_meshes ? ctx->max_meshes : 1) * MIP_MAX_LODS * 4));
+    bs.list_cap = entries;
   }
-  if (several_passes && slot_map && !bs.d_slot_of) MIP_HIP(ctx, hipMalloc(&bs.d_slot_of, cap * 4));
+  if (lists)
+    if (int32_t rc = grow(ctx, &bs.d_bucket_hist, &bs.hist_cap, hist_words, 4)) return rc;
+  if (slot_map)
+    if (int32_t rc = grow(ctx, &bs.d_slot_of, &bs.slot_cap, entries, 4)) return rc;
+  if (bucket_map)
+    if (int32_t rc = grow(ctx, &bs.d_bucket_of, &bs.bucket_cap, entries, 4)) return rc;
   return MIP_OK;
+}
+
+// The scratch of frame slot `slot`, asked for the context's capacities: every buffer is allocated once, at first need.
+int32_t slot_scratch(MipContext* ctx, uint32_t slot, bool lists, bool slot_map, bool bucket_map, MipContext::BatchScratch*& bs) {
+  if (ctx->batch.size() != ctx->slots.size()) ctx->batch.resize(ctx->slots.size());
+  bs = &ctx->batch[slot];
+  return ensure_scratch(ctx, *bs, instance_cap(ctx), (size_t)(ctx->max_meshes ? ctx->max_meshes : 1) * MIP_MAX_LODS, lists, slot_map, bucket_map);
+}
+
+void release_scratch(MipContext::BatchScratch& bs) {
+  for (uint32_t* p : {bs.d_counts, bs.d_totals, bs.d_keys[0], bs.d_ids[0], bs.d_keys[1], bs.d_ids[1], bs.d_bucket_hist, bs.d_slot_of, bs.d_bucket_of})
+    (void)hipFree(p);
+  bs = MipContext::BatchScratch{};
 }
 
 // The instantiation behind every name of the plan (batch_plan.hpp).
@@ -124,82 +146,126 @@ int32_t launch(MipContext* ctx, mip::BatchKernel kernel, uint32_t blocks, hipStr
   return MIP_OK;
 }
 
-void release_view_scratch(MipContext::ViewBatchScratch& vs) {
-  (void)hipFree(vs.d_counts);
-  (void)hipFree(vs.d_totals);
-  for (int k = 0; k < 2; ++k) {
-    (void)hipFree(vs.d_keys[k]);
-    (void)hipFree(vs.d_ids[k]);
-  }
-  (void)hipFree(vs.d_bucket_hist);
-  vs = MipContext::ViewBatchScratch{};
+uint32_t grid_blocks(mip::BatchGrid grid, const mip::BatchArgs& a) {
+  return grid == mip::BatchGrid::tiles ? a.n_tiles : grid == mip::BatchGrid::bins ? a.n_bins : 1u;
 }
 
-// mip_batch_draws_views' own scratch, for the entries (n_views x N) and global buckets (n_views x B) of this call: kept while
-// it is large enough, replaced by a larger one otherwise (hipFree waits for the work that still reads the old one).
-int32_t ensure_view_scratch(MipContext* ctx, MipContext::ViewBatchScratch& vs, size_t entries, size_t buckets, bool several_passes) {
-  if (!vs.d_totals) MIP_HIP(ctx, hipMalloc(&vs.d_totals, (mip::kBatchMaxPasses * mip::kBatchBins + 1) * 4));
-  if (entries > vs.entries_cap) {
-    (void)hipFree(vs.d_counts);
-    vs.d_counts = nullptr;
-    vs.entries_cap = 0;
-    MIP_HIP(ctx, hipMalloc(&vs.d_counts, (size_t)mip::kBatchBins * batch_tiles_for((uint32_t)entries) * 4));
-    vs.entries_cap = entries;
+// The fields every entry point fills the same way, into a zeroed block: the resident columns and tables, the chain under a
+// policy, the tile count of `entries`, n_bins, the scratch words and the command and count outputs. frame / bitmap are null
+// for mip_batch_draws_views, whose kernels take a camera, a base and a bitmap per view.
+void fill_common(MipContext* ctx, mip::LodBatchArgs& a, const MipContext::BatchScratch& bs, const mip::BatchPlan& plan,
+                 const MipLodPolicy* policy, const MipFrame* frame, const uint32_t* bitmap, uint32_t entries, unsigned long long buckets,
+                 void* batch_cmds, uint32_t* batch_count, uint32_t* instance_count) {
+  if (policy) {
+    a.chain = ctx->d_mesh_chain;
+    a.bucket_lod = ctx->d_bucket_lod;
+    std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
   }
-  if (several_passes && entries > vs.list_cap) {
-    for (int k = 0; k < 2; ++k) {
-      (void)hipFree(vs.d_keys[k]);
-      (void)hipFree(vs.d_ids[k]);
-      vs.d_keys[k] = vs.d_ids[k] = nullptr;
-    }
-    vs.list_cap = 0;
-    for (int k = 0; k < 2; ++k) {
-      MIP_HIP(ctx, hipMalloc(&vs.d_keys[k], entries * 4));
-      MIP_HIP(ctx, hipMalloc(&vs.d_ids[k], entries * 4));
-    }
-    vs.list_cap = entries;
+  a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
+  a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
+  a.bitmap = bitmap;
+  a.n = ctx->n;
+  a.n_tiles = batch_tiles_for(entries);
+  a.n_buckets = (uint32_t)buckets;
+  a.n_bins = plan.several() ? mip::kBatchBins : (uint32_t)buckets;
+  if (frame) {
+    a.first_instance_base = frame->first_instance_base;
+    std::memcpy(a.cam, frame->cam_pos, sizeof a.cam);
   }
-  if (several_passes && buckets > vs.hist_cap) {
-    (void)hipFree(vs.d_bucket_hist);
-    vs.d_bucket_hist = nullptr;
-    vs.hist_cap = 0;
-    MIP_HIP(ctx, hipMalloc(&vs.d_bucket_hist, buckets * 4));
-    vs.hist_cap = buckets;
+  a.counts = bs.d_counts;
+  a.members = a.members_out = bs.d_totals + mip::kBatchMaxPasses * mip::kBatchBins;
+  a.batch_cmds = static_cast<uint32_t*>(batch_cmds);
+  a.batch_count = batch_count;
+  a.instance_count = instance_count;
+#ifdef MIP_DEBUG_STAMPS
+  DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);  // as fill_kernel_args (api_frame.hip) permutes the frame's tiles
+#endif
+}
+
+// The radix passes of `plan` over the block fill_common filled, wired as batch_pass_io says and launched as batch_pass_launch
+// says. `a` is the leading part of the caller's most derived block, as launch() takes it. with_bucket_hist: the command
+// writer counts buckets, in hist_words words of bs.d_bucket_hist (cleared here); not so for mip_batch_draws_sorted.
+// around_count(p, before) runs in front of and behind the count launch of pass p: the caller's own fields of that launch.
+template <class AroundCount>
+int32_t run_passes(MipContext* ctx, const mip::BatchPlan& plan, const MipContext::BatchScratch& bs, bool with_bucket_hist, size_t hist_words,
+                   uint32_t* instance_ids, void* batch_model, hipStream_t stream, mip::LodBatchArgs& a, AroundCount around_count) {
+  const bool several = plan.several();
+  if (several && with_bucket_hist) MIP_HIP(ctx, hipMemsetAsync(bs.d_bucket_hist, 0, hist_words * 4, stream));
+  for (uint32_t p = 0; p < plan.passes; ++p) {
+    const mip::BatchPassIo io = mip::batch_pass_io(plan, p, batch_model != nullptr, with_bucket_hist);
+    a.shift = io.shift;
+    a.totals = bs.d_totals + io.totals_row * mip::kBatchBins;
+    a.bucket_hist = io.bucket_hist ? bs.d_bucket_hist : nullptr;
+    a.keys_in = io.list_in < 0 ? nullptr : bs.d_keys[io.list_in];
+    a.ids_in = io.list_in < 0 ? nullptr : bs.d_ids[io.list_in];
+    a.keys_out = io.list_out < 0 ? nullptr : bs.d_keys[io.list_out];
+    a.ids_out = io.list_out < 0 ? nullptr : bs.d_ids[io.list_out];
+    a.instance_ids = io.ids ? instance_ids : nullptr;
+    a.slot_of = io.slot_of ? bs.d_slot_of : nullptr;
+    a.batch_model = io.model ? static_cast<float4*>(batch_model) : nullptr;
+    auto step = [&](uint32_t i) {
+      const mip::BatchLaunch l = mip::batch_pass_launch(plan, p, i);
+      return launch(ctx, l.kernel, grid_blocks(l.grid, a), stream, a);
+    };
+    around_count(p, true);
+    if (int32_t rc = step(mip::kBatchLaunchCount)) return rc;
+    around_count(p, false);
+    if (int32_t rc = step(mip::kBatchLaunchRowscan)) return rc;
+    if (io.commands) {  // the scan's epilogue: bucket totals -> commands and counts (and the list's length for later passes)
+      a.bucket_totals = !several ? a.totals : with_bucket_hist ? bs.d_bucket_hist : nullptr;
+      if (int32_t rc = step(mip::kBatchLaunchCommands)) return rc;
+    }
+    if (int32_t rc = step(mip::kBatchLaunchScatter)) return rc;
   }
   return MIP_OK;
+}
+
+// The matrices of a several-pass call, through slot_of, behind everything else.
+int32_t store_models(MipContext* ctx, const mip::BatchPlan& plan, void* batch_model, hipStream_t stream, mip::LodBatchArgs& a) {
+  if (plan.model == mip::BatchKernel::none) return MIP_OK;
+  a.batch_model = static_cast<float4*>(batch_model);
+  return launch(ctx, plan.model, a.n_tiles, stream, a);
 }
 
 }  // namespace
 
 void batch_release(MipContext* ctx) {
-  for (auto& bs : ctx->batch) {
-    (void)hipFree(bs.d_counts);
-    (void)hipFree(bs.d_totals);
-    for (int k = 0; k < 2; ++k) {
-      (void)hipFree(bs.d_keys[k]);
-      (void)hipFree(bs.d_ids[k]);
-    }
-    (void)hipFree(bs.d_bucket_hist);
-    (void)hipFree(bs.d_slot_of);
-    (void)hipFree(bs.d_bucket_of);
-  }
+  for (auto& bs : ctx->batch) release_scratch(bs);
   ctx->batch.clear();
-  release_view_scratch(ctx->view_batch);
+  release_scratch(ctx->view_batch);
   (void)hipFree(ctx->batch_merge.d_words);
   ctx->batch_merge = MipContext::BatchMergeScratch{};
 }
 
 namespace {
 
-// The argument checks every entry point shares, and the context's device made current.
+// The checks the output structs of the family share, in the order every entry point makes them, with the texts of each entry
+// point. The alignment rules differ per entry and stay with it.
+struct OutputTexts {
+  const char *type, *needs_device, *null_outputs;
+};
+constexpr OutputTexts kDrawsTexts{"MipBatchOutputs", "mip_batch_draws needs MIP_OUT_DEVICE outputs", "batch_cmds/batch_count/instance_ids is NULL"};
+constexpr OutputTexts kMergeTexts{"MipBatchOutputs", "mip_merge_batches needs MIP_OUT_DEVICE outputs", "batch_cmds/batch_count/instance_ids is NULL"};
+constexpr OutputTexts kViewsTexts{"MipViewBatchOutputs", "mip_batch_draws_views needs MIP_OUT_DEVICE outputs", "batch_cmds/batch_counts/instance_ids is NULL"};
+uint32_t reserved_of(const MipBatchOutputs&) { return 0u; }  // (no such field)
+uint32_t reserved_of(const MipViewBatchOutputs& out) { return out.reserved; }
+const uint32_t* counts_of(const MipBatchOutputs& out) { return out.batch_count; }
+const uint32_t* counts_of(const MipViewBatchOutputs& out) { return out.batch_counts; }
+
+template <class Out>
+int32_t check_outputs(MipContext* ctx, const Out* out, const OutputTexts& texts) {
+  if (out->struct_size != sizeof(Out)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "%s.struct_size %u != %zu", texts.type, out->struct_size, sizeof(Out));
+  if (reserved_of(*out) != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "%s.reserved is %u, not 0", texts.type, reserved_of(*out));
+  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown %s flags 0x%x", texts.type, out->flags);
+  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "%s", texts.needs_device);
+  if (!out->batch_cmds || !counts_of(*out) || !out->instance_ids) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "%s", texts.null_outputs);
+  return MIP_OK;
+}
+
+// The argument checks the entry points behind a frame share, and the context's device made current.
 int32_t check_call(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipBatchOutputs* out) {
   if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
-  if (out->struct_size != sizeof(MipBatchOutputs))
-    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipBatchOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipBatchOutputs));
-  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipBatchOutputs flags 0x%x", out->flags);
-  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_batch_draws needs MIP_OUT_DEVICE outputs");
-  if (!out->batch_cmds || !out->batch_count || !out->instance_ids)
-    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds/batch_count/instance_ids is NULL");
+  if (int32_t rc = check_outputs(ctx, out, kDrawsTexts)) return rc;
   if ((uintptr_t)out->batch_cmds % 4u != 0u || (uintptr_t)out->batch_model % 16u != 0u)
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds / batch_model is not aligned (4 / 16 bytes)");
   if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
@@ -247,62 +313,15 @@ int32_t batch_draws(MipContext* ctx, const MipFrame* frame, const uint32_t* visi
   // the arithmetic mip_run's `model` comes from: the census decides (frame_plan.hpp, LaunchPlan.general)
   const bool general = ctx->nonfinite_instances != 0 || ctx->force_general;
   const mip::BatchPlan plan = mip::plan_batch(entry, policy && policy->mode == MIP_LOD_RELATIVE, buckets, out->batch_model != nullptr, general);
-  const bool several = plan.several();
-  if (ctx->batch.size() != ctx->slots.size()) ctx->batch.resize(ctx->slots.size());
-  MipContext::BatchScratch& bs = ctx->batch[slot];
-  if (int32_t rc = ensure_scratch(ctx, bs, several, out->batch_model != nullptr)) return rc;
+  MipContext::BatchScratch* bs = nullptr;
+  if (int32_t rc = slot_scratch(ctx, slot, plan.several(), plan.several() && out->batch_model, false, bs)) return rc;
 
   mip::ShardBatchArgs a{};  // the most derived block: every kernel takes its own leading part
+  fill_common(ctx, a, *bs, plan, policy, frame, visible_bitmap, n, buckets, out->batch_cmds, out->batch_count, out->instance_count);
   a.chunk = shard_chunk;
-  if (policy) {
-    a.chain = ctx->d_mesh_chain;
-    a.bucket_lod = ctx->d_bucket_lod;
-    std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
-  }
   a.depth_flip = order == MIP_BATCH_ORDER_FAR_FIRST ? mip::kBatchDepthMax : 0u;
-  a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
-  a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
-  a.bitmap = visible_bitmap;
-  a.n = n;
-  a.n_tiles = batch_tiles_for(n);
-  a.n_buckets = (uint32_t)buckets;
-  a.n_bins = several ? mip::kBatchBins : (uint32_t)buckets;
-  a.first_instance_base = frame->first_instance_base;
-  std::memcpy(a.cam, frame->cam_pos, sizeof a.cam);
-  a.counts = bs.d_counts;
-  a.members = a.members_out = bs.d_totals + mip::kBatchMaxPasses * mip::kBatchBins;
-  a.batch_cmds = static_cast<uint32_t*>(out->batch_cmds);
-  a.batch_count = out->batch_count;
-  a.instance_count = out->instance_count;
-#ifdef MIP_DEBUG_STAMPS
-  DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);  // as fill_kernel_args (api_frame.hip) permutes the frame's tiles
-#endif
-  if (several) MIP_HIP(ctx, hipMemsetAsync(bs.d_bucket_hist, 0, (size_t)buckets * 4, stream));
-
-  for (uint32_t p = 0; p < plan.passes; ++p) {
-    const bool last = p + 1 == plan.passes;
-    a.shift = p * mip::kBatchDigitBits;
-    a.totals = bs.d_totals + p * mip::kBatchBins;
-    a.bucket_hist = (several && p == 0) ? bs.d_bucket_hist : nullptr;
-    a.keys_in = p ? bs.d_keys[(p - 1) & 1u] : nullptr;
-    a.ids_in = p ? bs.d_ids[(p - 1) & 1u] : nullptr;
-    a.keys_out = last ? nullptr : bs.d_keys[p & 1u];
-    a.ids_out = last ? nullptr : bs.d_ids[p & 1u];
-    a.instance_ids = last ? out->instance_ids : nullptr;
-    a.slot_of = (last && several && out->batch_model) ? bs.d_slot_of : nullptr;
-    a.batch_model = (last && !several) ? static_cast<float4*>(out->batch_model) : nullptr;
-    if (int32_t rc = launch(ctx, plan.count(p), a.n_tiles, stream, a)) return rc;
-    if (int32_t rc = launch(ctx, mip::BatchKernel::rowscan, a.n_bins, stream, a)) return rc;
-    if (p == 0) {  // the scan's epilogue: bucket totals -> commands and the two counts (and the list's length for later passes)
-      a.bucket_totals = several ? bs.d_bucket_hist : a.totals;
-      if (int32_t rc = launch(ctx, plan.commands, 1, stream, a)) return rc;
-    }
-    if (int32_t rc = launch(ctx, plan.scatter(p), a.n_tiles, stream, a)) return rc;
-  }
-  if (plan.model != mip::BatchKernel::none) {
-    a.batch_model = static_cast<float4*>(out->batch_model);
-    if (int32_t rc = launch(ctx, plan.model, a.n_tiles, stream, a)) return rc;
-  }
+  if (int32_t rc = run_passes(ctx, plan, *bs, true, (size_t)buckets, out->instance_ids, out->batch_model, stream, a, [](uint32_t, bool) {})) return rc;
+  if (int32_t rc = store_models(ctx, plan, out->batch_model, stream, a)) return rc;
   return finish(ctx, stream, (out->flags & MIP_OUT_ASYNC) != 0);
 }
 
@@ -362,67 +381,25 @@ int32_t batch_draws_sorted(MipContext* ctx, const MipFrame* frame, const uint32_
   const bool general = ctx->nonfinite_instances != 0 || ctx->force_general;
   const bool axis = sort->metric == MIP_DEPTH_VIEW_AXIS;
   const mip::BatchPlan plan = mip::plan_batch_sorted(policy->mode == MIP_LOD_RELATIVE, axis, sort->depth_bits, out->batch_model != nullptr, general);
-  if (ctx->batch.size() != ctx->slots.size()) ctx->batch.resize(ctx->slots.size());
-  MipContext::BatchScratch& bs = ctx->batch[slot];
-  if (int32_t rc = ensure_scratch(ctx, bs, true, out->batch_model != nullptr)) return rc;
-  if (!bs.d_bucket_of) MIP_HIP(ctx, hipMalloc(&bs.d_bucket_of, instance_cap(ctx) * 4));
+  MipContext::BatchScratch* bs = nullptr;
+  if (int32_t rc = slot_scratch(ctx, slot, true, out->batch_model != nullptr, true, bs)) return rc;
 
   mip::SortedBatchArgs a{};
-  a.chain = ctx->d_mesh_chain;
-  a.bucket_lod = ctx->d_bucket_lod;
-  std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
+  fill_common(ctx, a, *bs, plan, policy, frame, visible_bitmap, n, buckets, out->batch_cmds, out->batch_count, out->instance_count);
   a.depth_shift = 32u - sort->depth_bits;
   a.depth_flip = sort->order == MIP_BATCH_ORDER_FAR_FIRST ? (axis ? mip::kSortedUmaxAxis : mip::kSortedUmaxRadial) >> a.depth_shift : 0u;
   if (axis) std::memcpy(a.axis, sort->axis, sizeof a.axis);
-  a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
-  a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
-  a.bitmap = visible_bitmap;
-  a.n = n;
-  a.n_tiles = batch_tiles_for(n);
-  a.n_buckets = (uint32_t)buckets;
-  a.n_bins = mip::kBatchBins;
-  a.first_instance_base = frame->first_instance_base;
-  std::memcpy(a.cam, frame->cam_pos, sizeof a.cam);
-  a.counts = bs.d_counts;
-  a.members = a.members_out = bs.d_totals + mip::kBatchMaxPasses * mip::kBatchBins;
-  a.batch_cmds = static_cast<uint32_t*>(out->batch_cmds);
-  a.batch_count = out->batch_count;
-  a.instance_count = out->instance_count;
-#ifdef MIP_DEBUG_STAMPS
-  DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);
-#endif
-
-  for (uint32_t p = 0; p < plan.passes; ++p) {
-    const bool last = p + 1 == plan.passes;
-    a.shift = p * mip::kBatchDigitBits;
-    a.totals = bs.d_totals + p * mip::kBatchBins;
-    a.keys_in = p ? bs.d_keys[(p - 1) & 1u] : nullptr;
-    a.ids_in = p ? bs.d_ids[(p - 1) & 1u] : nullptr;
-    a.keys_out = last ? nullptr : bs.d_keys[p & 1u];
-    a.ids_out = last ? nullptr : bs.d_ids[p & 1u];
-    a.instance_ids = last ? out->instance_ids : nullptr;
-    a.slot_of = (last && out->batch_model) ? bs.d_slot_of : nullptr;
-    a.bucket_out = p == 0 ? bs.d_bucket_of : nullptr;  // the count of pass 0 stores the buckets; its scatter does not store them again
-    if (int32_t rc = launch(ctx, plan.count(p), a.n_tiles, stream, a)) return rc;
-    a.bucket_out = nullptr;
-    if (int32_t rc = launch(ctx, mip::BatchKernel::rowscan, a.n_bins, stream, a)) return rc;
-    if (p == 0)  // the scan's epilogue: the digit totals -> the list's length and instance_count
-      if (int32_t rc = launch(ctx, plan.commands, 1, stream, a)) return rc;
-    if (int32_t rc = launch(ctx, plan.scatter(p), a.n_tiles, stream, a)) return rc;
-  }
-  // the run stage: the tile rows reuse `counts` (row 0), the slots' buckets a list buffer the last pass did not read, and the
+  // the count of pass 0 stores the buckets; no other launch stores them again
+  auto bucket_out = [&](uint32_t p, bool before) { a.bucket_out = (before && p == 0) ? bs->d_bucket_of : nullptr; };
+  if (int32_t rc = run_passes(ctx, plan, *bs, false, 0, out->instance_ids, out->batch_model, stream, a, bucket_out)) return rc;
+  // the run stage: the tile rows reuse `counts` (row 0), the slots' buckets the list buffer batch_plan.hpp frees for them, and the
   // row's sum — the number of heads — is batch_count
-  a.bucket_in = bs.d_bucket_of;
-  a.slot_bucket = bs.d_keys[(plan.passes - 1) & 1u];
+  a.bucket_in = bs->d_bucket_of;
+  a.slot_bucket = bs->d_keys[mip::batch_run_stage_list(plan)];
   a.totals = out->batch_count;
-  for (uint32_t k = 0; k < mip::kBatchRunStageLaunches; ++k) {
-    const mip::BatchKernel kernel = mip::batch_run_stage(k);
-    if (int32_t rc = launch(ctx, kernel, kernel == mip::BatchKernel::rowscan ? 1u : a.n_tiles, stream, a)) return rc;
-  }
-  if (plan.model != mip::BatchKernel::none) {
-    a.batch_model = static_cast<float4*>(out->batch_model);
-    if (int32_t rc = launch(ctx, plan.model, a.n_tiles, stream, a)) return rc;
-  }
+  for (uint32_t k = 0; k < mip::kBatchRunStageLaunches; ++k)
+    if (int32_t rc = launch(ctx, mip::batch_run_stage(k), grid_blocks(mip::batch_run_stage_grid(k), a), stream, a)) return rc;
+  if (int32_t rc = store_models(ctx, plan, out->batch_model, stream, a)) return rc;
   return finish(ctx, stream, async);
 }
 
@@ -431,13 +408,7 @@ int32_t batch_draws_sorted(MipContext* ctx, const MipFrame* frame, const uint32_
 int32_t batch_draws_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps, uint32_t n_views,
                           const MipLodPolicy* policy, const MipViewBatchOutputs* out) {
   if (!frames || !visible_bitmaps || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frames/visible_bitmaps/out is NULL");
-  if (out->struct_size != sizeof(MipViewBatchOutputs))
-    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipViewBatchOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipViewBatchOutputs));
-  if (out->reserved != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipViewBatchOutputs.reserved is %u, not 0", out->reserved);
-  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipViewBatchOutputs flags 0x%x", out->flags);
-  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_batch_draws_views needs MIP_OUT_DEVICE outputs");
-  if (!out->batch_cmds || !out->batch_counts || !out->instance_ids)
-    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds/batch_counts/instance_ids is NULL");
+  if (int32_t rc = check_outputs(ctx, out, kViewsTexts)) return rc;
   if ((uintptr_t)out->batch_cmds % 4u != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds is not 4-byte aligned");
   if (n_views == 0 || n_views > MIP_MAX_VIEWS) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "n_views %u outside 1..%u", n_views, (unsigned)MIP_MAX_VIEWS);
   if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
@@ -465,16 +436,11 @@ int32_t batch_draws_views(MipContext* ctx, const MipFrame* frames, const uint32_
   uint32_t hist_copies = several ? 64u : 1u;
   while (hist_copies > 1u && hist_copies * buckets > (1ull << 20)) hist_copies >>= 1;
   const size_t hist_words = (size_t)hist_copies * (size_t)buckets;
-  MipContext::ViewBatchScratch& vs = ctx->view_batch;
-  if (int32_t rc = ensure_view_scratch(ctx, vs, entries, hist_words, several)) return rc;
+  MipContext::BatchScratch& vs = ctx->view_batch;
+  if (int32_t rc = ensure_scratch(ctx, vs, entries, hist_words, several, false, false)) return rc;
 
   mip::ViewBatchArgs a{};
-  a.chain = ctx->d_mesh_chain;
-  a.bucket_lod = ctx->d_bucket_lod;
-  std::memcpy(a.switch_sq, policy->switch_sq, sizeof a.switch_sq);
-  a.pos = ctx->d_pos; a.rot = ctx->d_rot; a.scale = ctx->d_scale; a.mesh_id = ctx->d_mesh_id;
-  a.meshes = ctx->d_meshes; a.mesh_draw = ctx->d_mesh_draw;
-  a.n = n;
+  fill_common(ctx, a, vs, plan, policy, nullptr, nullptr, entries, buckets, out->batch_cmds, nullptr, nullptr);
   a.n_views = n_views;
   a.view_buckets = (uint32_t)view_buckets;
   a.n_entries = entries;
@@ -485,37 +451,9 @@ int32_t batch_draws_views(MipContext* ctx, const MipFrame* frames, const uint32_
     std::memcpy(a.view_cam[v], frames[v].cam_pos, sizeof a.view_cam[v]);
     a.view_base[v] = frames[v].first_instance_base;
   }
-  a.n_tiles = batch_tiles_for(entries);
-  a.n_buckets = (uint32_t)buckets;
-  a.n_bins = several ? mip::kBatchBins : (uint32_t)buckets;
-  a.counts = vs.d_counts;
-  a.members = a.members_out = vs.d_totals + mip::kBatchMaxPasses * mip::kBatchBins;
-  a.batch_cmds = static_cast<uint32_t*>(out->batch_cmds);
   a.batch_counts = out->batch_counts;
   a.view_first_slot = out->view_first_slot;
-#ifdef MIP_DEBUG_STAMPS
-  DebugSwitches().tile_order(a.n_tiles, a.debug_tile_mult, a.debug_tile_add);
-#endif
-  if (several) MIP_HIP(ctx, hipMemsetAsync(vs.d_bucket_hist, 0, hist_words * 4, stream));
-
-  for (uint32_t p = 0; p < plan.passes; ++p) {
-    const bool last = p + 1 == plan.passes;
-    a.shift = p * mip::kBatchDigitBits;
-    a.totals = vs.d_totals + p * mip::kBatchBins;
-    a.bucket_hist = (several && p == 0) ? vs.d_bucket_hist : nullptr;
-    a.keys_in = p ? vs.d_keys[(p - 1) & 1u] : nullptr;
-    a.ids_in = p ? vs.d_ids[(p - 1) & 1u] : nullptr;
-    a.keys_out = last ? nullptr : vs.d_keys[p & 1u];
-    a.ids_out = last ? nullptr : vs.d_ids[p & 1u];
-    a.instance_ids = last ? out->instance_ids : nullptr;
-    if (int32_t rc = launch(ctx, plan.count(p), a.n_tiles, stream, a)) return rc;
-    if (int32_t rc = launch(ctx, mip::BatchKernel::rowscan, a.n_bins, stream, a)) return rc;
-    if (p == 0) {  // global bucket totals -> every view's commands, count and first slot (and the list's length for later passes)
-      a.bucket_totals = several ? vs.d_bucket_hist : a.totals;
-      if (int32_t rc = launch(ctx, plan.commands, 1, stream, a)) return rc;
-    }
-    if (int32_t rc = launch(ctx, plan.scatter(p), a.n_tiles, stream, a)) return rc;
-  }
+  if (int32_t rc = run_passes(ctx, plan, vs, true, hist_words, out->instance_ids, nullptr, stream, a, [](uint32_t, bool) {})) return rc;
   return finish(ctx, stream, async);
 }
 
@@ -523,12 +461,7 @@ int32_t batch_draws_views(MipContext* ctx, const MipFrame* frames, const uint32_
 // context's first stream, where the other merges run.
 int32_t merge_batches(MipContext* ctx, const void* chunks, uint32_t n_chunks, uint64_t stride, uint32_t capacity, const MipBatchOutputs* out) {
   if (!chunks || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "chunks/out is NULL");
-  if (out->struct_size != sizeof(MipBatchOutputs))
-    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipBatchOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipBatchOutputs));
-  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipBatchOutputs flags 0x%x", out->flags);
-  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_merge_batches needs MIP_OUT_DEVICE outputs");
-  if (!out->batch_cmds || !out->batch_count || !out->instance_ids)
-    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "batch_cmds/batch_count/instance_ids is NULL");
+  if (int32_t rc = check_outputs(ctx, out, kMergeTexts)) return rc;
   if (out->batch_model) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_merge_batches does not merge matrices: batch_model must be NULL");
   if ((uintptr_t)out->batch_cmds % 4u != 0u || (uintptr_t)out->instance_ids % 4u != 0u || (uintptr_t)out->batch_count % 4u != 0u ||
       (uintptr_t)out->instance_count % 4u != 0u)
@@ -550,13 +483,7 @@ int32_t merge_batches(MipContext* ctx, const void* chunks, uint32_t n_chunks, ui
 
   const mip::BatchMergePlan plan = mip::plan_batch_merge(n_chunks, buckets, capacity);
   MipContext::BatchMergeScratch& ms = ctx->batch_merge;
-  if (plan.scratch_words > ms.words_cap) {  // (hipFree waits for the work that still reads the old one)
-    (void)hipFree(ms.d_words);
-    ms.d_words = nullptr;
-    ms.words_cap = 0;
-    MIP_HIP(ctx, hipMalloc(&ms.d_words, (size_t)plan.scratch_words * 4));
-    ms.words_cap = (size_t)plan.scratch_words;
-  }
+  if (int32_t rc = grow(ctx, &ms.d_words, &ms.words_cap, (size_t)plan.scratch_words, 4)) return rc;
   mip::BatchMergeArgs a{};
   a.chunks = static_cast<const unsigned char*>(chunks);
   a.stride = stride;

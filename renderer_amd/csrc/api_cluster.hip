@@ -12,19 +12,6 @@ static_assert(MIP_CLUSTER_TRIANGLES == mip::kClusterTriangles, "cluster_plan.hpp
 namespace mip_host {
 namespace {
 
-// Room for `want` elements of `bytes_each` bytes at *p: kept while it is large enough, replaced by a larger allocation otherwise
-// (hipFree waits for the work that still reads the old one). *cap is the number of elements *p holds.
-template <class T>
-int32_t grow(MipContext* ctx, T** p, size_t* cap, size_t want, size_t bytes_each) {
-  if (*p && want <= *cap) return MIP_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  MIP_HIP(ctx, hipMalloc(reinterpret_cast<void**>(p), (want ? want : 1) * bytes_each));
-  *cap = want;
-  return MIP_OK;
-}
-
 // The overflow words (pinned, device-visible): two per frame slot. [2 slot] is raised by the asynchronous calls of the slot and
 // collected by mip_wait; [2 slot + 1] by a synchronous call, which drains its stream and collects the word itself — so a call
 // that fitted is never blamed for another's overflow, and no overflow is reported twice.

@@ -1,8 +1,9 @@
 // batch_plan.hpp — which kernels a batched-draws call launches: a pure function of the entry point, the policy's mode, the
 // bucket count, whether matrices are wanted and the census decision (plan_batch), or, for mip_batch_draws_sorted, of the mode,
-// the depth metric, depth_bits, whether matrices are wanted and the census decision (plan_batch_sorted). Plain C++, no HIP:
-// enumerated on the CPU by tests/native/batch_plan_check.cpp and tests/native/batch_sorted_plan_check.cpp. api_batch.hip maps
-// a BatchKernel to its instantiation and executes the plan.
+// the depth metric, depth_bits, whether matrices are wanted and the census decision (plan_batch_sorted); and what every pass
+// of a plan reads, writes and launches (batch_pass_io, batch_pass_launch). Plain C++, no HIP: enumerated on the CPU by
+// tests/native/batch_plan_check.cpp, batch_views_plan_check.cpp and batch_sorted_plan_check.cpp. api_batch.hip maps a
+// BatchKernel to its instantiation and executes the plan with one pass driver.
 #pragma once
 
 #include <cstdint>
@@ -129,6 +130,49 @@ constexpr BatchPlan plan_batch_sorted(bool relative, bool axis, uint32_t depth_b
   return p;
 }
 
+// What pass p wires up. The (key, instance) lists ping-pong between two buffer pairs: pass p reads the pair pass p - 1 wrote
+// and writes the other one; pass 0 forms its keys from the instance columns and the last pass writes the outputs instead.
+// `want_model`: the caller gave batch_model (never for views and shards). `with_bucket_hist`: the command writer counts
+// buckets, so pass 0 of several accumulates them (every entry but mip_batch_draws_sorted, whose commands come from runs).
+struct BatchPassIo {
+  int32_t list_in, list_out;  // the buffer pair read / written: 0, 1 or -1 for none
+  bool ids;                   // writes instance_ids
+  bool slot_of;               // writes the slot map the model kernel reads
+  bool model;                 // stores batch_model itself (the single pass)
+  bool bucket_hist;           // accumulates the members per bucket
+  bool commands;              // the commands kernel runs behind this pass's rowscan
+  uint32_t shift, totals_row; // the digit's shift; the row of the digit totals
+};
+constexpr BatchPassIo batch_pass_io(const BatchPlan& plan, uint32_t p, bool want_model, bool with_bucket_hist) {
+  const bool last = p + 1 == plan.passes;
+  BatchPassIo io{};
+  io.list_in = p ? (int32_t)((p - 1u) & 1u) : -1;
+  io.list_out = last ? -1 : (int32_t)(p & 1u);
+  io.ids = last;
+  io.slot_of = last && plan.several() && want_model;
+  io.model = last && !plan.several() && want_model;
+  io.bucket_hist = with_bucket_hist && plan.several() && p == 0;
+  io.commands = p == 0;
+  io.shift = p * kBatchDigitBits;
+  io.totals_row = p;
+  return io;
+}
+
+// The launches of pass p in order, each with the kind of its grid: one workgroup per tile, per bin, or one. kernel == none:
+// not launched (the commands kernel of passes 1..).
+enum class BatchGrid : uint32_t { tiles, bins, one };
+struct BatchLaunch {
+  BatchKernel kernel;
+  BatchGrid grid;
+};
+enum : uint32_t { kBatchLaunchCount, kBatchLaunchRowscan, kBatchLaunchCommands, kBatchLaunchScatter, kBatchPassLaunches };
+constexpr BatchLaunch batch_pass_launch(const BatchPlan& plan, uint32_t p, uint32_t i) {
+  return i == kBatchLaunchCount     ? BatchLaunch{plan.count(p), BatchGrid::tiles}
+         : i == kBatchLaunchRowscan ? BatchLaunch{BatchKernel::rowscan, BatchGrid::bins}
+         : i == kBatchLaunchCommands ? BatchLaunch{p == 0 ? plan.commands : BatchKernel::none, BatchGrid::one}
+                                     : BatchLaunch{plan.scatter(p), BatchGrid::tiles};
+}
+
 // The run stage of mip_batch_draws_sorted, in launch order, behind the last scatter (and in front of the model kernel):
 // per-tile head counts, their scan over the tiles (one row), the heads' commands, instanceCount of every command.
 constexpr uint32_t kBatchRunStageLaunches = 4;
@@ -136,5 +180,9 @@ constexpr BatchKernel batch_run_stage(uint32_t i) {
   constexpr BatchKernel k[kBatchRunStageLaunches] = {BatchKernel::run_heads, BatchKernel::rowscan, BatchKernel::run_commands, BatchKernel::run_counts};
   return k[i];
 }
+constexpr BatchGrid batch_run_stage_grid(uint32_t i) { return batch_run_stage(i) == BatchKernel::rowscan ? BatchGrid::one : BatchGrid::tiles; }
+// The list buffer pair whose keys the run stage may overwrite with the slots' buckets: the one the last pass did not read
+// (it read pair (passes - 2) & 1, and wrote none).
+constexpr uint32_t batch_run_stage_list(const BatchPlan& plan) { return (plan.passes - 1u) & 1u; }
 
 }  // namespace mip

@@ -5,10 +5,10 @@
 //   api_sharded.hip   shard merges, the collective-library seam, mip_run_sharded and its collective repair
 //   api_interop.hip   external memory and external semaphores (row f-2)
 //   api_occlusion.hip the occlusion-culling extension: depth pyramid builds, mip_run_occluded (occlusion_kernel.hpp)
-//   api_batch.hip     the batched-draws extension: mip_batch_draws, mip_batch_draws_lods, mip_batch_draws_ordered,
-//                     mip_batch_draws_views, mip_batch_draws_shard — one stage (batch_kernel.hpp) under the key policies of batch_lods_kernel.hpp and
-//                     batch_views_kernel.hpp, planned by batch_plan.hpp; mip_merge_batches (batch_merge_kernel.hpp,
-//                     batch_merge_plan.hpp)
+//   api_batch.hip     the batched-draws extension: mip_batch_draws, _lods, _ordered, _shard, _sorted and _views — one stage
+//                     (batch_kernel.hpp) under the key policies of batch_lods_kernel.hpp, batch_views_kernel.hpp and
+//                     batch_sorted_kernel.hpp, planned by batch_plan.hpp and run by one pass driver; mip_merge_batches
+//                     (batch_merge_kernel.hpp, batch_merge_plan.hpp)
 //   api_cluster.hip   the cluster-culling extension: mip_build_clusters, mip_cull_clusters (cluster_kernel.hpp, cluster_plan.hpp)
 // (round 3 had all of it in one 2 224-line mip_api.hip)
 #pragma once
@@ -95,28 +95,23 @@ struct MipContext {
   uint32_t graph_round = 64;          // frames per replay round over all slots (MIP_TUNE_GRAPH_ROUND, 0 = off)
   std::vector<FrameSlot> slots;
   uint32_t next_slot = 0;
-  // mip_batch_draws / mip_batch_draws_lods (api_batch.hip): scratch per frame slot, allocated at first use from max_instances / max_meshes
+  // batched draws (api_batch.hip): the scratch of the pass driver, every buffer allocated at first need and replaced by a
+  // larger one when a call asks for more. `batch`: one per frame slot, for the entry points that run behind a frame, always
+  // asked for the context's capacities (max_instances entries, MIP_MAX_LODS x max_meshes histogram words), so every buffer
+  // is allocated once. `view_batch`: mip_batch_draws_views' own on the first stream, asked for the n_views x N entries and
+  // the histogram copies of the call.
   struct BatchScratch {
-    uint32_t* d_counts = nullptr;       // [256 bins][tiles] members per (bin, tile), scanned in place
+    uint32_t* d_counts = nullptr;       // [256 bins][tiles of entries] members per (bin, tile), scanned in place
     uint32_t* d_totals = nullptr;       // kBatchMaxPasses x 256 digit totals + the member count
-    uint32_t* d_keys[2] = {nullptr, nullptr};  // tables of more than 128 meshes: the (key, instance) lists between passes
+    uint32_t* d_keys[2] = {nullptr, nullptr};  // several passes: the (key, instance) lists between passes
     uint32_t* d_ids[2] = {nullptr, nullptr};
-    uint32_t* d_bucket_hist = nullptr;  //   members per bucket, MIP_MAX_LODS x max_meshes words
+    uint32_t* d_bucket_hist = nullptr;  //   members per bucket (views: per global bucket, in every one of hist_copies copies)
     uint32_t* d_slot_of = nullptr;      //   slot of every member by instance (batch_model)
     uint32_t* d_bucket_of = nullptr;    // mip_batch_draws_sorted: bucket of every member by instance (the run stage)
+    size_t tiles_cap = 0, list_cap = 0, hist_cap = 0, slot_cap = 0, bucket_cap = 0;  // tiles d_counts holds, entries of each list, words of d_bucket_hist, entries of the two maps
   };
   std::vector<BatchScratch> batch;
-  // mip_batch_draws_views (api_batch.hip): the call's own scratch on the first stream, allocated at first use for the
-  // n_views x N entries asked for and grown by a larger call; never a slot's BatchScratch
-  struct ViewBatchScratch {
-    uint32_t* d_counts = nullptr;       // [256 bins][tiles of entries]
-    uint32_t* d_totals = nullptr;       // kBatchMaxPasses x 256 digit totals + the member count
-    uint32_t* d_keys[2] = {nullptr, nullptr};  // more than 256 global buckets: the (key, instance) lists between passes
-    uint32_t* d_ids[2] = {nullptr, nullptr};
-    uint32_t* d_bucket_hist = nullptr;  //   members per global bucket, n_views x B words in every copy (hist_copies of them)
-    size_t entries_cap = 0, list_cap = 0, hist_cap = 0;  // entries d_counts / the lists hold, words of d_bucket_hist
-  };
-  ViewBatchScratch view_batch;
+  BatchScratch view_batch;
   // mip_merge_batches (api_batch.hip): the offsets kernel's tables on the first stream (batch_merge_plan.hpp says what they
   // hold), allocated at first use for the n_chunks x B asked for and grown by a larger call
   struct BatchMergeScratch {
@@ -310,6 +305,19 @@ struct DebugSwitches {
   }
 };
 #endif
+
+// Room for `want` elements of `bytes_each` bytes at *p: kept while it is large enough, replaced by a larger allocation otherwise
+// (hipFree waits for the work that still reads the old one). *cap is the number of elements *p holds.
+template <class T>
+int32_t grow(MipContext* ctx, T** p, size_t* cap, size_t want, size_t bytes_each) {
+  if (*p && want <= *cap) return MIP_OK;
+  (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  MIP_HIP(ctx, hipMalloc(reinterpret_cast<void**>(p), (want ? want : 1) * bytes_each));
+  *cap = want;
+  return MIP_OK;
+}
 
 int32_t bind_device(MipContext* ctx);
 int32_t sync_all(MipContext* ctx);

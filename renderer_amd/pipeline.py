@@ -505,12 +505,8 @@ class InstancePipeline:
         self._check(self._lib.mip_run_occluded(self._ctx, C.addressof(frame), C.addressof(occlusion), C.addressof(outputs)))
 
     # -- batched draws (extension) --
-    def batch_draws(self, frame, visible_bitmap_ptr, *, batch_cmds, batch_count, instance_ids, instance_count=0, batch_model=0,
-                    async_=False):
-        """mip_batch_draws: one instanced command per non-empty (mesh, LOD) bucket of the members of `visible_bitmap_ptr` (a
-        device bitmap in MipOutputs.visible_bitmap's layout), the entity ids in slot order and, optionally, the members' model
-        matrices in slot order. Device pointers; enqueued behind the frame this context issued last. `frame` from make_frame
-        (its cam_pos and first_instance_base are read)."""
+    @staticmethod
+    def _batch_outputs(batch_cmds, batch_count, instance_ids, instance_count, batch_model, async_):
         out = MipBatchOutputs()
         out.struct_size = C.sizeof(MipBatchOutputs)
         out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
@@ -519,6 +515,15 @@ class InstancePipeline:
         out.instance_ids = instance_ids or None
         out.instance_count = instance_count or None
         out.batch_model = batch_model or None
+        return out
+
+    def batch_draws(self, frame, visible_bitmap_ptr, *, batch_cmds, batch_count, instance_ids, instance_count=0, batch_model=0,
+                    async_=False):
+        """mip_batch_draws: one instanced command per non-empty (mesh, LOD) bucket of the members of `visible_bitmap_ptr` (a
+        device bitmap in MipOutputs.visible_bitmap's layout), the entity ids in slot order and, optionally, the members' model
+        matrices in slot order. Device pointers; enqueued behind the frame this context issued last. `frame` from make_frame
+        (its cam_pos and first_instance_base are read)."""
+        out = self._batch_outputs(batch_cmds, batch_count, instance_ids, instance_count, batch_model, async_)
         self._check(self._lib.mip_batch_draws(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(out)))
 
     def batch_draws_lods(self, frame, visible_bitmap_ptr, policy, *, batch_cmds, batch_count, instance_ids, instance_count=0,
@@ -526,14 +531,7 @@ class InstancePipeline:
         """mip_batch_draws_lods: batch_draws over the whole LOD chain — one instanced command per non-empty (mesh, LOD) bucket,
         bucket = lod_base[mesh] + lod, the LOD chosen by `policy` (make_lod_policy). batch_cmds needs room for
         min(sum of n_lods, N) commands; everything else as batch_draws."""
-        out = MipBatchOutputs()
-        out.struct_size = C.sizeof(MipBatchOutputs)
-        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
-        out.batch_cmds = batch_cmds or None
-        out.batch_count = batch_count or None
-        out.instance_ids = instance_ids or None
-        out.instance_count = instance_count or None
-        out.batch_model = batch_model or None
+        out = self._batch_outputs(batch_cmds, batch_count, instance_ids, instance_count, batch_model, async_)
         self._check(self._lib.mip_batch_draws_lods(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                    C.addressof(out)))
 
@@ -546,14 +544,7 @@ class InstancePipeline:
         if isinstance(order, str):
             order = {"draw_index": _lib.MIP_BATCH_ORDER_DRAW_INDEX, "near_first": _lib.MIP_BATCH_ORDER_NEAR_FIRST,
                      "far_first": _lib.MIP_BATCH_ORDER_FAR_FIRST}[order]
-        out = MipBatchOutputs()
-        out.struct_size = C.sizeof(MipBatchOutputs)
-        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
-        out.batch_cmds = batch_cmds or None
-        out.batch_count = batch_count or None
-        out.instance_ids = instance_ids or None
-        out.instance_count = instance_count or None
-        out.batch_model = batch_model or None
+        out = self._batch_outputs(batch_cmds, batch_count, instance_ids, instance_count, batch_model, async_)
         self._check(self._lib.mip_batch_draws_ordered(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                       int(order), C.addressof(out)))
 
@@ -563,14 +554,7 @@ class InstancePipeline:
         make_sort_policy: radial or view-axis depth, near or far first, 16 / 24 / 32 key bits; ties in draw order) and one
         instanced command per run of neighbouring slots that draw the same bucket — the transparent pass. batch_cmds needs room
         for N commands; everything else as batch_draws_ordered."""
-        out = MipBatchOutputs()
-        out.struct_size = C.sizeof(MipBatchOutputs)
-        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
-        out.batch_cmds = batch_cmds or None
-        out.batch_count = batch_count or None
-        out.instance_ids = instance_ids or None
-        out.instance_count = instance_count or None
-        out.batch_model = batch_model or None
+        out = self._batch_outputs(batch_cmds, batch_count, instance_ids, instance_count, batch_model, async_)
         self._check(self._lib.mip_batch_draws_sorted(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                      C.addressof(sort), C.addressof(out)))
 
@@ -614,13 +598,7 @@ class InstancePipeline:
         n_chunks x chunk_capacity words, batch_cmds for min(B, n_chunks x chunk_capacity) commands. A corrupt chunk is
         MIP_ERR_DEVICE, a chunk with more members than chunk_capacity MIP_ERR_CAPACITY (from wait() for an async call); both
         leave two zero counts and nothing else."""
-        out = MipBatchOutputs()
-        out.struct_size = C.sizeof(MipBatchOutputs)
-        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
-        out.batch_cmds = batch_cmds or None
-        out.batch_count = batch_count or None
-        out.instance_ids = instance_ids or None
-        out.instance_count = instance_count or None
+        out = self._batch_outputs(batch_cmds, batch_count, instance_ids, instance_count, 0, async_)
         self._check(self._lib.mip_merge_batches(self._ctx, chunks_ptr or None, int(n_chunks), int(chunk_stride_bytes), int(chunk_capacity),
                                                 C.addressof(out)))
 

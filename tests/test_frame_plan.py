@@ -52,7 +52,10 @@ def test_skin_plan_tables_over_every_small_skeleton(tmp_path):
 def test_batch_plan_selects_the_kernels_the_entry_points_selected(tmp_path):
     """plan_batch (renderer_amd/csrc/batch_plan.hpp), which instantiation of the batched-draws stage every launch of a call is:
     every entry point, mode, bucket count at the pass boundaries, with and without matrices, both census decisions — against the
-    nested conditions the three entry points held before they shared one plan. A wrong entry is another key policy's kernel."""
+    nested conditions the three entry points held before they shared one plan. A wrong entry is another key policy's kernel.
+    Then the pass schedule (batch_pass_io, batch_pass_launch, batch_run_stage_list) of every plan, views and sorted included,
+    against the three pass loops the host held before it had one pass driver, and its invariants: a wrong ping-pong index is
+    a pass that reads the list it writes."""
     exe = str(tmp_path / "batch_plan_check")
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "native", "batch_plan_check.cpp"), "-o", exe])
@@ -61,6 +64,10 @@ def test_batch_plan_selects_the_kernels_the_entry_points_selected(tmp_path):
     last = out.stdout.strip().split("\n")[-1]
     assert last.startswith("BATCH PLAN OK"), out.stdout[-2000:]
     assert int(last.split()[3]) == 2 * 2 * 15 * 4 + 2 * 10 * 4   # draws and lods at 15 bucket counts, ordered at the 10 it accepts
+    schedule = out.stdout.strip().split("\n")[-2]
+    assert schedule.startswith("BATCH SCHEDULE OK"), out.stdout[-2000:]
+    # the plans above, shard and views at the 15 bucket counts, sorted at 3 key widths x mode x metric x matrices x census
+    assert int(schedule.split()[3]) == 2 * 2 * 15 * 4 + 2 * 10 * 4 + 2 * 15 * 2 + 2 * 15 + 2 * 2 * 3 * 2 * 2
 
 
 def test_plan_header_has_no_hip_dependency():
