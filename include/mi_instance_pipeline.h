@@ -824,11 +824,72 @@ int32_t mip_read_cluster_boxes(MipContext* ctx, float* host_out, uint32_t capaci
 int32_t mip_cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
                           const MipOcclusion* occ, const MipClusterOutputs* out);
 
+/* ---- Extension: cluster culling in two phases — record the occluded clusters, test them again -------------------------
+ * The only pyramid a frame has when it starts is last frame's. mip_cull_clusters_phase is mip_cull_clusters as two calls around
+ * the frame's own depth: FIRST culls against the old pyramid and RECORDS the work items it removed for occlusion alone; after
+ * the survivors are drawn and the pyramid is rebuilt, SECOND tests exactly those items against the new pyramid and emits the
+ * ones that are visible after all — and nothing that FIRST already drew. NOT a reference behaviour; checked against this
+ * repository's restatement (tests/cluster_phase_restatement.py) only. MEMBERS, WORK ITEMS, W, SURVIVES, HEAD and COMMANDS are
+ * the words of mip_cull_clusters above; mip_cull_clusters itself is unchanged.
+ *
+ * THE RECORD: the caller's DEVICE memory, 16-byte aligned, record_bytes of room. A 16-byte header of four words {W, members,
+ * candidates, 0}, then ceil(W / 64) 64-bit words: bit j of word k belongs to work item 64 k + j in (i, c) order; bits at or
+ * above W are 0. mip_cluster_record_bytes(work_items) = 16 + 8 x ceil(work_items / 64) is its size; pure, no device, no context.
+ *
+ * FIRST (phase = MIP_CLUSTER_PHASE_FIRST). occ is required, exactly as mip_cull_clusters takes it (a pyramid; candidates,
+ * occluded_bitmap NULL; flags 0). cluster_cmds, cmd_count and stats are byte for byte what mip_cull_clusters writes for the
+ * same ctx, frame, visible_bitmap, policy, occ and out. The record is written in addition: the bit of work item (i, c) is set
+ * iff its world box is NOT culled by the plane test against frame->planes AND is occluded by steps 1-9 of the occlusion test
+ * under occ — an item the planes cull is no candidate, whatever the pyramid says. candidates = the number of set bits. A
+ * command overflow (heads > cmd_capacity) leaves the record complete and valid. A WORK overflow is mip_cull_clusters' (W >
+ * work_capacity or its own bound, W >= 2^32) and also record_bytes < mip_cluster_record_bytes(W): commands, count, stats and
+ * status follow mip_cull_clusters' work-overflow rule, the record's header becomes {0xFFFFFFFF, 0, 0, 0} — no running call
+ * has that W — and no record word is defined. N = 0: a zero count, zero stats and the header {0, 0, 0, 0}.
+ *
+ * SECOND (phase = MIP_CLUSTER_PHASE_SECOND). frame (cam_pos and first_instance_base), visible_bitmap and policy are the FIRST
+ * call's, and the instance columns, the mesh table and the cluster table are unchanged since that call; occ is the NEW
+ * pyramid, required, in the same form. frame->planes is NOT read: a candidate has passed the plane test. MEMBERS, WORK ITEMS
+ * and W are formed as always. SURVIVES2(i, c) holds iff the item's record bit is set AND its world box is not occluded by
+ * steps 1-9 under occ. HEAD and COMMANDS are mip_cull_clusters' rules with SURVIVES2 in SURVIVES' place: a surviving item is
+ * a HEAD if c == 0 or (i, c - 1) does not survive this call — a run that touches a run FIRST drew is still a command of its
+ * own. stats = {heads, survivors of this call, W, members}. The command-overflow rule is unchanged; a W that exceeds
+ * work_capacity, or that the record_bytes stated to this call have no words for, is the work overflow of mip_cull_clusters.
+ * NOT THIS CALL'S RECORD: if the header's W or members differs from the call's, the status is MIP_ERR_DEVICE, cmd_count = 0,
+ * stats = {0, 0, W, members} (the call's own) and nothing else is written. The status comes from the call, or from mip_wait
+ * for an asynchronous one, by the route of an overflow (WHO REPORTS AN OVERFLOW above, with this code; when asynchronous
+ * calls since the last mip_wait raised both, MIP_ERR_DEVICE is the one returned). The context stays usable. This is a sanity
+ * check, not proof that nothing moved: a record of another call with the same W and the same member count is accepted, and
+ * its bits are then applied to the wrong items. The record is never modified by SECOND. N = 0: a zero count, zero stats.
+ *
+ * REFUSED, nothing written, MIP_ERR_INVALID_ARGUMENT: everything mip_cull_clusters refuses; a NULL rec or record; a record
+ * that is not 16-byte aligned; record_bytes < 16; an unknown phase; a wrong MipClusterRecord.struct_size; a NULL occ.
+ * MIP_ERR_NOT_READY as mip_cull_clusters.
+ * ORDERING: both calls go on the stream of the frame issued last, as mip_cull_clusters does. A SECOND call normally follows
+ * mip_build_depth_pyramid and the phase-2 mip_run_occluded, which with more than one frame in flight is another slot's
+ * stream than the FIRST call's: the context orders every SECOND call behind the last FIRST call it was given, on the device;
+ * the caller needs no host wait between them.
+ * THE FRAME that composes instance phases and cluster phases: (1) mip_run_occluded with last frame's pyramid, then FIRST over
+ * its bitmap; (2) draw, rebuild the pyramid; (3) mip_run_occluded with the inverted candidates, then plain mip_cull_clusters
+ * over ITS bitmap under the new pyramid (instances phase 1 never saw as visible have no record); (4) SECOND over phase 1's
+ * bitmap. */
+#define MIP_CLUSTER_PHASE_FIRST  1u
+#define MIP_CLUSTER_PHASE_SECOND 2u
+typedef struct MipClusterRecord {
+  uint32_t struct_size;   /* = sizeof(MipClusterRecord) */
+  uint32_t phase;         /* MIP_CLUSTER_PHASE_FIRST: written; _SECOND: read */
+  void*    record;        /* DEVICE, 16-byte aligned, the caller's */
+  uint64_t record_bytes;  /* room behind `record` */
+} MipClusterRecord;       /* 24 B */
+uint64_t mip_cluster_record_bytes(uint64_t work_items);
+int32_t mip_cull_clusters_phase(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                const MipOcclusion* occ, const MipClusterOutputs* out, const MipClusterRecord* rec);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every
  * frames_in_flight frames): it is where their errors surface. The MIP_ERR_CAPACITY of an asynchronous
- * mip_cull_clusters is returned when there is no other error to return; otherwise by the mip_wait after. */
+ * mip_cull_clusters (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase) is returned
+ * when there is no other error to return; otherwise by the mip_wait after. */
 int32_t mip_wait(MipContext* ctx);
 
 /* Merge `n_chunks` shard draw lists (each: MipShardHeader followed by its commands,

@@ -182,6 +182,19 @@ pub struct MipClusterOutputs {
     pub stats: *mut u32,
 }
 
+/// Phases of mip_cull_clusters_phase.
+pub const MIP_CLUSTER_PHASE_FIRST: u32 = 1;
+pub const MIP_CLUSTER_PHASE_SECOND: u32 = 2;
+
+/// The record of mip_cull_clusters_phase: written by FIRST, read by SECOND; the caller's device memory, 16-byte aligned.
+#[repr(C)]
+pub struct MipClusterRecord {
+    pub struct_size: u32,
+    pub phase: u32,
+    pub record: *mut c_void,
+    pub record_bytes: u64,
+}
+
 /// Per-frame parameters of the occlusion test (mip_cull_clusters reads pyramid, width, height and pv).
 #[repr(C)]
 pub struct MipOcclusion {
@@ -272,6 +285,11 @@ extern "C" {
     /// The frustum test and (occ non-null) the Hi-Z test per cluster of every member; one command per run of survivors.
     pub fn mip_cull_clusters(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
                              occ: *const MipOcclusion, out: *const MipClusterOutputs) -> i32;
+    /// 16 + 8 x ceil(work_items / 64): the bytes of a record. Pure.
+    pub fn mip_cluster_record_bytes(work_items: u64) -> u64;
+    /// mip_cull_clusters in two phases: FIRST records the clusters the Hi-Z test alone removed, SECOND tests them again.
+    pub fn mip_cull_clusters_phase(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
+                                   occ: *const MipOcclusion, out: *const MipClusterOutputs, rec: *const MipClusterRecord) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -289,6 +307,7 @@ const _: [u8; 28] = [0; std::mem::size_of::<MipSortPolicy>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipViewBatchOutputs>()];
 const _: [u8; 16] = [0; std::mem::size_of::<MipBatchChunkHeader>()];
 const _: [u8; 40] = [0; std::mem::size_of::<MipClusterOutputs>()];
+const _: [u8; 24] = [0; std::mem::size_of::<MipClusterRecord>()];
 const _: [u8; 104] = [0; std::mem::size_of::<MipOcclusion>()];
 
 impl Pipeline {

@@ -1,21 +1,27 @@
 // api_cluster.hip — C ABI of the instance pipeline, part 7 of 7: cluster culling (extension, not reference behaviour).
 // mip_build_clusters cuts every level of every mesh into clusters of MIP_CLUSTER_TRIANGLES triangles and builds their boxes on
 // the device from the resident geometry; mip_cull_clusters runs the frustum test and (optionally) the Hi-Z test of the
-// instance level on every cluster of every member of a bitmap and writes one command per run of surviving clusters.
+// instance level on every cluster of every member of a bitmap and writes one command per run of surviving clusters;
+// mip_cull_clusters_phase is the same call in two phases: FIRST also records the clusters that passed the planes and failed the
+// Hi-Z test, SECOND tests exactly those again under a new pyramid.
 // cluster_plan.hpp holds the arithmetic and the launch plan; the kernels (cluster_kernel.hpp) are instantiated here and only here.
 #include "context.hpp"
 #include "cluster_kernel.hpp"
 
 static_assert(sizeof(MipClusterOutputs) == 40, "MipClusterOutputs is part of the ABI");
+static_assert(sizeof(MipClusterRecord) == 24, "MipClusterRecord is part of the ABI");
+static_assert(mip::kClusterFirst == MIP_CLUSTER_PHASE_FIRST && mip::kClusterSecond == MIP_CLUSTER_PHASE_SECOND, "cluster_kernel.hpp restates the header");
 static_assert(MIP_CLUSTER_TRIANGLES == mip::kClusterTriangles, "cluster_plan.hpp restates the header");
 
 namespace mip_host {
 namespace {
 
-// The overflow words (pinned, device-visible): two per frame slot. [2 slot] is raised by the asynchronous calls of the slot and
+// The status words (pinned, device-visible): two per frame slot. [2 slot] is raised by the asynchronous calls of the slot and
 // collected by mip_wait; [2 slot + 1] by a synchronous call, which drains its stream and collects the word itself — so a call
-// that fitted is never blamed for another's overflow, and no overflow is reported twice.
+// that fitted is never blamed for another's overflow, and no overflow is reported twice. A word holds a code: the bits
+// kClusterStatusCapacity (an overflow) and kClusterStatusDevice (a SECOND call met a record that is not its own).
 constexpr uint32_t kStatusWords = 2 * MIP_MAX_FRAMES_IN_FLIGHT;
+constexpr const char* kNotItsRecord = "mip_cull_clusters_phase: the record's header names another W or another member count than this SECOND call's: it is not the record of the FIRST call over these members (a zero count is written, stats holds the call's W and members)";
 
 // Every level of every mesh against the host copies of the geometry, as check_geometry (api_frame.hip) checks LODs 0 and 1:
 // the level's range inside the uploaded indices, every vertex its triangles name inside the uploaded vertices.
@@ -84,7 +90,7 @@ int32_t build_clusters(MipContext* ctx) {
   return MIP_OK;
 }
 
-int32_t ensure_scratch(MipContext* ctx, MipContext::ClusterScratch& cs, const mip::ClusterPlan& plan) {
+int32_t ensure_scratch(MipContext* ctx, MipContext::ClusterScratch& cs, const mip::ClusterPlan& plan, bool first) {
   const size_t cap = instance_cap(ctx);
   if (!cs.d_instances) {
     MIP_HIP(ctx, hipMalloc(&cs.d_instances, (4 * cap + 1) * 4));
@@ -96,6 +102,15 @@ int32_t ensure_scratch(MipContext* ctx, MipContext::ClusterScratch& cs, const mi
   if (int32_t rc = grow(ctx, &cs.d_words, &cs.words_cap, (size_t)plan.survive_words, 16)) return rc;
   if (int32_t rc = grow(ctx, &cs.d_tile_heads, &cs.head_tiles_cap, (size_t)plan.head_tiles, 4)) return rc;
   if (int32_t rc = grow(ctx, &cs.d_tile_survivors, &cs.survivor_tiles_cap, (size_t)plan.head_tiles, 4)) return rc;
+  if (first)
+    if (int32_t rc = grow(ctx, &cs.d_tile_candidates, &cs.candidate_tiles_cap, (size_t)plan.head_tiles, 4)) return rc;
+  return MIP_OK;
+}
+
+// The event a SECOND call waits for: behind everything the FIRST call enqueued.
+int32_t record_written(MipContext* ctx, hipStream_t stream) {
+  if (!ctx->cluster_record_written) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_record_written, hipEventDisableTiming));
+  MIP_HIP(ctx, hipEventRecord(ctx->cluster_record_written, stream));
   return MIP_OK;
 }
 
@@ -107,8 +122,9 @@ int32_t launch(MipContext* ctx, Kernel kernel, uint32_t blocks, hipStream_t stre
 }
 
 // Every check first (a refused call writes nothing), then the seven launches on the stream of the frame issued last.
+// rec == null: mip_cull_clusters; else a phase of mip_cull_clusters_phase (`phased`: the entry point, which refuses a null rec).
 int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy, const MipOcclusion* occ,
-                      const MipClusterOutputs* out) {
+                      const MipClusterOutputs* out, const MipClusterRecord* rec, bool phased) {
   if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
   if (out->struct_size != sizeof(MipClusterOutputs))
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipClusterOutputs));
@@ -126,6 +142,17 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
     if (occ->flags || occ->candidates || occ->occluded_bitmap)
       return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_cull_clusters takes no MipOcclusion flags, candidates or occluded_bitmap");
   }
+  if (phased) {
+    if (!rec) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "rec is NULL");
+    if (rec->struct_size != sizeof(MipClusterRecord))
+      return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterRecord.struct_size %u != %zu", rec->struct_size, sizeof(MipClusterRecord));
+    if (rec->phase != MIP_CLUSTER_PHASE_FIRST && rec->phase != MIP_CLUSTER_PHASE_SECOND)
+      return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipClusterRecord.phase %u", rec->phase);
+    if (!rec->record || (uintptr_t)rec->record % 16u != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "record is NULL or not 16-byte aligned");
+    if (rec->record_bytes < mip::kClusterRecordHeaderBytes) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "record_bytes %llu < 16", (unsigned long long)rec->record_bytes);
+    if (!occ) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_cull_clusters_phase needs a MipOcclusion: both phases test against a pyramid");
+  }
+  const bool first = rec && rec->phase == MIP_CLUSTER_PHASE_FIRST, second = rec && rec->phase == MIP_CLUSTER_PHASE_SECOND;
   if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
   if (!ctx->clusters.valid) return fail(ctx, MIP_ERR_NOT_READY, "no cluster table, or the mesh table / geometry changed since mip_build_clusters");
   if (int32_t rc = bind_device(ctx)) return rc;
@@ -137,6 +164,10 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   if (n == 0) {  // nothing to test: zeros
     MIP_HIP(ctx, hipMemsetAsync(out->cmd_count, 0, 4, stream));
     if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, 16, stream));
+    if (first) {
+      MIP_HIP(ctx, hipMemsetAsync(rec->record, 0, mip::kClusterRecordHeaderBytes, stream));
+      if (int32_t rc = record_written(ctx, stream)) return rc;
+    }
     return finish(ctx, stream, async);
   }
   if (!ctx->h_cluster_status) {
@@ -144,17 +175,23 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
     std::memset(ctx->h_cluster_status, 0, kStatusWords * 4);
   }
   const MipContext::ClusterTable& table = ctx->clusters;
-  const unsigned long long bound = mip::cluster_work_bound(n, table.max_clusters, out->work_capacity);
+  unsigned long long bound = mip::cluster_work_bound(n, table.max_clusters, out->work_capacity);
+  if (rec) {  // a W the record has no words for is a work overflow
+    const unsigned long long room = mip::cluster_record_items(rec->record_bytes);
+    bound = room < bound ? room : bound;
+  }
   const mip::ClusterPlan plan = mip::plan_cluster_cull(n, bound);
   if (ctx->cluster_scratch.size() != ctx->slots.size()) ctx->cluster_scratch.resize(ctx->slots.size());
   MipContext::ClusterScratch& cs = ctx->cluster_scratch[slot];
-  if (int32_t rc = ensure_scratch(ctx, cs, plan)) return rc;
+  if (int32_t rc = ensure_scratch(ctx, cs, plan, first)) return rc;
   if (occ && ctx->next_slot != slot) {
     // a pyramid built for the next run sits on that slot's stream: this call goes behind what that stream holds now
     if (!ctx->cluster_pyramid_ready) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_pyramid_ready, hipEventDisableTiming));
     MIP_HIP(ctx, hipEventRecord(ctx->cluster_pyramid_ready, ctx->slots[ctx->next_slot].stream));
     MIP_HIP(ctx, hipStreamWaitEvent(stream, ctx->cluster_pyramid_ready, 0));
   }
+  // SECOND goes behind the FIRST call that wrote the record, whichever slot's stream that call ran on
+  if (second && ctx->cluster_record_written) MIP_HIP(ctx, hipStreamWaitEvent(stream, ctx->cluster_record_written, 0));
 
   mip::ClusterArgs a{};
   a.lods.chain = ctx->d_mesh_chain;
@@ -193,6 +230,11 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   a.cmd_capacity = out->cmd_capacity;
   a.cmd_count = out->cmd_count;
   a.stats = out->stats;
+  if (rec) {
+    a.record_header = static_cast<uint32_t*>(rec->record);
+    a.record_words = reinterpret_cast<unsigned long long*>(static_cast<char*>(rec->record) + mip::kClusterRecordHeaderBytes);
+    a.tile_candidates = cs.d_tile_candidates;
+  }
   volatile uint32_t* status = ctx->h_cluster_status + 2u * slot + (async ? 0u : 1u);  // slot < MIP_MAX_FRAMES_IN_FLIGHT
   MIP_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&a.status), const_cast<uint32_t*>(status), 0));
   if (!async) *status = 0;  // (no synchronous call of the slot is in flight: each one drains its stream)
@@ -206,16 +248,29 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   if (int32_t rc = relative ? launch(ctx, mip::mip_cluster_count_kernel<MIP_LOD_RELATIVE>, plan.instance_tiles, stream, a)
                             : launch(ctx, mip::mip_cluster_count_kernel<MIP_LOD_DISTANCE>, plan.instance_tiles, stream, a))
     return rc;
-  if (int32_t rc = launch(ctx, mip::mip_cluster_scan_kernel, 1, stream, a)) return rc;
+  if (int32_t rc = second ? launch(ctx, mip::mip_cluster_scan_kernel<mip::kClusterSecond>, 1, stream, a)
+                          : launch(ctx, mip::mip_cluster_scan_kernel<mip::kClusterPlain>, 1, stream, a))
+    return rc;
   if (int32_t rc = launch(ctx, mip::mip_cluster_members_kernel, plan.instance_tiles, stream, a)) return rc;
-  if (int32_t rc = launch(ctx, mip::mip_cluster_cull_kernel, plan.cull_blocks, stream, a)) return rc;
-  if (int32_t rc = launch(ctx, mip::mip_cluster_heads_kernel, plan.head_blocks, stream, a)) return rc;
-  if (int32_t rc = launch(ctx, mip::mip_cluster_epilogue_kernel, 1, stream, a)) return rc;
+  if (int32_t rc = second  ? launch(ctx, mip::mip_cluster_retest_kernel, plan.retest_blocks, stream, a)
+                   : first ? launch(ctx, mip::mip_cluster_cull_kernel<true>, plan.cull_blocks, stream, a)
+                           : launch(ctx, mip::mip_cluster_cull_kernel<false>, plan.cull_blocks, stream, a))
+    return rc;
+  if (int32_t rc = first ? launch(ctx, mip::mip_cluster_heads_kernel<true>, plan.head_blocks, stream, a)
+                         : launch(ctx, mip::mip_cluster_heads_kernel<false>, plan.head_blocks, stream, a))
+    return rc;
+  if (int32_t rc = first ? launch(ctx, mip::mip_cluster_epilogue_kernel<true>, 1, stream, a)
+                         : launch(ctx, mip::mip_cluster_epilogue_kernel<false>, 1, stream, a))
+    return rc;
   if (int32_t rc = launch(ctx, mip::mip_cluster_commands_kernel, plan.head_blocks, stream, a)) return rc;
+  if (first)
+    if (int32_t rc = record_written(ctx, stream)) return rc;
   if (int32_t rc = finish(ctx, stream, async)) return rc;
   if (!async && *status) {  // this call's own word, and its stream has drained
+    const uint32_t code = *status;
     *status = 0;
-    return fail(ctx, MIP_ERR_CAPACITY, "mip_cull_clusters: more runs than cmd_capacity (the first cmd_capacity commands are written), or more work items than work_capacity / 2^32 - 1 (nothing is written); stats holds the counts");
+    if (code & mip::kClusterStatusDevice) return fail(ctx, MIP_ERR_DEVICE, "%s", kNotItsRecord);
+    return fail(ctx, MIP_ERR_CAPACITY, "mip_cull_clusters: more runs than cmd_capacity (the first cmd_capacity commands are written), or more work items than work_capacity / 2^32 - 1 / the record has words for (nothing is written); stats holds the counts");
   }
   return MIP_OK;
 }
@@ -232,6 +287,7 @@ int32_t cluster_wait_status(MipContext* ctx, int32_t rc) {
     ((volatile uint32_t*)ctx->h_cluster_status)[k] = 0;
   }
   if (!raised) return MIP_OK;
+  if (raised & mip::kClusterStatusDevice) return fail(ctx, MIP_ERR_DEVICE, "asynchronous %s", kNotItsRecord);
   return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters had more runs than cmd_capacity, or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
 }
 
@@ -247,12 +303,15 @@ void cluster_release(MipContext* ctx) {
     (void)hipFree(cs.d_words);
     (void)hipFree(cs.d_tile_heads);
     (void)hipFree(cs.d_tile_survivors);
+    (void)hipFree(cs.d_tile_candidates);
   }
   ctx->cluster_scratch.clear();
   if (ctx->h_cluster_status) (void)hipHostFree(ctx->h_cluster_status);
   ctx->h_cluster_status = nullptr;
   if (ctx->cluster_pyramid_ready) (void)hipEventDestroy(ctx->cluster_pyramid_ready);
   ctx->cluster_pyramid_ready = nullptr;
+  if (ctx->cluster_record_written) (void)hipEventDestroy(ctx->cluster_record_written);
+  ctx->cluster_record_written = nullptr;
 }
 
 }  // namespace mip_host
@@ -291,7 +350,16 @@ int32_t mip_cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t
                           const MipOcclusion* occ, const MipClusterOutputs* out) {
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
   if (int32_t rc = check_policy(ctx, policy)) return rc;
-  return cull_clusters(ctx, frame, visible_bitmap, policy, occ, out);
+  return cull_clusters(ctx, frame, visible_bitmap, policy, occ, out, nullptr, false);
+}
+
+uint64_t mip_cluster_record_bytes(uint64_t work_items) { return mip::cluster_record_bytes(work_items); }
+
+int32_t mip_cull_clusters_phase(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                const MipOcclusion* occ, const MipClusterOutputs* out, const MipClusterRecord* rec) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  return cull_clusters(ctx, frame, visible_bitmap, policy, occ, out, rec, true);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// cluster_kernel.hpp — cluster culling (mip_build_clusters, mip_cull_clusters; extension, not reference behaviour), gfx950:
+// cluster_kernel.hpp — cluster culling (mip_build_clusters, mip_cull_clusters, mip_cull_clusters_phase; extension, not reference behaviour), gfx950:
 // the frustum test and the Hi-Z test of the instance level on every 64-triangle cluster of every member, and one draw
 // command per run of surviving clusters. include/mi_instance_pipeline.h specifies it, tests/cluster_restatement.py restates
 // it in numpy, cluster_plan.hpp holds the arithmetic that is not a kernel. Instantiated in api_cluster.hip only.
@@ -27,6 +27,17 @@
 //              head's rank = the tile's prefix + the words before + the lanes below; the run length by scanning the survive
 //              words forward, bounded by the clusters the instance has left; guarded by cmd_capacity
 //
+// The two phases (mip_cull_clusters_phase) are the same seven launches with a compile-time phase:
+//
+//   FIRST      cull stores a third ballot, passed the planes && occluded, as the record word of its 64 items; heads counts
+//              the record's bits beside the survivors; the epilogue writes the record's header
+//   SECOND     scan compares the record's header with the call's W and members (a record of another call: W = 0 for the
+//              kernels behind it, the device-error bit raised); retest takes cull's place: a wave reads its record word and
+//              stores a zero survive word and a zero start word for a zero one — no search, no gather, no arithmetic —
+//              and else locates its items, builds their boxes and runs box_occluded alone, the ballot under the record word
+//
+// The kernels mip_cull_clusters launches are the instantiations of phase 0, the code they had before the phases existed.
+//
 // No workgroup waits for another and nothing depends on the order workgroups start in. The kernels that walk work items run
 // a grid sized for the host's bound on W (capped, cluster_plan.hpp) and loop over the tiles W — read from device memory —
 // gives; the diagnostic build permutes the tiles of every kernel.
@@ -48,7 +59,12 @@ static_assert(kClusterItemTile == kWaves * kBatchRounds * 64u && kClusterHeadTil
 constexpr uint32_t kClusterScW = 0;        // W, or 0 when the call does not run
 constexpr uint32_t kClusterScMembers = 1;
 constexpr uint32_t kClusterScWTrue = 2;    // W mod 2^32, whatever was decided
+constexpr uint32_t kClusterScRuns = 3;     // 1 when the call runs
 constexpr uint32_t kClusterScWords = 4;    // words the scan writes
+
+// the phase a kernel is instantiated for, and the bits of a slot's status word (a code, read by the host)
+constexpr uint32_t kClusterPlain = 0, kClusterFirst = 1, kClusterSecond = 2;
+constexpr uint32_t kClusterStatusCapacity = 1u, kClusterStatusDevice = 2u;
 
 struct ClusterBuildArgs {
   const float* vertices;
@@ -88,6 +104,10 @@ struct ClusterArgs {
   uint32_t* stats;               // or null
   uint32_t* status;              // the context's device-visible overflow word
   uint32_t debug_order;          // diagnostic build only: kClusterOrder* of the looping grids
+  // a two-phase call (appended: the layout in front of them is mip_cull_clusters')
+  uint32_t* record_header;       // the caller's record: {W, members, candidates, 0}, or null
+  unsigned long long* record_words;  // one per 64 work items behind the header: written by FIRST, read by SECOND
+  uint32_t* tile_candidates;     // scratch, head tiles (FIRST)
 };
 
 // ---- build ----
@@ -155,8 +175,11 @@ __device__ __forceinline__ uint32_t cluster_loop_tile(const ClusterArgs& a, uint
 #endif
 }
 
-__device__ __forceinline__ void cluster_raise(const ClusterArgs& a) {
-  __hip_atomic_store(a.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+// The slot's status word gains a bit. The calls of a slot are ordered by its stream and a call raises from one thread of one
+// kernel at a time; the host clears the word only after the stream has drained: nobody else writes between the load and the store.
+__device__ __forceinline__ void cluster_raise(const ClusterArgs& a, uint32_t code) {
+  const uint32_t old = __hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(a.status, old | code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // Exclusive scan of one 64-bit value per thread over the workgroup; `total` is the sum. s: kClusterThreads words.
@@ -217,8 +240,10 @@ __global__ __launch_bounds__(kClusterThreads) void mip_cluster_count_kernel(cons
   }
 }
 
-// scan: the tiles' sums become exclusive prefixes; W, members, and whether the call runs. One workgroup.
-static __global__ __launch_bounds__(kClusterThreads) __attribute__((unused)) void mip_cluster_scan_kernel(const ClusterArgs a) {
+// scan: the tiles' sums become exclusive prefixes; W, members, and whether the call runs. One workgroup. SECOND: a record whose
+// header names another W or another member count is not this call's — the kernels behind see W = 0, the epilogue zeros.
+template <uint32_t kPhase>
+__global__ __launch_bounds__(kClusterThreads) void mip_cluster_scan_kernel(const ClusterArgs a) {
   __shared__ unsigned long long s_scan[kClusterThreads];
   const uint32_t n_tiles = a.lods.n_tiles;
   unsigned long long items_before = 0, members_before = 0;
@@ -237,11 +262,16 @@ static __global__ __launch_bounds__(kClusterThreads) __attribute__((unused)) voi
   }
   if (threadIdx.x == 0u) {
     const bool fits = cluster_work_fits(items_before, a.bound);
-    a.scalars[kClusterScW] = fits ? (uint32_t)items_before : 0u;
+    bool runs = fits;
+    if constexpr (kPhase == kClusterSecond)
+      runs = fits && a.record_header[0] == (uint32_t)items_before && a.record_header[1] == (uint32_t)members_before;
+    a.scalars[kClusterScW] = runs ? (uint32_t)items_before : 0u;
+    a.scalars[kClusterScRuns] = runs ? 1u : 0u;
     a.scalars[kClusterScMembers] = (uint32_t)members_before;
     a.scalars[kClusterScWTrue] = (uint32_t)items_before;
     a.member_first[(uint32_t)members_before] = (uint32_t)items_before;  // members <= n: the list's end
-    if (!fits) cluster_raise(a);
+    if (!fits) cluster_raise(a, kClusterStatusCapacity);
+    else if (!runs) cluster_raise(a, kClusterStatusDevice);
   }
 }
 
@@ -315,8 +345,30 @@ __device__ __forceinline__ ClusterItem cluster_locate(const ClusterArgs& a, uint
   return {a.member_inst[m0 + j], w - first};
 }
 
-// cull: both tests on every work item; the survive word and the start word of every 64
-static __global__ __launch_bounds__(kClusterThreads, 4) __attribute__((unused)) void mip_cluster_cull_kernel(const ClusterArgs a) {
+// The world box of work item `it`: the model matrix from the instance columns, the CLUSTER's box in the mesh box's place.
+// For the retest kernel; cull holds the same lines itself, because calling this from it changed the schedule of the kernel
+// mip_cull_clusters launches, which is held to the instructions it had before the phases existed.
+__device__ __forceinline__ void cluster_world_box(const ClusterArgs& a, const ClusterItem& it, Instance& inst) {
+  const uint32_t i = it.inst;
+  const float px = a.lods.pos[3 * (size_t)i + 0], py = a.lods.pos[3 * (size_t)i + 1], pz = a.lods.pos[3 * (size_t)i + 2];
+  const float4 q = a.lods.rot[i];
+  const float sc = a.lods.scale[i];
+  const size_t g = (size_t)a.cluster_base[a.bucket[i]] + it.cluster;
+  const float4 b0 = a.boxes[2u * g], b1 = a.boxes[2u * g + 1u];
+  MeshEntry mb;  // the cluster's box in the mesh box's place
+  mb.min_x = b0.x; mb.min_y = b0.y; mb.min_z = b0.z; mb.len0 = 0u;
+  mb.max_x = b1.x; mb.max_y = b1.y; mb.max_z = b1.z; mb.len1 = 0u;
+  float rm[3][3];
+  quat_to_rotation(q.x, q.y, q.z, q.w, rm);
+  struct { const float* box_override; } no_box = {nullptr};
+  // always the kernel with the fall-back tiers: a cluster's box may hold anything the vertices hold
+  instance_tiered<false, true>(no_box, i, rm, px, py, pz, sc, mb, inst);
+}
+
+// cull: both tests on every work item; the survive word and the start word of every 64. kRecord (FIRST): and the record word,
+// the items that passed the planes and are occluded.
+template <bool kRecord>
+__global__ __launch_bounds__(kClusterThreads, 4) void mip_cluster_cull_kernel(const ClusterArgs a) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t w_total = a.scalars[kClusterScW], members = a.scalars[kClusterScMembers];
   const uint32_t n_tiles = cluster_item_tiles(w_total);
@@ -345,8 +397,45 @@ static __global__ __launch_bounds__(kClusterThreads, 4) __attribute__((unused)) 
       // always the kernel with the fall-back tiers: a cluster's box may hold anything the vertices hold
       instance_tiered<false, true>(no_box, i, rm, px, py, pz, sc, mb, inst);
       bool survives = active && !coarse_culled(inst, a.planes);
+      [[maybe_unused]] const bool passed = survives;
       if (survives && a.pyramid) survives = !box_occluded(inst.mins, inst.maxs, a.pv, a.pyramid, a.width, a.height);
       const unsigned long long s = __ballot(survives), start = __ballot(active && it.cluster == 0u);
+      if (lane == 0u) a.words[base >> 6] = make_ulonglong2(s, start);
+      if constexpr (kRecord) {
+        const unsigned long long candidates = __ballot(passed && !survives);  // (an item at or above W is not active: its bit is 0)
+        if (lane == 0u) a.record_words[base >> 6] = candidates;
+      }
+    }
+  }
+}
+
+// retest (SECOND, in cull's place): the Hi-Z test alone, on the items the record names. A wave reads its record word first: a
+// zero word is answered with a zero survive word and a zero start word — a head can only be in a non-zero word, and nothing
+// else reads a start word.
+static __global__ __launch_bounds__(kClusterThreads, 4) __attribute__((unused)) void mip_cluster_retest_kernel(const ClusterArgs a) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t w_total = a.scalars[kClusterScW], members = a.scalars[kClusterScMembers];
+  const uint32_t n_tiles = cluster_item_tiles(w_total);
+  for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const uint32_t tile = cluster_loop_tile(a, t, n_tiles);
+#pragma unroll 1
+    for (uint32_t r = 0; r < kBatchRounds; ++r) {
+      const unsigned long long base64 = (unsigned long long)tile * kClusterItemTile + wave * (kBatchRounds * 64u) + r * 64u;
+      if (base64 >= w_total) break;  // (the whole wave; the rounds behind it start later still)
+      const uint32_t base = (uint32_t)base64;
+      const unsigned long long loaded = a.record_words[base >> 6];  // word < ceil(W / 64): the scan matched W, the host the room
+      const unsigned long long candidates = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(loaded >> 32)) << 32) |
+                                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)loaded);
+      if (candidates == 0ull) {  // (the whole wave)
+        if (lane == 0u) a.words[base >> 6] = make_ulonglong2(0ull, 0ull);
+        continue;
+      }
+      const ClusterItem it = cluster_locate(a, base, lane, w_total, members);
+      const bool active = base + lane < w_total && ((candidates >> lane) & 1ull) != 0ull;
+      Instance inst;
+      cluster_world_box(a, it, inst);
+      const bool survives = active && !box_occluded(inst.mins, inst.maxs, a.pv, a.pyramid, a.width, a.height);
+      const unsigned long long s = __ballot(survives), start = __ballot(base + lane < w_total && it.cluster == 0u);
       if (lane == 0u) a.words[base >> 6] = make_ulonglong2(s, start);
     }
   }
@@ -359,9 +448,11 @@ __device__ __forceinline__ unsigned long long cluster_head_mask(const ClusterArg
   return w.x & (w.y | ~((w.x << 1) | before));
 }
 
-// heads: the head and survivor counts of every tile of 256 words
-static __global__ __launch_bounds__(kClusterThreads) __attribute__((unused)) void mip_cluster_heads_kernel(const ClusterArgs a) {
+// heads: the head and survivor counts of every tile of 256 words; kRecord (FIRST): and the candidates of the record's words
+template <bool kRecord>
+__global__ __launch_bounds__(kClusterThreads) void mip_cluster_heads_kernel(const ClusterArgs a) {
   __shared__ uint32_t s_heads[kWaves], s_survivors[kWaves];
+  __shared__ uint32_t s_candidates[kRecord ? kWaves : 1u];
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t w_total = a.scalars[kClusterScW];
   const uint32_t n_words = cluster_survive_words(w_total), n_tiles = cluster_head_tiles(w_total);
@@ -375,6 +466,10 @@ static __global__ __launch_bounds__(kClusterThreads) __attribute__((unused)) voi
       s_heads[wave] = heads;
       s_survivors[wave] = survivors;
     }
+    if constexpr (kRecord) {
+      const uint32_t candidates = wave_sum(valid ? (uint32_t)__popcll(a.record_words[word]) : 0u);
+      if (lane == 0u) s_candidates[wave] = candidates;
+    }
     __syncthreads();
     if (threadIdx.x == 0u) {
       uint32_t th = 0, ts = 0;
@@ -385,19 +480,33 @@ static __global__ __launch_bounds__(kClusterThreads) __attribute__((unused)) voi
       }
       a.tile_heads[tile] = th;
       a.tile_survivors[tile] = ts;
+      if constexpr (kRecord) {
+        uint32_t tc = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kWaves; ++w) tc += s_candidates[w];
+        a.tile_candidates[tile] = tc;
+      }
     }
     __syncthreads();  // the sums are free for the next tile
   }
 }
 
 // epilogue: the head counts become exclusive prefixes; the count, the stats and the status of the call. One workgroup.
-static __global__ __launch_bounds__(kClusterThreads) __attribute__((unused)) void mip_cluster_epilogue_kernel(const ClusterArgs a) {
+// kRecord (FIRST): and the record's header — {W, members, candidates, 0}, or that of a call that did not run.
+template <bool kRecord>
+__global__ __launch_bounds__(kClusterThreads) void mip_cluster_epilogue_kernel(const ClusterArgs a) {
   __shared__ uint32_t s_wave[kWaves];
   const uint32_t n_tiles = cluster_head_tiles(a.scalars[kClusterScW]);  // 0 when the call does not run
   uint32_t heads_before = 0, survivors = 0;
+  uint32_t candidates = 0;
   for (uint32_t first = 0; first < n_tiles; first += kClusterThreads) {
     const uint32_t t = first + threadIdx.x;
     uint32_t th, ts;
+    if constexpr (kRecord) {
+      uint32_t tc;
+      (void)batch_block_scan(t < n_tiles ? a.tile_candidates[t] : 0u, s_wave, tc);
+      candidates += tc;
+    }
     const uint32_t excl = batch_block_scan(t < n_tiles ? a.tile_heads[t] : 0u, s_wave, th);
     (void)batch_block_scan(t < n_tiles ? a.tile_survivors[t] : 0u, s_wave, ts);
     if (t < n_tiles) a.tile_heads[t] = heads_before + excl;
@@ -412,7 +521,14 @@ static __global__ __launch_bounds__(kClusterThreads) __attribute__((unused)) voi
       a.stats[2] = a.scalars[kClusterScWTrue];
       a.stats[3] = a.scalars[kClusterScMembers];
     }
-    if (heads_before > a.cmd_capacity) cluster_raise(a);
+    if (heads_before > a.cmd_capacity) cluster_raise(a, kClusterStatusCapacity);
+    if constexpr (kRecord) {
+      const bool runs = a.scalars[kClusterScRuns] != 0u;
+      a.record_header[0] = runs ? a.scalars[kClusterScW] : kClusterRecordRefused;
+      a.record_header[1] = runs ? a.scalars[kClusterScMembers] : 0u;
+      a.record_header[2] = runs ? candidates : 0u;
+      a.record_header[3] = 0u;
+    }
   }
 }
 

@@ -1,7 +1,7 @@
-// cluster_plan.hpp — the arithmetic of cluster culling (mip_build_clusters, mip_cull_clusters; extension, not reference
-// behaviour) that is not a kernel: how a level is cut into clusters, the bound on a call's work items, the grids and the
-// scratch a call takes, the tiles a looping grid walks, the permutation the diagnostic build puts on them, the index count of
-// a run. Plain C++, no HIP: api_cluster.hip and cluster_kernel.hpp call it, tests/native/cluster_plan_check.cpp enumerates it
+// cluster_plan.hpp — the arithmetic of cluster culling (mip_build_clusters, mip_cull_clusters, mip_cull_clusters_phase;
+// extension, not reference behaviour) that is not a kernel: how a level is cut into clusters, the bound on a call's work items,
+// the grids and the scratch a call takes, the tiles a looping grid walks, the permutation the diagnostic build puts on them,
+// the index count of a run, the size of a two-phase call's record and the work items a record has room for. Plain C++, no HIP: api_cluster.hip and cluster_kernel.hpp call it, tests/native/cluster_plan_check.cpp enumerates it
 // on the CPU over its decision edges.
 #pragma once
 
@@ -50,6 +50,18 @@ constexpr unsigned long long cluster_work_bound(uint32_t n, uint32_t max_cluster
 // Whether a call with W work items runs (else MIP_ERR_CAPACITY, no command written): W < 2^32 and within the bound.
 MIP_CLUSTER_HD constexpr bool cluster_work_fits(unsigned long long w, unsigned long long bound) { return w <= kClusterMaxWork && w <= bound; }
 
+// The record of a two-phase call (mip_cull_clusters_phase): a 16-byte header, then one 64-bit word per 64 work items.
+constexpr unsigned long long kClusterRecordHeaderBytes = 16;
+constexpr uint32_t kClusterRecordRefused = 0xFFFFFFFFu;       // the header's W of a FIRST call that did not run: no running call has it
+constexpr unsigned long long cluster_record_bytes(unsigned long long work_items) {
+  return kClusterRecordHeaderBytes + 8ull * (work_items / 64ull + (work_items % 64ull ? 1ull : 0ull));
+}
+// The most work items a record of `record_bytes` (>= 16) has words for: the bound a phase call's W is held to besides its own.
+constexpr unsigned long long cluster_record_items(unsigned long long record_bytes) {
+  const unsigned long long words = (record_bytes - kClusterRecordHeaderBytes) / 8ull;
+  return words >= (kClusterMaxWork + 63ull) / 64ull ? kClusterMaxWork : words * 64ull;
+}
+
 MIP_CLUSTER_HD constexpr uint32_t cluster_item_tiles(uint32_t w) { return w / kClusterItemTile + (w % kClusterItemTile ? 1u : 0u); }
 MIP_CLUSTER_HD constexpr uint32_t cluster_survive_words(uint32_t w) { return w / 64u + (w % 64u ? 1u : 0u); }
 MIP_CLUSTER_HD constexpr uint32_t cluster_head_tiles(uint32_t w) { return w / kClusterHeadTile + (w % kClusterHeadTile ? 1u : 0u); }
@@ -60,6 +72,7 @@ MIP_CLUSTER_HD constexpr uint32_t cluster_head_tiles(uint32_t w) { return w / kC
 struct ClusterPlan {
   uint32_t instance_tiles;   // workgroups of the count and members kernels
   uint32_t cull_blocks;      // the cull kernel's grid
+  uint32_t retest_blocks;    // the retest kernel's grid (SECOND): it walks the same item tiles
   uint32_t head_blocks;      // the heads and commands kernels' grid
   unsigned long long survive_words;  // 16 bytes each: the survive word and the start word of 64 work items
   uint32_t head_tiles;       // rows of the head counts
@@ -72,6 +85,7 @@ constexpr ClusterPlan plan_cluster_cull(uint32_t n, unsigned long long bound) {
   const unsigned long long item_tiles = (bound + kClusterItemTile - 1u) / kClusterItemTile;
   const unsigned long long head_tiles = (bound + kClusterHeadTile - 1u) / kClusterHeadTile;
   p.cull_blocks = item_tiles < 1u ? 1u : item_tiles < kClusterMaxBlocks ? (uint32_t)item_tiles : kClusterMaxBlocks;
+  p.retest_blocks = p.cull_blocks;
   p.head_blocks = head_tiles < 1u ? 1u : head_tiles < kClusterMaxBlocks ? (uint32_t)head_tiles : kClusterMaxBlocks;
   p.survive_words = (bound + 63u) / 64u;
   p.head_tiles = head_tiles < 1u ? 1u : (uint32_t)head_tiles;

@@ -9,7 +9,7 @@
 //                     (batch_kernel.hpp) under the key policies of batch_lods_kernel.hpp, batch_views_kernel.hpp and
 //                     batch_sorted_kernel.hpp, planned by batch_plan.hpp and run by one pass driver; mip_merge_batches
 //                     (batch_merge_kernel.hpp, batch_merge_plan.hpp)
-//   api_cluster.hip   the cluster-culling extension: mip_build_clusters, mip_cull_clusters (cluster_kernel.hpp, cluster_plan.hpp)
+//   api_cluster.hip   the cluster-culling extension: mip_build_clusters, mip_cull_clusters, mip_cull_clusters_phase (cluster_kernel.hpp, cluster_plan.hpp)
 // (round 3 had all of it in one 2 224-line mip_api.hip)
 #pragma once
 
@@ -138,11 +138,13 @@ struct MipContext {
     void* d_words = nullptr;            // 16 bytes per 64 work items: the survive word and the start word
     uint32_t* d_tile_heads = nullptr;   // per head tile: heads
     uint32_t* d_tile_survivors = nullptr;  //              survivors
-    size_t words_cap = 0, head_tiles_cap = 0, survivor_tiles_cap = 0;
+    uint32_t* d_tile_candidates = nullptr;  //           the record's candidates (a FIRST call of mip_cull_clusters_phase)
+    size_t words_cap = 0, head_tiles_cap = 0, survivor_tiles_cap = 0, candidate_tiles_cap = 0;
   };
   std::vector<ClusterScratch> cluster_scratch;
-  uint32_t* h_cluster_status = nullptr;  // pinned, device-visible, two words per frame slot: an asynchronous / a synchronous cull of the slot overflowed
+  uint32_t* h_cluster_status = nullptr;  // pinned, device-visible, two words per frame slot: the code an asynchronous / a synchronous cull of the slot raised
   hipEvent_t cluster_pyramid_ready = nullptr;  // orders a cull behind a pyramid built on another slot's stream
+  hipEvent_t cluster_record_written = nullptr;  // behind the last FIRST call of mip_cull_clusters_phase: its SECOND call waits for it, on whichever slot's stream
   std::vector<FrameSlot> view_states;  // mip_run_views: one prefix state per view, all on `stream`
   hipStream_t stream = nullptr;  // = slots[0].stream: uploads, merges, timing
   // resident inputs
@@ -344,7 +346,8 @@ int32_t run_frame(MipContext* ctx, const MipFrame* frame, const MipOutputs* out,
 void batch_release(MipContext* ctx);                  // api_batch.hip: the batched-draws scratch, for mip_destroy
 int32_t check_policy(MipContext* ctx, const MipLodPolicy* policy);  // api_batch.hip: MipLodPolicy as the header states it
 void cluster_release(MipContext* ctx);                // api_cluster.hip: the cluster table and the culls' scratch, for mip_destroy
-// api_cluster.hip: the status mip_wait returns — `rc`, or MIP_ERR_CAPACITY when an asynchronous mip_cull_clusters overflowed
+// api_cluster.hip: the status mip_wait returns — `rc`, or MIP_ERR_CAPACITY when an asynchronous mip_cull_clusters overflowed,
+// MIP_ERR_DEVICE when an asynchronous SECOND call of mip_cull_clusters_phase met a record that is not its own
 int32_t cluster_wait_status(MipContext* ctx, int32_t rc);
 int32_t launch_occluded_frame(MipContext* ctx, const MipOcclusion* occ, mip::KernelArgs& a, const mip::LaunchPlan& plan, hipStream_t stream);  // api_occlusion.hip
 

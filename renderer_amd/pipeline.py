@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipClusterOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+from ._lib import (MipBatchOutputs, MipClusterOutputs, MipClusterRecord, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
                    MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
@@ -153,6 +153,25 @@ def make_cluster_outputs(cluster_cmds, cmd_capacity, cmd_count, stats=0, work_ca
     o.cmd_count = cmd_count or None
     o.stats = stats or None
     return o
+
+
+def cluster_record_bytes(work_items):
+    """mip_cluster_record_bytes: bytes of a two-phase record for `work_items` (instance, cluster) items: a 16-byte header and
+    one 64-bit word per 64 items."""
+    return 16 + 8 * ((int(work_items) + 63) // 64)
+
+
+def make_cluster_record(phase, record, record_bytes):
+    """A MipClusterRecord for cull_clusters_phase: phase MIP_CLUSTER_PHASE_FIRST / _SECOND (or "first" / "second"), a device
+    pointer to the caller's 16-byte aligned record and the room behind it (cluster_record_bytes of the call's bound on W)."""
+    if isinstance(phase, str):
+        phase = {"first": _lib.MIP_CLUSTER_PHASE_FIRST, "second": _lib.MIP_CLUSTER_PHASE_SECOND}[phase]
+    r = MipClusterRecord()
+    r.struct_size = C.sizeof(MipClusterRecord)
+    r.phase = int(phase)
+    r.record = record or None
+    r.record_bytes = int(record_bytes)
+    return r
 
 
 def make_frame(planes, cam_pos, first_instance_base=0, first_index_base=0, pv=None):
@@ -626,6 +645,17 @@ class InstancePipeline:
         asynchronous call) when the runs do not fit cmd_capacity or the work items exceed work_capacity."""
         self._check(self._lib.mip_cull_clusters(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                 C.addressof(occlusion) if occlusion is not None else None, C.addressof(outputs)))
+
+    def cull_clusters_phase(self, frame, visible_bitmap_ptr, policy, outputs, occlusion, record):
+        """mip_cull_clusters_phase: cull_clusters in two phases around the frame's own depth. With a FIRST `record`
+        (make_cluster_record) the outputs are cull_clusters' under `occlusion` (last frame's pyramid) and the record names every
+        cluster that passed the planes and failed the Hi-Z test; with a SECOND record — the same frame, bitmap and policy,
+        `occlusion` the pyramid rebuilt from what phase 1 drew — exactly those clusters are tested again and the ones visible
+        now are written, one command per run. The context orders SECOND behind FIRST. MIP_ERR_DEVICE (from wait() for an
+        asynchronous call) when the record's header does not match the call's work items and members."""
+        self._check(self._lib.mip_cull_clusters_phase(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                      C.addressof(occlusion) if occlusion is not None else None, C.addressof(outputs),
+                                                      C.addressof(record) if record is not None else None))
 
     # -- diagnostics --
     def timings(self):
