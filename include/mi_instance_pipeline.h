@@ -805,7 +805,7 @@ int32_t mip_merge_batches(MipContext* ctx, const void* chunks, uint32_t n_chunks
  * built (mip_build_depth_pyramid) for the next run need no wait. Scratch is the call's own, per frame slot, allocated at
  * first use and grown by a larger call; with work_capacity = 0 it is sized for N x the largest C (16 bytes per 64 work
  * items), so a scene of large meshes should state its bound.
- * OUT OF SCOPE: a normal-cone back-face test; feeding the per-triangle stage from surviving clusters; views, shards, skinned
+ * OUT OF SCOPE: a normal-cone back-face test (the per-triangle test on surviving clusters is mip_cull_cluster_triangles); views, shards, skinned
  * instances, mip_run_many and recorded graphs; batch_model. */
 #define MIP_CLUSTER_TRIANGLES 64u
 typedef struct MipClusterOutputs {
@@ -883,6 +883,52 @@ typedef struct MipClusterRecord {
 uint64_t mip_cluster_record_bytes(uint64_t work_items);
 int32_t mip_cull_clusters_phase(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
                                 const MipOcclusion* occ, const MipClusterOutputs* out, const MipClusterRecord* rec);
+
+/* ---- Extension: per-triangle culling of surviving clusters — the instance -> cluster -> triangle pipeline ---------------
+ * mip_cull_cluster_triangles is mip_cull_clusters followed by the per-triangle stage's test on the triangles of the clusters
+ * that survived: instead of ranges of the source index buffer it writes ONE culled index stream and commands into it.
+ * NOT a reference behaviour; checked against this repository's restatement (tests/cluster_triangle_restatement.py) only.
+ * MEMBERS, WORK ITEMS, W, SURVIVES and HEAD are the words of mip_cull_clusters above; mip_cull_clusters itself is unchanged.
+ * frame->planes, frame->pv, frame->cam_pos and frame->first_instance_base are read; frame->first_index_base is not. No
+ * `model` buffer is an input.
+ *
+ * TRI_SURVIVES(i, c, t), for a surviving item (i, c) and a triangle t of cluster c — triangle t of the level is
+ * indices[index_offset[lod] + 3t .. + 3) over vertices[vertex_offset + index]: the triangle survives iff the per-triangle
+ * stage's test does NOT cull it. clip = pv * (model * vec4(v, 1)) as column combinations left to right, no FMA; culled iff the
+ * determinant of the xyw columns is > 0, or all three corners lie beyond one x or y NDC bound. `model` is the sixteen floats
+ * mip_run writes to `model` for instance i, non-finite rows included; the call forms it from the instance columns.
+ * INDEX STREAM: for every surviving triangle its three source index values, as the per-triangle stage appends them, packed
+ * densely from word 0 of culled_indices in (i, c, t) order. Words at or behind 3 x (surviving triangles) are never touched.
+ * COMMANDS: one per HEAD, in (i, c) order, at the entry mip_cull_clusters would use: indexCount = 3 x the surviving triangles
+ * of the run's clusters, firstIndex = 3 x the surviving triangles of all items in front of the head, instanceCount = 1,
+ * vertexOffset = the mesh's, firstInstance = first_instance_base + i. A run none of whose triangles survives KEEPS its command
+ * with indexCount = 0, a legal draw that draws nothing. cmd_count = min(heads, cmd_capacity).
+ * stats (optional, 6 words): {heads, surviving clusters, W, members, surviving triangles, triangles tested} — tested = the
+ * triangles of the surviving clusters; the last two mod 2^32.
+ * OVERFLOW, reported as mip_cull_clusters reports (WHO REPORTS AN OVERFLOW above). WORK overflow, as mip_cull_clusters:
+ * cmd_count = 0, stats = {0, 0, W mod 2^32, members, 0, 0}, nothing else written. INDEX overflow, 3 x surviving triangles >
+ * index_capacity or >= 2^32: MIP_ERR_CAPACITY, cmd_count = 0, no command and no index written, stats holds the true six values
+ * — size the buffer by stats[4] and call again. COMMAND overflow: the first cmd_capacity commands exactly as with room, the
+ * index stream complete, MIP_ERR_CAPACITY. The context stays usable in every case. N = 0: a zero count and six zero stats.
+ * REFUSED, nothing written: everything mip_cull_clusters refuses; a NULL or misaligned culled_indices and a wrong struct_size
+ * are MIP_ERR_INVALID_ARGUMENT.
+ * ORDERING and scratch are mip_cull_clusters'; the scratch per frame slot is 12 bytes per work item of the bound larger (a
+ * triangle word and a prefix per item) — 110 MB at 9.1 M items — so, again, a scene of large meshes should set work_capacity.
+ * OUT OF SCOPE: the two-phase record; views, shards and skinned instances; mip_run_many and recorded graphs; dropping empty
+ * commands; first_index_base. */
+typedef struct MipClusterTriangleOutputs {
+  uint32_t struct_size;      /* = sizeof(MipClusterTriangleOutputs) */
+  uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
+  void* cluster_cmds;        /* DEVICE: room for cmd_capacity MipDrawIndexedIndirectCommand */
+  uint32_t cmd_capacity;     /* commands that fit */
+  uint32_t work_capacity;    /* the caller's bound on W; 0 = N x the largest C of the table */
+  uint32_t* cmd_count;       /* DEVICE: commands written */
+  uint32_t* stats;           /* DEVICE, optional, 6 words */
+  void* culled_indices;      /* DEVICE, 4-byte aligned: room for index_capacity 32-bit indices */
+  uint32_t index_capacity;   /* indices that fit */
+} MipClusterTriangleOutputs; /* 56 B */
+int32_t mip_cull_cluster_triangles(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                   const MipOcclusion* occ, const MipClusterTriangleOutputs* out);
 
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).

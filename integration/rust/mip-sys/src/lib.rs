@@ -182,6 +182,20 @@ pub struct MipClusterOutputs {
     pub stats: *mut u32,
 }
 
+/// Outputs of mip_cull_cluster_triangles: MipClusterOutputs' fields, then the culled index stream (see the header).
+#[repr(C)]
+pub struct MipClusterTriangleOutputs {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub cluster_cmds: *mut c_void,
+    pub cmd_capacity: u32,
+    pub work_capacity: u32,
+    pub cmd_count: *mut u32,
+    pub stats: *mut u32,
+    pub culled_indices: *mut c_void,
+    pub index_capacity: u32,
+}
+
 /// Phases of mip_cull_clusters_phase.
 pub const MIP_CLUSTER_PHASE_FIRST: u32 = 1;
 pub const MIP_CLUSTER_PHASE_SECOND: u32 = 2;
@@ -290,6 +304,9 @@ extern "C" {
     /// mip_cull_clusters in two phases: FIRST records the clusters the Hi-Z test alone removed, SECOND tests them again.
     pub fn mip_cull_clusters_phase(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
                                    occ: *const MipOcclusion, out: *const MipClusterOutputs, rec: *const MipClusterRecord) -> i32;
+    /// mip_cull_clusters, then the per-triangle test on the surviving clusters: one culled index stream, commands into it.
+    pub fn mip_cull_cluster_triangles(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
+                                      occ: *const MipOcclusion, out: *const MipClusterTriangleOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -308,6 +325,7 @@ const _: [u8; 48] = [0; std::mem::size_of::<MipViewBatchOutputs>()];
 const _: [u8; 16] = [0; std::mem::size_of::<MipBatchChunkHeader>()];
 const _: [u8; 40] = [0; std::mem::size_of::<MipClusterOutputs>()];
 const _: [u8; 24] = [0; std::mem::size_of::<MipClusterRecord>()];
+const _: [u8; 56] = [0; std::mem::size_of::<MipClusterTriangleOutputs>()];
 const _: [u8; 104] = [0; std::mem::size_of::<MipOcclusion>()];
 
 impl Pipeline {

@@ -58,7 +58,7 @@ EXPORTS = (
     "mip_set_instances_device", "mip_update_instances", "mip_set_geometry", "mip_set_blas_addresses", "mip_run", "mip_run_many", "mip_wait", "mip_merge_draw_lists", "mip_merge_wire_lists", "mip_merge_wire_lists_packed", "mip_wire_index_bits", "mip_light_draw_lists", "mip_set_skeleton", "mip_set_poses", "mip_run_skinned", "mip_run_views", "mip_comm_unique_id", "mip_comm_init", "mip_comm_destroy", "mip_run_sharded", "mip_import_external_fd", "mip_release_external", "mip_import_external_semaphore_fd", "mip_external_semaphore_on_device", "mip_wait_external", "mip_signal_external", "mip_release_external_semaphore", "mip_last_error",
     "mip_get_timings", "mip_depth_pyramid_bytes", "mip_build_depth_pyramid", "mip_run_occluded", "mip_batch_draws", "mip_batch_draws_lods", "mip_batch_draws_ordered", "mip_batch_draws_sorted", "mip_batch_draws_views", "mip_batch_draws_shard", "mip_merge_batches", "mip_reset_timings", "mip_instance_count",
     "mip_build_clusters", "mip_cluster_count", "mip_read_cluster_boxes", "mip_cull_clusters",
-    "mip_cluster_record_bytes", "mip_cull_clusters_phase",
+    "mip_cluster_record_bytes", "mip_cull_clusters_phase", "mip_cull_cluster_triangles",
 )
 
 
@@ -178,6 +178,15 @@ class MipClusterOutputs(C.Structure):
         ("work_capacity", C.c_uint32),
         ("cmd_count", C.c_void_p),
         ("stats", C.c_void_p),
+    ]
+
+
+class MipClusterTriangleOutputs(C.Structure):
+    """mip_cull_cluster_triangles' outputs (include/mi_instance_pipeline.h): MipClusterOutputs' fields, the culled index
+    stream and its capacity, 56 B."""
+    _fields_ = MipClusterOutputs._fields_ + [
+        ("culled_indices", C.c_void_p),
+        ("index_capacity", C.c_uint32),
     ]
 
 
@@ -346,6 +355,7 @@ def load_library():
     _declare_newer(lib, "mip_cull_clusters", [vp, vp, vp, vp, vp, vp])
     _declare_newer(lib, "mip_cluster_record_bytes", [C.c_uint64], restype=C.c_uint64)
     _declare_newer(lib, "mip_cull_clusters_phase", [vp, vp, vp, vp, vp, vp, vp])
+    _declare_newer(lib, "mip_cull_cluster_triangles", [vp, vp, vp, vp, vp, vp])
     lib.mip_instance_count.argtypes = [vp]
     lib.mip_instance_count.restype = C.c_uint32
     _lib = lib

@@ -3,13 +3,17 @@
 // the device from the resident geometry; mip_cull_clusters runs the frustum test and (optionally) the Hi-Z test of the
 // instance level on every cluster of every member of a bitmap and writes one command per run of surviving clusters;
 // mip_cull_clusters_phase is the same call in two phases: FIRST also records the clusters that passed the planes and failed the
-// Hi-Z test, SECOND tests exactly those again under a new pyramid.
-// cluster_plan.hpp holds the arithmetic and the launch plan; the kernels (cluster_kernel.hpp) are instantiated here and only here.
+// Hi-Z test, SECOND tests exactly those again under a new pyramid; mip_cull_cluster_triangles runs the per-triangle stage's test
+// on the triangles of the surviving clusters and writes one culled index stream with the commands into it.
+// cluster_plan.hpp and cluster_triangle_plan.hpp hold the arithmetic and the launch plans; the kernels (cluster_kernel.hpp,
+// cluster_triangle_kernel.hpp) are instantiated here and only here.
 #include "context.hpp"
 #include "cluster_kernel.hpp"
+#include "cluster_triangle_kernel.hpp"
 
 static_assert(sizeof(MipClusterOutputs) == 40, "MipClusterOutputs is part of the ABI");
 static_assert(sizeof(MipClusterRecord) == 24, "MipClusterRecord is part of the ABI");
+static_assert(sizeof(MipClusterTriangleOutputs) == 56, "MipClusterTriangleOutputs is part of the ABI");
 static_assert(mip::kClusterFirst == MIP_CLUSTER_PHASE_FIRST && mip::kClusterSecond == MIP_CLUSTER_PHASE_SECOND, "cluster_kernel.hpp restates the header");
 static_assert(MIP_CLUSTER_TRIANGLES == mip::kClusterTriangles, "cluster_plan.hpp restates the header");
 
@@ -107,6 +111,16 @@ int32_t ensure_scratch(MipContext* ctx, MipContext::ClusterScratch& cs, const mi
   return MIP_OK;
 }
 
+// What mip_cull_cluster_triangles takes on top (cluster_triangle_plan.hpp): 12 bytes per work item of the bound.
+int32_t ensure_triangle_scratch(MipContext* ctx, MipContext::ClusterScratch& cs, const mip::ClusterTrianglePlan& plan) {
+  if (!cs.d_tri_scalars) MIP_HIP(ctx, hipMalloc(&cs.d_tri_scalars, mip::kClusterTriScWords * 4));
+  if (int32_t rc = grow(ctx, &cs.d_triangle_words, &cs.triangle_words_cap, (size_t)plan.triangle_words, 8)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_item_prefix, &cs.item_prefix_cap, (size_t)plan.item_prefixes, 4)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_word_total, &cs.word_total_cap, (size_t)plan.word_totals, 4)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_tile_triangles, &cs.tile_triangles_cap, (size_t)plan.item_tiles, 8)) return rc;
+  return MIP_OK;
+}
+
 // The event a SECOND call waits for: behind everything the FIRST call enqueued.
 int32_t record_written(MipContext* ctx, hipStream_t stream) {
   if (!ctx->cluster_record_written) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_record_written, hipEventDisableTiming));
@@ -114,8 +128,8 @@ int32_t record_written(MipContext* ctx, hipStream_t stream) {
   return MIP_OK;
 }
 
-template <class Kernel>
-int32_t launch(MipContext* ctx, Kernel kernel, uint32_t blocks, hipStream_t stream, const mip::ClusterArgs& a) {
+template <class Kernel, class Args>
+int32_t launch(MipContext* ctx, Kernel kernel, uint32_t blocks, hipStream_t stream, const Args& a) {
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(mip::kClusterThreads), 0, stream, a);
   MIP_HIP(ctx, hipGetLastError());
   return MIP_OK;
@@ -123,8 +137,10 @@ int32_t launch(MipContext* ctx, Kernel kernel, uint32_t blocks, hipStream_t stre
 
 // Every check first (a refused call writes nothing), then the seven launches on the stream of the frame issued last.
 // rec == null: mip_cull_clusters; else a phase of mip_cull_clusters_phase (`phased`: the entry point, which refuses a null rec).
+// tri != null: mip_cull_cluster_triangles — `out` holds its leading fields; the triangle test, its scan, the write and the
+// commands into the culled stream take the place of the epilogue and the commands kernel (nine launches).
 int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy, const MipOcclusion* occ,
-                      const MipClusterOutputs* out, const MipClusterRecord* rec, bool phased) {
+                      const MipClusterOutputs* out, const MipClusterRecord* rec, bool phased, const MipClusterTriangleOutputs* tri = nullptr) {
   if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
   if (out->struct_size != sizeof(MipClusterOutputs))
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipClusterOutputs));
@@ -163,7 +179,7 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   const uint32_t n = ctx->n;
   if (n == 0) {  // nothing to test: zeros
     MIP_HIP(ctx, hipMemsetAsync(out->cmd_count, 0, 4, stream));
-    if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, 16, stream));
+    if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, tri ? 4 * mip::kClusterTriangleStats : 16, stream));
     if (first) {
       MIP_HIP(ctx, hipMemsetAsync(rec->record, 0, mip::kClusterRecordHeaderBytes, stream));
       if (int32_t rc = record_written(ctx, stream)) return rc;
@@ -184,6 +200,9 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   if (ctx->cluster_scratch.size() != ctx->slots.size()) ctx->cluster_scratch.resize(ctx->slots.size());
   MipContext::ClusterScratch& cs = ctx->cluster_scratch[slot];
   if (int32_t rc = ensure_scratch(ctx, cs, plan, first)) return rc;
+  const mip::ClusterTrianglePlan tri_plan = mip::plan_cluster_triangles(n, bound);
+  if (tri)
+    if (int32_t rc = ensure_triangle_scratch(ctx, cs, tri_plan)) return rc;
   if (occ && ctx->next_slot != slot) {
     // a pyramid built for the next run sits on that slot's stream: this call goes behind what that stream holds now
     if (!ctx->cluster_pyramid_ready) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_pyramid_ready, hipEventDisableTiming));
@@ -259,10 +278,32 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   if (int32_t rc = first ? launch(ctx, mip::mip_cluster_heads_kernel<true>, plan.head_blocks, stream, a)
                          : launch(ctx, mip::mip_cluster_heads_kernel<false>, plan.head_blocks, stream, a))
     return rc;
-  if (int32_t rc = first ? launch(ctx, mip::mip_cluster_epilogue_kernel<true>, 1, stream, a)
-                         : launch(ctx, mip::mip_cluster_epilogue_kernel<false>, 1, stream, a))
-    return rc;
-  if (int32_t rc = launch(ctx, mip::mip_cluster_commands_kernel, plan.head_blocks, stream, a)) return rc;
+  if (tri) {
+    mip::ClusterTriangleArgs ta{};
+    ta.c = a;
+    ta.vertices = ctx->d_vertices;
+    ta.indices = ctx->d_indices;
+    ta.vertex_bytes = (unsigned long long)ctx->n_vertices * 12ull;
+    ta.geometry_finite = ctx->geometry_finite ? 1u : 0u;
+    std::memcpy(ta.pv, frame->pv, sizeof ta.pv);
+    ta.triangle_words = cs.d_triangle_words;
+    ta.item_prefix = cs.d_item_prefix;
+    ta.word_total = cs.d_word_total;
+    ta.tile_kept = cs.d_tile_triangles;
+    ta.tile_tested = cs.d_tile_triangles + tri_plan.item_tiles;
+    ta.tri_scalars = cs.d_tri_scalars;
+    ta.culled_indices = static_cast<uint32_t*>(tri->culled_indices);
+    ta.index_capacity = tri->index_capacity;
+    if (int32_t rc = launch(ctx, mip::mip_cluster_triangle_test_kernel, tri_plan.test_blocks, stream, ta)) return rc;
+    if (int32_t rc = launch(ctx, mip::mip_cluster_triangle_scan_kernel, 1, stream, ta)) return rc;
+    if (int32_t rc = launch(ctx, mip::mip_cluster_triangle_write_kernel, tri_plan.write_blocks, stream, ta)) return rc;
+    if (int32_t rc = launch(ctx, mip::mip_cluster_triangle_commands_kernel, tri_plan.command_blocks, stream, ta)) return rc;
+  } else {
+    if (int32_t rc = first ? launch(ctx, mip::mip_cluster_epilogue_kernel<true>, 1, stream, a)
+                           : launch(ctx, mip::mip_cluster_epilogue_kernel<false>, 1, stream, a))
+      return rc;
+    if (int32_t rc = launch(ctx, mip::mip_cluster_commands_kernel, plan.head_blocks, stream, a)) return rc;
+  }
   if (first)
     if (int32_t rc = record_written(ctx, stream)) return rc;
   if (int32_t rc = finish(ctx, stream, async)) return rc;
@@ -270,6 +311,8 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
     const uint32_t code = *status;
     *status = 0;
     if (code & mip::kClusterStatusDevice) return fail(ctx, MIP_ERR_DEVICE, "%s", kNotItsRecord);
+    if (tri)
+      return fail(ctx, MIP_ERR_CAPACITY, "mip_cull_cluster_triangles: more surviving indices than index_capacity or 2^32 - 1 (no command and no index is written; stats[4] holds the surviving triangles), more runs than cmd_capacity (the first cmd_capacity commands and the whole stream are written), or more work items than work_capacity / 2^32 - 1 (nothing is written)");
     return fail(ctx, MIP_ERR_CAPACITY, "mip_cull_clusters: more runs than cmd_capacity (the first cmd_capacity commands are written), or more work items than work_capacity / 2^32 - 1 / the record has words for (nothing is written); stats holds the counts");
   }
   return MIP_OK;
@@ -304,6 +347,11 @@ void cluster_release(MipContext* ctx) {
     (void)hipFree(cs.d_tile_heads);
     (void)hipFree(cs.d_tile_survivors);
     (void)hipFree(cs.d_tile_candidates);
+    (void)hipFree(cs.d_tri_scalars);
+    (void)hipFree(cs.d_triangle_words);
+    (void)hipFree(cs.d_item_prefix);
+    (void)hipFree(cs.d_word_total);
+    (void)hipFree(cs.d_tile_triangles);
   }
   ctx->cluster_scratch.clear();
   if (ctx->h_cluster_status) (void)hipHostFree(ctx->h_cluster_status);
@@ -360,6 +408,26 @@ int32_t mip_cull_clusters_phase(MipContext* ctx, const MipFrame* frame, const ui
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
   if (int32_t rc = check_policy(ctx, policy)) return rc;
   return cull_clusters(ctx, frame, visible_bitmap, policy, occ, out, rec, true);
+}
+
+int32_t mip_cull_cluster_triangles(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                   const MipOcclusion* occ, const MipClusterTriangleOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  if (!out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
+  if (out->struct_size != sizeof(MipClusterTriangleOutputs))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterTriangleOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipClusterTriangleOutputs));
+  if (!out->culled_indices || (uintptr_t)out->culled_indices % 4u != 0u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "culled_indices is NULL or not 4-byte aligned");
+  MipClusterOutputs leading{};  // the fields the two structs share, for the checks and the launches they share
+  leading.struct_size = sizeof(MipClusterOutputs);
+  leading.flags = out->flags;
+  leading.cluster_cmds = out->cluster_cmds;
+  leading.cmd_capacity = out->cmd_capacity;
+  leading.work_capacity = out->work_capacity;
+  leading.cmd_count = out->cmd_count;
+  leading.stats = out->stats;
+  return cull_clusters(ctx, frame, visible_bitmap, policy, occ, &leading, nullptr, false, out);
 }
 
 }  // extern "C"

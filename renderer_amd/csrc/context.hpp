@@ -140,6 +140,13 @@ struct MipContext {
     uint32_t* d_tile_survivors = nullptr;  //              survivors
     uint32_t* d_tile_candidates = nullptr;  //           the record's candidates (a FIRST call of mip_cull_clusters_phase)
     size_t words_cap = 0, head_tiles_cap = 0, survivor_tiles_cap = 0, candidate_tiles_cap = 0;
+    // mip_cull_cluster_triangles (cluster_triangle_plan.hpp): 12 bytes per work item of the call's bound on top
+    uint32_t* d_tri_scalars = nullptr;
+    unsigned long long* d_triangle_words = nullptr;  // per work item: the ballot of its cluster's surviving triangles
+    uint32_t* d_item_prefix = nullptr;  // per work item + 1: the surviving triangles in front of it
+    uint32_t* d_word_total = nullptr;   // per survive word: the surviving triangles of its 64 items
+    uint32_t* d_tile_triangles = nullptr;  // per item tile: surviving triangles (then their prefix), behind them the tested ones
+    size_t triangle_words_cap = 0, item_prefix_cap = 0, word_total_cap = 0, tile_triangles_cap = 0;
   };
   std::vector<ClusterScratch> cluster_scratch;
   uint32_t* h_cluster_status = nullptr;  // pinned, device-visible, two words per frame slot: the code an asynchronous / a synchronous cull of the slot raised

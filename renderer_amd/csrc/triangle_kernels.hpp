@@ -254,6 +254,7 @@ __device__ __forceinline__ uint32_t chunk_walk(const TriangleArgs& a, const Chun
   return survivors;
 }
 
+#ifndef MIP_TRIANGLE_DEVICE_HELPERS_ONLY  // (cluster_triangle_kernel.hpp takes the device helpers above; the kernels stay in stages_tu.hip)
 // Round 5, frames above tri_block_max instances: the range kernel's grid (choice_mode 1) and the wave-per-command grid over the
 // sorted commands (choice_mode 2) are both launched; every workgroup of both — and of the sort and map kernels in front of them
 // — asks this (wave-uniform, from the slot's own command list), and the grid the frame is not for returns at once.
@@ -1238,5 +1239,6 @@ __global__ __launch_bounds__(256, MIP_TRI_CHUNK_WAVES_PER_SIMD) void mip_triangl
   if (plan_tri_choice_is_ranges(ca.t.max_lod_tris, stream_slots(ca.t, ca.t.first_index_base, count), count, ca.t.choice_waves)) triangle_ranges_body(ca, count, s_masks);
   else triangle_waves_body(ca.t, count);
 }
+#endif  // MIP_TRIANGLE_DEVICE_HELPERS_ONLY
 
 }  // namespace mip

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipClusterOutputs, MipClusterRecord, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+from ._lib import (MipBatchOutputs, MipClusterOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
                    MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
@@ -152,6 +152,23 @@ def make_cluster_outputs(cluster_cmds, cmd_capacity, cmd_count, stats=0, work_ca
     o.work_capacity = int(work_capacity)
     o.cmd_count = cmd_count or None
     o.stats = stats or None
+    return o
+
+
+def make_cluster_triangle_outputs(cluster_cmds, cmd_capacity, cmd_count, culled_indices, index_capacity, stats=0, work_capacity=0, async_=False):
+    """A MipClusterTriangleOutputs for cull_cluster_triangles: make_cluster_outputs' fields, a device pointer to room for
+    index_capacity 32-bit indices of the culled stream, and (optional) SIX stats words {heads, surviving clusters, W, members,
+    surviving triangles, triangles tested}."""
+    o = MipClusterTriangleOutputs()
+    o.struct_size = C.sizeof(MipClusterTriangleOutputs)
+    o.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+    o.cluster_cmds = cluster_cmds or None
+    o.cmd_capacity = int(cmd_capacity)
+    o.work_capacity = int(work_capacity)
+    o.cmd_count = cmd_count or None
+    o.stats = stats or None
+    o.culled_indices = culled_indices or None
+    o.index_capacity = int(index_capacity)
     return o
 
 
@@ -656,6 +673,16 @@ class InstancePipeline:
         self._check(self._lib.mip_cull_clusters_phase(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                       C.addressof(occlusion) if occlusion is not None else None, C.addressof(outputs),
                                                       C.addressof(record) if record is not None else None))
+
+    def cull_cluster_triangles(self, frame, visible_bitmap_ptr, policy, outputs, occlusion=None):
+        """mip_cull_cluster_triangles: cull_clusters, then the per-triangle stage's test (frame's pv) on every triangle of the
+        surviving clusters. `outputs` (make_cluster_triangle_outputs) receives the surviving triangles' indices as one dense
+        stream and one command per run of surviving clusters into it — a run with no surviving triangle keeps its command with
+        indexCount 0. MIP_ERR_CAPACITY (from wait() for an asynchronous call) when the stream does not fit index_capacity
+        (nothing is written; stats[4] says how many triangles survive), the runs do not fit cmd_capacity or the work items
+        exceed work_capacity."""
+        self._check(self._lib.mip_cull_cluster_triangles(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                         C.addressof(occlusion) if occlusion is not None else None, C.addressof(outputs)))
 
     # -- diagnostics --
     def timings(self):
