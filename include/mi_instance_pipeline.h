@@ -805,8 +805,8 @@ int32_t mip_merge_batches(MipContext* ctx, const void* chunks, uint32_t n_chunks
  * built (mip_build_depth_pyramid) for the next run need no wait. Scratch is the call's own, per frame slot, allocated at
  * first use and grown by a larger call; with work_capacity = 0 it is sized for N x the largest C (16 bytes per 64 work
  * items), so a scene of large meshes should state its bound.
- * OUT OF SCOPE: a normal-cone back-face test (the per-triangle test on surviving clusters is mip_cull_cluster_triangles); views, shards, skinned
- * instances, mip_run_many and recorded graphs; batch_model. */
+ * OUT OF SCOPE: views, shards, skinned instances, mip_run_many and recorded graphs; batch_model. (The per-triangle test on
+ * surviving clusters is mip_cull_cluster_triangles; the normal-cone back-face test is mip_cull_clusters_cone.) */
 #define MIP_CLUSTER_TRIANGLES 64u
 typedef struct MipClusterOutputs {
   uint32_t struct_size;      /* = sizeof(MipClusterOutputs) */
@@ -929,6 +929,74 @@ typedef struct MipClusterTriangleOutputs {
 } MipClusterTriangleOutputs; /* 56 B */
 int32_t mip_cull_cluster_triangles(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
                                    const MipOcclusion* occ, const MipClusterTriangleOutputs* out);
+
+/* ---- Extension: cluster culling with normal cones — the back-face test per 64-triangle cluster --------------------------
+ * The per-triangle stage culls a triangle whose clip-space determinant is > 0 (back-facing). A cluster all of whose triangles
+ * are back-facing for a view is found here from 32 bytes, before an index is loaded. NOT a reference behaviour; checked against
+ * this repository's restatement (tests/cluster_cone_restatement.py) only. Every entry point above is unchanged.
+ * All arithmetic below is float, one rounding per written operation (no FMA), sqrtf and / correctly rounded.
+ *
+ * THE CONE TABLE (mip_build_cluster_cones): one cone per cluster of a valid cluster table, 8 floats {axis xyz, k, centre xyz, r},
+ * bucket-major like the boxes, built on the device from the resident geometry; the call returns when it is complete. For
+ * triangle t of the cluster with corners p0, p1, p2 (vertices[vertex_offset + index], in index order):
+ *   e1 = p1 - p0, e2 = p2 - p0 (per component); n = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y - e1.y e2.x);
+ *   len2 = (n.x n.x + n.y n.y) + n.z n.z. The triangle is PROPER iff len2 > 0 and len2 < +inf. nh_t = n / sqrtf(len2).
+ *   AXIS: A = the sum of nh_t over the cluster, per component, as a fixed butterfly over 64 slots (slot t = triangle t, a slot
+ *   without a triangle holds +0): level j = 0..5 replaces every slot v[l] by v[l] + v[l xor 2^j]; float addition is commutative,
+ *   so all slots hold the same bits. aa = (A.x A.x + A.y A.y) + A.z A.z; a = A / sqrtf(aa).
+ *   SPREAD: m = the minimum over the cluster's triangles of (nh.x a.x + nh.y a.y) + nh.z a.z; k = sqrtf(fmaxf(1 - m m, 0)) + 2^-7.
+ *   SPHERE: with lo, hi the cluster's box: centre = (hi + lo) / 2, h = (hi - lo) / 2, r0 = sqrtf((h.x h.x + h.y h.y) + h.z h.z),
+ *   r = r0 + r0 x 2^-7.
+ *   NO CONE — k = +inf, the other seven floats +0 — when a triangle of the cluster is not PROPER (a zero-area triangle is never
+ *   culled by the determinant; NaN and infinite vertices end here), when aa is not > 0 and < +inf, or when m is not > 0.1f.
+ * The margins 2^-7 (on k, absolute) and 2^-7 (on r, relative) make the test below conservative against the rounding of the
+ * build and of the per-frame chain inside a domain: every triangle has len2 >= 2^-10 (e1.e1)(e2.e2), and the cluster centre's
+ * model-space coordinates times s and the instance's position are at most 2^12 s r in magnitude, and s k |d| >= 2^-63 so that no
+ * square underflows (DESIGN section 29 derives it; the library does not check the domain).
+ * The table needs a valid cluster table (MIP_ERR_NOT_READY) and becomes STALE with it: after mip_set_mesh_table,
+ * mip_set_geometry or a new mip_build_clusters the cone calls return MIP_ERR_NOT_READY until it is built again.
+ * mip_read_cluster_cones copies the 8 floats per cluster to HOST memory under mip_read_cluster_boxes' rules.
+ *
+ * THE VIEW (MipClusterCone). eye: the world-space point the view projects from; facing: +1.0f or -1.0f. Write rows x, y, w of
+ * a projection pv as [A | b]: clip.xyw = A (x - e) with e = -A^-1 b, and the per-triangle stage's determinant is
+ * det(A) x (x0 - e) . n_t; so that stage culls triangle t exactly when facing x n_t . (x0 - e) > 0 with facing = sign(det A).
+ * mip_cone_from_pv computes e and facing in double and rounds once; pure host, no context. It returns
+ * MIP_ERR_INVALID_ARGUMENT for a NULL argument, a singular or non-finite A, or an eye that is no finite float (an orthographic
+ * projection has no eye). The eye of a shadow view is the light; frame->cam_pos stays the LOD rule's reference point.
+ *
+ * PER FRAME (mip_cull_clusters_cone, mip_cull_cluster_triangles_cone): mip_cull_clusters / mip_cull_cluster_triangles with
+ * `cone` in front of `out`. MEMBERS, WORK ITEMS, W, HEAD, COMMANDS, TRI_SURVIVES, the index stream, the stats (4 and 6 words),
+ * the three overflow rules, WHO REPORTS AN OVERFLOW, ORDERING and scratch are those calls', with SURVIVES replaced by
+ *   SURVIVES_CONE(i, c) = SURVIVES(i, c) AND NOT CONE_CULLED(i, c).
+ * CONE_CULLED(i, c), with p, q = (i, j, k, w), s the instance's position, rotation and scale and {a, k, centre, r} the cone:
+ *   GUARD: s > 0 and | qq - 1 | <= 2^-20, qq = ((q.i q.i + q.j q.j) + q.k q.k) + q.w q.w. (A non-unit quaternion makes the
+ *   matrix no similarity, a non-positive scale flips the winding: such an instance is never cone-culled.)
+ *   M[r][c] = R[r][c] x s, R the rotation matrix of the model matrix's chain (nalgebra's to_rotation_matrix): the upper 3 x 3
+ *   of the sixteen floats mip_run writes for a finite instance. For r = 0, 1, 2:
+ *   cw[r] = ((M[r][0] centre.x + M[r][1] centre.y) + M[r][2] centre.z) + p[r];  aw[r] = (M[r][0] a.x + M[r][1] a.y) + M[r][2] a.z;
+ *   d = cw - eye;  da = (d.x aw.x + d.y aw.y) + d.z aw.z;  dd = (d.x d.x + d.y d.y) + d.z d.z;
+ *   Av = facing x da - (s s) r;  Bv = ((s k) (s k)) dd.
+ *   CONE_CULLED iff GUARD and Av > 0 and Av Av > Bv and Av and Bv are finite.
+ * NO CONE (k = +inf), a NaN anywhere, an infinite eye and a non-finite instance all fail a comparison: the item is not
+ * cone-culled. This is d . a >= k |d| + r for the cluster's bounding sphere, k = sin(theta), scaled by s and squared; strict
+ * comparisons keep the edge-on tie on the surviving side, as det > 0 does.
+ * REFUSED, nothing written: everything the plain call refuses; a NULL cone, a wrong MipClusterCone.struct_size, flags != 0, a
+ * facing other than +1.0f / -1.0f: MIP_ERR_INVALID_ARGUMENT; no valid cone table: MIP_ERR_NOT_READY.
+ * OUT OF SCOPE: a cone form of mip_cull_clusters_phase; orthographic views; apex-form cones and spheres tighter than the box's;
+ * views, shards, skinned instances, mip_run_many and recorded graphs. */
+typedef struct MipClusterCone {
+  uint32_t struct_size;   /* = sizeof(MipClusterCone) */
+  uint32_t flags;         /* 0 */
+  float eye[3];           /* world-space point the view projects from */
+  float facing;           /* +1.0f or -1.0f, nothing else */
+} MipClusterCone;         /* 24 B */
+int32_t mip_build_cluster_cones(MipContext* ctx);
+int32_t mip_read_cluster_cones(MipContext* ctx, float* host_out, uint32_t capacity_clusters);
+int32_t mip_cone_from_pv(const float pv[16], MipClusterCone* out);
+int32_t mip_cull_clusters_cone(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                               const MipOcclusion* occ, const MipClusterCone* cone, const MipClusterOutputs* out);
+int32_t mip_cull_cluster_triangles_cone(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                        const MipOcclusion* occ, const MipClusterCone* cone, const MipClusterTriangleOutputs* out);
 
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).

@@ -209,6 +209,16 @@ pub struct MipClusterRecord {
     pub record_bytes: u64,
 }
 
+/// The view's side of the normal-cone back-face test (mip_cull_clusters_cone): the point the view projects from and the
+/// sign of its determinant, +1.0 or -1.0. mip_cone_from_pv fills it from a projection.
+#[repr(C)]
+pub struct MipClusterCone {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub eye: [f32; 3],
+    pub facing: f32,
+}
+
 /// Per-frame parameters of the occlusion test (mip_cull_clusters reads pyramid, width, height and pv).
 #[repr(C)]
 pub struct MipOcclusion {
@@ -307,6 +317,16 @@ extern "C" {
     /// mip_cull_clusters, then the per-triangle test on the surviving clusters: one culled index stream, commands into it.
     pub fn mip_cull_cluster_triangles(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
                                       occ: *const MipOcclusion, out: *const MipClusterTriangleOutputs) -> i32;
+    /// Extension: normal cones. One cone per cluster of a valid cluster table; stale with that table.
+    pub fn mip_build_cluster_cones(ctx: *mut MipContext) -> i32;
+    pub fn mip_read_cluster_cones(ctx: *mut MipContext, host_out: *mut f32, capacity_clusters: u32) -> i32;
+    /// Pure host: the eye and the facing of a projection (rows x, y, w of pv), in double, rounded once.
+    pub fn mip_cone_from_pv(pv: *const f32, out: *mut MipClusterCone) -> i32;
+    /// mip_cull_clusters / mip_cull_cluster_triangles with the cone's back-face test in front of the box tests.
+    pub fn mip_cull_clusters_cone(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
+                                  occ: *const MipOcclusion, cone: *const MipClusterCone, out: *const MipClusterOutputs) -> i32;
+    pub fn mip_cull_cluster_triangles_cone(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
+                                           occ: *const MipOcclusion, cone: *const MipClusterCone, out: *const MipClusterTriangleOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -326,6 +346,7 @@ const _: [u8; 16] = [0; std::mem::size_of::<MipBatchChunkHeader>()];
 const _: [u8; 40] = [0; std::mem::size_of::<MipClusterOutputs>()];
 const _: [u8; 24] = [0; std::mem::size_of::<MipClusterRecord>()];
 const _: [u8; 56] = [0; std::mem::size_of::<MipClusterTriangleOutputs>()];
+const _: [u8; 24] = [0; std::mem::size_of::<MipClusterCone>()];
 const _: [u8; 104] = [0; std::mem::size_of::<MipOcclusion>()];
 
 impl Pipeline {

@@ -59,6 +59,7 @@ EXPORTS = (
     "mip_get_timings", "mip_depth_pyramid_bytes", "mip_build_depth_pyramid", "mip_run_occluded", "mip_batch_draws", "mip_batch_draws_lods", "mip_batch_draws_ordered", "mip_batch_draws_sorted", "mip_batch_draws_views", "mip_batch_draws_shard", "mip_merge_batches", "mip_reset_timings", "mip_instance_count",
     "mip_build_clusters", "mip_cluster_count", "mip_read_cluster_boxes", "mip_cull_clusters",
     "mip_cluster_record_bytes", "mip_cull_clusters_phase", "mip_cull_cluster_triangles",
+    "mip_build_cluster_cones", "mip_read_cluster_cones", "mip_cone_from_pv", "mip_cull_clusters_cone", "mip_cull_cluster_triangles_cone",
 )
 
 
@@ -197,6 +198,16 @@ class MipClusterRecord(C.Structure):
         ("phase", C.c_uint32),
         ("record", C.c_void_p),
         ("record_bytes", C.c_uint64),
+    ]
+
+
+class MipClusterCone(C.Structure):
+    """The view's side of the normal-cone test (include/mi_instance_pipeline.h): the eye and the facing, 24 B."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("eye", C.c_float * 3),
+        ("facing", C.c_float),
     ]
 
 
@@ -356,6 +367,11 @@ def load_library():
     _declare_newer(lib, "mip_cluster_record_bytes", [C.c_uint64], restype=C.c_uint64)
     _declare_newer(lib, "mip_cull_clusters_phase", [vp, vp, vp, vp, vp, vp, vp])
     _declare_newer(lib, "mip_cull_cluster_triangles", [vp, vp, vp, vp, vp, vp])
+    _declare_newer(lib, "mip_build_cluster_cones", [vp])
+    _declare_newer(lib, "mip_read_cluster_cones", [vp, vp, C.c_uint32])
+    _declare_newer(lib, "mip_cone_from_pv", [vp, vp])
+    _declare_newer(lib, "mip_cull_clusters_cone", [vp, vp, vp, vp, vp, vp, vp])
+    _declare_newer(lib, "mip_cull_cluster_triangles_cone", [vp, vp, vp, vp, vp, vp, vp])
     lib.mip_instance_count.argtypes = [vp]
     lib.mip_instance_count.restype = C.c_uint32
     _lib = lib

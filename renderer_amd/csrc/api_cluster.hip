@@ -5,15 +5,21 @@
 // mip_cull_clusters_phase is the same call in two phases: FIRST also records the clusters that passed the planes and failed the
 // Hi-Z test, SECOND tests exactly those again under a new pyramid; mip_cull_cluster_triangles runs the per-triangle stage's test
 // on the triangles of the surviving clusters and writes one culled index stream with the commands into it.
-// cluster_plan.hpp and cluster_triangle_plan.hpp hold the arithmetic and the launch plans; the kernels (cluster_kernel.hpp,
-// cluster_triangle_kernel.hpp) are instantiated here and only here.
+// mip_build_cluster_cones gives every cluster of a valid table a normal cone, and mip_cull_clusters_cone /
+// mip_cull_cluster_triangles_cone are the two culls with the cone's back-face test in front of SURVIVES (one new kernel in
+// the cull kernel's place; every other launch is the plain call's).
+// cluster_plan.hpp, cluster_triangle_plan.hpp and cluster_cone_plan.hpp hold the arithmetic and the launch plans; the kernels
+// (cluster_kernel.hpp, cluster_triangle_kernel.hpp, cluster_cone_kernel.hpp) are instantiated here and only here.
 #include "context.hpp"
 #include "cluster_kernel.hpp"
 #include "cluster_triangle_kernel.hpp"
+#include "cluster_cone_kernel.hpp"
 
 static_assert(sizeof(MipClusterOutputs) == 40, "MipClusterOutputs is part of the ABI");
 static_assert(sizeof(MipClusterRecord) == 24, "MipClusterRecord is part of the ABI");
 static_assert(sizeof(MipClusterTriangleOutputs) == 56, "MipClusterTriangleOutputs is part of the ABI");
+static_assert(sizeof(MipClusterCone) == 24, "MipClusterCone is part of the ABI");
+static_assert(sizeof(mip::ClusterConeEntry) == 2 * sizeof(float4), "a cone is the two 16-byte words the kernels load");
 static_assert(mip::kClusterFirst == MIP_CLUSTER_PHASE_FIRST && mip::kClusterSecond == MIP_CLUSTER_PHASE_SECOND, "cluster_kernel.hpp restates the header");
 static_assert(MIP_CLUSTER_TRIANGLES == mip::kClusterTriangles, "cluster_plan.hpp restates the header");
 
@@ -69,6 +75,7 @@ int32_t build_clusters(MipContext* ctx) {
   if (int32_t rc = sync_all(ctx)) return rc;  // a cull in flight reads the table this call replaces
   MipContext::ClusterTable& t = ctx->clusters;
   t.valid = false;
+  t.cones_valid = false;  // (cones of the table this call replaces)
   if (int32_t rc = grow(ctx, &t.d_boxes, &t.boxes_cap, (size_t)total, 2 * sizeof(float4))) return rc;
   if (int32_t rc = grow(ctx, &t.d_cluster_base, &t.base_cap, base.size(), 4)) return rc;
   MIP_HIP(ctx, hipMemcpyAsync(t.d_cluster_base, base.data(), base.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -91,6 +98,45 @@ int32_t build_clusters(MipContext* ctx) {
   t.total = (uint32_t)total;
   t.max_clusters = max_clusters;
   t.valid = true;
+  return MIP_OK;
+}
+
+// One cone per cluster of the valid table, from the resident geometry and the table's boxes; synchronous like the table's build.
+int32_t build_cluster_cones(MipContext* ctx) {
+  MipContext::ClusterTable& t = ctx->clusters;
+  if (!t.valid) return fail(ctx, MIP_ERR_NOT_READY, "mip_build_cluster_cones needs a valid cluster table (mip_build_clusters)");
+  if (int32_t rc = bind_device(ctx)) return rc;
+  if (int32_t rc = sync_all(ctx)) return rc;  // a cull in flight reads the cones this call replaces
+  t.cones_valid = false;
+  if (int32_t rc = grow(ctx, &t.d_cones, &t.cones_cap, (size_t)t.total, 2 * sizeof(float4))) return rc;
+  if (t.total) {
+    mip::ClusterConeBuildArgs a{};
+    a.b.vertices = ctx->d_vertices;
+    a.b.indices = ctx->d_indices;
+    a.b.chain = ctx->d_mesh_chain;
+    a.b.mesh_draw = ctx->d_mesh_draw;
+    a.b.bucket_lod = ctx->d_bucket_lod;
+    a.b.cluster_base = t.d_cluster_base;
+    a.b.boxes = t.d_boxes;
+    a.b.n_buckets = (uint32_t)ctx->lod_buckets;
+    a.b.total = t.total;
+    a.cones = t.d_cones;
+    const uint32_t blocks = (t.total + mip::kWaves - 1u) / mip::kWaves;
+    hipLaunchKernelGGL(mip::mip_cluster_cone_build_kernel, dim3(blocks), dim3(mip::kClusterThreads), 0, ctx->stream, a);
+    MIP_HIP(ctx, hipGetLastError());
+    MIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  t.cones_valid = true;
+  return MIP_OK;
+}
+
+// What the two cone calls refuse on top of the plain calls' list.
+int32_t check_cone(MipContext* ctx, const MipClusterCone* cone) {
+  if (!cone) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cone is NULL");
+  if (cone->struct_size != sizeof(MipClusterCone))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterCone.struct_size %u != %zu", cone->struct_size, sizeof(MipClusterCone));
+  if (cone->flags) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipClusterCone flags 0x%x", cone->flags);
+  if (!(cone->facing == 1.0f || cone->facing == -1.0f)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterCone.facing is neither +1 nor -1");
   return MIP_OK;
 }
 
@@ -139,9 +185,14 @@ int32_t launch(MipContext* ctx, Kernel kernel, uint32_t blocks, hipStream_t stre
 // rec == null: mip_cull_clusters; else a phase of mip_cull_clusters_phase (`phased`: the entry point, which refuses a null rec).
 // tri != null: mip_cull_cluster_triangles — `out` holds its leading fields; the triangle test, its scan, the write and the
 // commands into the culled stream take the place of the epilogue and the commands kernel (nine launches).
+// cone != null (`coned`: the entry point, which refuses a null cone): the cone calls — mip_cluster_cone_cull_kernel in the
+// cull kernel's place, nothing else differs.
 int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy, const MipOcclusion* occ,
-                      const MipClusterOutputs* out, const MipClusterRecord* rec, bool phased, const MipClusterTriangleOutputs* tri = nullptr) {
+                      const MipClusterOutputs* out, const MipClusterRecord* rec, bool phased, const MipClusterTriangleOutputs* tri = nullptr,
+                      const MipClusterCone* cone = nullptr, bool coned = false) {
   if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
+  if (coned)
+    if (int32_t rc = check_cone(ctx, cone)) return rc;
   if (out->struct_size != sizeof(MipClusterOutputs))
     return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipClusterOutputs));
   if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipClusterOutputs flags 0x%x", out->flags);
@@ -171,6 +222,8 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   const bool first = rec && rec->phase == MIP_CLUSTER_PHASE_FIRST, second = rec && rec->phase == MIP_CLUSTER_PHASE_SECOND;
   if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
   if (!ctx->clusters.valid) return fail(ctx, MIP_ERR_NOT_READY, "no cluster table, or the mesh table / geometry changed since mip_build_clusters");
+  if (cone && !ctx->clusters.cones_valid)
+    return fail(ctx, MIP_ERR_NOT_READY, "no cone table, or the cluster table changed since mip_build_cluster_cones");
   if (int32_t rc = bind_device(ctx)) return rc;
 
   const uint32_t slot = ctx->last_slot;
@@ -271,7 +324,15 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
                           : launch(ctx, mip::mip_cluster_scan_kernel<mip::kClusterPlain>, 1, stream, a))
     return rc;
   if (int32_t rc = launch(ctx, mip::mip_cluster_members_kernel, plan.instance_tiles, stream, a)) return rc;
-  if (int32_t rc = second  ? launch(ctx, mip::mip_cluster_retest_kernel, plan.retest_blocks, stream, a)
+  mip::ClusterConeArgs ca{};
+  if (cone) {
+    ca.c = a;
+    ca.cones = table.d_cones;
+    std::memcpy(ca.eye, cone->eye, sizeof ca.eye);
+    ca.facing = cone->facing;
+  }
+  if (int32_t rc = cone    ? launch(ctx, mip::mip_cluster_cone_cull_kernel, plan.cull_blocks, stream, ca)
+                   : second ? launch(ctx, mip::mip_cluster_retest_kernel, plan.retest_blocks, stream, a)
                    : first ? launch(ctx, mip::mip_cluster_cull_kernel<true>, plan.cull_blocks, stream, a)
                            : launch(ctx, mip::mip_cluster_cull_kernel<false>, plan.cull_blocks, stream, a))
     return rc;
@@ -337,6 +398,7 @@ int32_t cluster_wait_status(MipContext* ctx, int32_t rc) {
 void cluster_release(MipContext* ctx) {
   (void)hipFree(ctx->clusters.d_boxes);
   (void)hipFree(ctx->clusters.d_cluster_base);
+  (void)hipFree(ctx->clusters.d_cones);
   ctx->clusters = MipContext::ClusterTable{};
   for (auto& cs : ctx->cluster_scratch) {
     (void)hipFree(cs.d_instances);
@@ -394,6 +456,43 @@ int32_t mip_read_cluster_boxes(MipContext* ctx, float* host_out, uint32_t capaci
   return MIP_OK;
 }
 
+int32_t mip_build_cluster_cones(MipContext* ctx) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  return build_cluster_cones(ctx);
+}
+
+int32_t mip_read_cluster_cones(MipContext* ctx, float* host_out, uint32_t capacity_clusters) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (!ctx->clusters.valid || !ctx->clusters.cones_valid)
+    return fail(ctx, MIP_ERR_NOT_READY, "no cone table, or the cluster table changed since mip_build_cluster_cones");
+  const uint32_t total = ctx->clusters.total;
+  if (capacity_clusters < total) return fail(ctx, MIP_ERR_CAPACITY, "%u clusters, room for %u", total, capacity_clusters);
+  if (!total) return MIP_OK;
+  if (!host_out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "host_out is NULL");
+  if (int32_t rc = bind_device(ctx)) return rc;
+  MIP_HIP(ctx, hipMemcpy(host_out, ctx->clusters.d_cones, (size_t)total * 2 * sizeof(float4), hipMemcpyDeviceToHost));  // 8 floats per cluster, as stored
+  return MIP_OK;
+}
+
+int32_t mip_cone_from_pv(const float pv[16], MipClusterCone* out) {
+  if (!pv || !out) return MIP_ERR_INVALID_ARGUMENT;
+  float m[16], eye[3], facing;
+  std::memcpy(m, pv, sizeof m);
+  if (!mip::cone_from_pv(m, eye, facing)) return MIP_ERR_INVALID_ARGUMENT;
+  out->struct_size = sizeof(MipClusterCone);
+  out->flags = 0;
+  std::memcpy(out->eye, eye, sizeof eye);
+  out->facing = facing;
+  return MIP_OK;
+}
+
+int32_t mip_cull_clusters_cone(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                               const MipOcclusion* occ, const MipClusterCone* cone, const MipClusterOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  return cull_clusters(ctx, frame, visible_bitmap, policy, occ, out, nullptr, false, nullptr, cone, true);
+}
+
 int32_t mip_cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
                           const MipOcclusion* occ, const MipClusterOutputs* out) {
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
@@ -410,9 +509,9 @@ int32_t mip_cull_clusters_phase(MipContext* ctx, const MipFrame* frame, const ui
   return cull_clusters(ctx, frame, visible_bitmap, policy, occ, out, rec, true);
 }
 
-int32_t mip_cull_cluster_triangles(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
-                                   const MipOcclusion* occ, const MipClusterTriangleOutputs* out) {
-  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+// mip_cull_cluster_triangles and its cone form: the checks of the trailing fields, then the call the two structs share
+static int32_t cull_cluster_triangles(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                               const MipOcclusion* occ, const MipClusterTriangleOutputs* out, const MipClusterCone* cone, bool coned) {
   if (int32_t rc = check_policy(ctx, policy)) return rc;
   if (!out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
   if (out->struct_size != sizeof(MipClusterTriangleOutputs))
@@ -427,7 +526,19 @@ int32_t mip_cull_cluster_triangles(MipContext* ctx, const MipFrame* frame, const
   leading.work_capacity = out->work_capacity;
   leading.cmd_count = out->cmd_count;
   leading.stats = out->stats;
-  return cull_clusters(ctx, frame, visible_bitmap, policy, occ, &leading, nullptr, false, out);
+  return cull_clusters(ctx, frame, visible_bitmap, policy, occ, &leading, nullptr, false, out, cone, coned);
+}
+
+int32_t mip_cull_cluster_triangles(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                   const MipOcclusion* occ, const MipClusterTriangleOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  return cull_cluster_triangles(ctx, frame, visible_bitmap, policy, occ, out, nullptr, false);
+}
+
+int32_t mip_cull_cluster_triangles_cone(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                        const MipOcclusion* occ, const MipClusterCone* cone, const MipClusterTriangleOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  return cull_cluster_triangles(ctx, frame, visible_bitmap, policy, occ, out, cone, true);
 }
 
 }  // extern "C"

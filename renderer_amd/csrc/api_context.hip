@@ -345,6 +345,7 @@ int32_t mip_set_mesh_table(MipContext* ctx, const MipMesh* meshes, uint32_t m) {
   ctx->h_meshes.assign(meshes, meshes + m);
   ctx->geometry_checked = 0;
   ctx->clusters.valid = false;  // (mip_build_clusters cut the old table's levels)
+  ctx->clusters.cones_valid = false;
   ctx->max_lod_tris = 0;
   for (uint32_t k = 0; k < m; ++k)
     for (uint32_t l = 0; l < meshes[k].n_lods && l < 2u; ++l)
@@ -407,6 +408,7 @@ int32_t mip_set_geometry(MipContext* ctx, const float* vertex_xyz, uint32_t n_ve
   ctx->h_indices.assign(indices, indices + n_indices);
   ctx->geometry_checked = 0;
   ctx->clusters.valid = false;  // (mip_build_clusters read the old geometry)
+  ctx->clusters.cones_valid = false;
   return MIP_OK;
 }
 

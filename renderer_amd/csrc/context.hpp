@@ -128,6 +128,10 @@ struct MipContext {
     size_t boxes_cap = 0, base_cap = 0; // clusters / words the two hold
     uint32_t total = 0, max_clusters = 0;  // clusters in the table; the largest C of a bucket
     bool valid = false;
+    // the normal cones mip_build_cluster_cones makes of a valid table (cluster_cone_plan.hpp): stale with the table
+    float4* d_cones = nullptr;          // two per cluster, bucket-major: {axis xyz, k}, {centre xyz, r}
+    size_t cones_cap = 0;
+    bool cones_valid = false;
   };
   ClusterTable clusters;
   struct ClusterScratch {

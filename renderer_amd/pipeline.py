@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipClusterOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
                    MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
@@ -189,6 +189,27 @@ def make_cluster_record(phase, record, record_bytes):
     r.record = record or None
     r.record_bytes = int(record_bytes)
     return r
+
+
+def make_cluster_cone(pv=None, eye=None, facing=None):
+    """A MipClusterCone for cull_clusters_cone / cull_cluster_triangles_cone: from a projection `pv` (float32[16], column-major)
+    through mip_cone_from_pv — the point the view projects from and the sign of its determinant, in double, rounded once; a
+    singular (orthographic) or non-finite pv raises MIP_ERR_INVALID_ARGUMENT — or from an explicit `eye` (3 floats; a shadow
+    view's is the light) and `facing` (+1 or -1), which also override what pv gives."""
+    c = MipClusterCone()
+    c.struct_size = C.sizeof(MipClusterCone)
+    if pv is not None:
+        m = np.ascontiguousarray(np.asarray(pv, np.float32).reshape(16))
+        rc = _lib.load_library().mip_cone_from_pv(m.ctypes.data, C.addressof(c))
+        if rc != 0:
+            raise MipError(rc, "mip_cone_from_pv: rows x, y, w of pv are singular or not finite (an orthographic view has no eye)")
+    elif eye is None or facing is None:
+        raise ValueError("make_cluster_cone needs pv, or eye and facing")
+    if eye is not None:
+        c.eye[:] = [float(v) for v in np.asarray(eye, np.float32).reshape(3)]
+    if facing is not None:
+        c.facing = float(facing)
+    return c
 
 
 def make_frame(planes, cam_pos, first_instance_base=0, first_index_base=0, pv=None):
@@ -683,6 +704,33 @@ class InstancePipeline:
         exceed work_capacity."""
         self._check(self._lib.mip_cull_cluster_triangles(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                          C.addressof(occlusion) if occlusion is not None else None, C.addressof(outputs)))
+
+    # -- cluster culling with normal cones (extension) --
+    def build_cluster_cones(self):
+        """mip_build_cluster_cones: one normal cone per cluster of the valid cluster table (build_clusters first; whatever makes
+        that table stale makes the cones stale)."""
+        self._check(self._lib.mip_build_cluster_cones(self._ctx))
+
+    def read_cluster_cones(self):
+        """The cone table as a (clusters, 8) float32 array {axis xyz, k, centre xyz, r}, bucket-major; k = +inf: no cone."""
+        cones = np.zeros((self.cluster_count(), 8), np.float32)
+        self._check(self._lib.mip_read_cluster_cones(self._ctx, cones.ctypes.data, len(cones)))
+        return cones
+
+    def cull_clusters_cone(self, frame, visible_bitmap_ptr, policy, cone, outputs, occlusion=None):
+        """mip_cull_clusters_cone: cull_clusters with the normal-cone back-face test of `cone` (make_cluster_cone) in front: a
+        cluster all of whose triangles face away from the cone's eye is removed before its box is tested."""
+        self._check(self._lib.mip_cull_clusters_cone(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                     C.addressof(occlusion) if occlusion is not None else None,
+                                                     C.addressof(cone) if cone is not None else None, C.addressof(outputs)))
+
+    def cull_cluster_triangles_cone(self, frame, visible_bitmap_ptr, policy, cone, outputs, occlusion=None):
+        """mip_cull_cluster_triangles_cone: cull_cluster_triangles over the clusters cull_clusters_cone leaves. With cone =
+        make_cluster_cone(frame's pv) the cone removes only triangles the per-triangle test would cull, up to that test's own
+        float rounding on slivers."""
+        self._check(self._lib.mip_cull_cluster_triangles_cone(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                              C.addressof(occlusion) if occlusion is not None else None,
+                                                              C.addressof(cone) if cone is not None else None, C.addressof(outputs)))
 
     # -- diagnostics --
     def timings(self):

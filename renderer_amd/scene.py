@@ -322,6 +322,27 @@ def _first_use_order(pos, tris):
     return pos[order], new_id[tris].astype(np.uint32)
 
 
+def _patch_order(n_vertices, n_triangles):
+    """The permutation that lists _torus_mesh's triangles patch by patch: the grid's quads in tiles of 8 (around the large
+    circle) x 4 (around the small one), row by row inside a tile, both triangles of a quad together — 64 triangles per full
+    tile, so a 64-triangle cluster is one compact patch of the surface. A list that keeps only every k-th triangle of the
+    grid gets tiles of 8 x 4 k quads, which again hold about 64 of its triangles."""
+    w = max(3, int(np.sqrt(n_vertices)))
+    h = max(3, n_vertices // w)
+    while w * h > n_vertices and h > 3:
+        h -= 1
+    if w * h > n_vertices:
+        w = h = 3
+    full = 2 * w * h
+    # the triangles _torus_mesh returns, as positions in its whole list: the lower triangle of quad q at q, the upper at w h + q
+    order = (np.arange(n_triangles, dtype=np.int64) * full) // max(n_triangles, 1) if n_triangles <= full \
+        else np.arange(n_triangles, dtype=np.int64) % full
+    quad, upper = order % (w * h), order // (w * h)
+    i, j = quad // h, quad % h
+    tj = 4 * max(1, int(round(full / max(n_triangles, 1))))
+    return np.lexsort((upper, j % tj, i % 8, j // tj, i // 8))   # (the last key is the primary one)
+
+
 def make_geometry(meshes, ordering="rows"):
     """Consolidated position and index buffers matching a mesh table's vertex_offset /
     index_offset / index_len (what consolidate_mesh_buffers builds). Returns (vertices (V,3) f32,
@@ -331,8 +352,10 @@ def make_geometry(meshes, ordering="rows"):
     vertices row-major: a triangle's corners are a grid row (~sqrt(V) vertices) apart. "strips" — the same
     surface listed quad by quad along the strips with the vertices renumbered in first-use order: the layout
     of a vertex-cache/vertex-fetch optimised mesh. "shuffled" — the triangles of "rows" in random order: no
-    locality at all (every 64-triangle step spans the whole mesh)."""
-    if ordering not in ("rows", "strips", "shuffled"):
+    locality at all (every 64-triangle step spans the whole mesh). "patches" — the quads in tiles of 8 x 4 (64
+    triangles: one cluster of mip_build_clusters is one compact patch, the layout a meshlet builder produces; wider
+    tiles where the list keeps only a part of the grid's triangles), the vertices in first-use order."""
+    if ordering not in ("rows", "strips", "shuffled", "patches"):
         raise ValueError(ordering)
     m = len(meshes)
     voff = meshes["vertex_offset"].astype(np.int64)
@@ -361,6 +384,9 @@ def make_geometry(meshes, ordering="rows"):
             pos, tris = _first_use_order(pos, tris)
         elif ordering == "shuffled":
             tris = tris[np.random.default_rng(1234 + k).permutation(len(tris))]
+        elif ordering == "patches":
+            tris = tris[_patch_order(int(vcount[k]), len(tris))]
+            pos, tris = _first_use_order(pos, tris)
         vertices[voff[k] : voff[k] + vcount[k]] = pos
         for l in range(int(meshes["n_lods"][k])):
             tl = int(meshes["index_len"][k, l]) // 3
