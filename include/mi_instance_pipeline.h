@@ -805,8 +805,9 @@ int32_t mip_merge_batches(MipContext* ctx, const void* chunks, uint32_t n_chunks
  * built (mip_build_depth_pyramid) for the next run need no wait. Scratch is the call's own, per frame slot, allocated at
  * first use and grown by a larger call; with work_capacity = 0 it is sized for N x the largest C (16 bytes per 64 work
  * items), so a scene of large meshes should state its bound.
- * OUT OF SCOPE: views, shards, skinned instances, mip_run_many and recorded graphs; batch_model. (The per-triangle test on
- * surviving clusters is mip_cull_cluster_triangles; the normal-cone back-face test is mip_cull_clusters_cone.) */
+ * OUT OF SCOPE: shards, skinned instances, mip_run_many and recorded graphs; batch_model. (The per-triangle test on
+ * surviving clusters is mip_cull_cluster_triangles; the normal-cone back-face test is mip_cull_clusters_cone; several views
+ * in one call are mip_cull_clusters_views.) */
 #define MIP_CLUSTER_TRIANGLES 64u
 typedef struct MipClusterOutputs {
   uint32_t struct_size;      /* = sizeof(MipClusterOutputs) */
@@ -998,11 +999,69 @@ int32_t mip_cull_clusters_cone(MipContext* ctx, const MipFrame* frame, const uin
 int32_t mip_cull_cluster_triangles_cone(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
                                         const MipOcclusion* occ, const MipClusterCone* cone, const MipClusterTriangleOutputs* out);
 
+/* ---- Extension: cluster culling for several views in one call -------------------------------------------------------------
+ * mip_cull_clusters (the frustum test, no pyramid) for n_views views of the resident instances — cascades, cube faces, the
+ * lights of a shadow pass, stereo eyes — in ONE call: the level, the work items and the world box of every (instance, cluster)
+ * are formed once, and only the six planes and the bitmap bit differ per view. NOT a reference behaviour; checked against this
+ * repository's restatement (tests/cluster_views_restatement.py), byte for byte. MEMBERS' LOD, WORK ITEMS, the world box, HEAD
+ * and the command fields are the words of mip_cull_clusters above; mip_cull_clusters itself is unchanged.
+ *
+ * VIEWS: 1 <= n_views <= MIP_MAX_VIEWS. frames and visible_bitmaps are as in mip_batch_draws_views: view v is frames[v] with
+ * visible_bitmaps[v]; `visible_bitmaps` is a HOST array of n_views DEVICE pointers; a NULL entry means every resident
+ * instance; two views may share a pointer. Read per view: planes and first_instance_base.
+ * ONE LOD FOR ALL VIEWS: the level of instance i is picked by `policy` from frames[0].cam_pos, exactly as mip_batch_draws_lods
+ * picks it; frames[v].cam_pos for v > 0 is NOT read. This differs deliberately from mip_batch_draws_views, which picks a level
+ * per view: a shadow caster keeps one level across cascades and faces, and a shared level is what makes a work item, and its
+ * world box, common to all views.
+ * MEMBERS: instance i is a member iff its bit is set in AT LEAST ONE view's bitmap (a NULL entry counts as set) and
+ * T(bucket_i) > 0.
+ * WORK ITEMS, W: as in mip_cull_clusters, over these members: (i, c) for every member i in draw-index order and every
+ * c < C(bucket_i) in order.
+ * SURVIVES_v(i, c): bit i of view v is set, AND the world box — the one mip_cull_clusters defines: same chain, same numbers —
+ * is not culled by the plane test against frames[v].planes.
+ * HEAD and COMMANDS, per view: mip_cull_clusters' rules with SURVIVES_v in place of SURVIVES; firstInstance =
+ * frames[v].first_instance_base + i. View v's commands are entries [v * cmd_stride, v * cmd_stride + cmd_counts[v]) of
+ * cluster_cmds; cmd_counts[v] = min(heads_v, cmd_stride); entries at or behind a view's count are never touched.
+ * stats (optional, 2 + 2 x n_views words): {W, members, heads_0, survivors_0, heads_1, survivors_1, ...}.
+ * THE EQUIVALENCE: let f_v = frames[v] with cam_pos replaced by frames[0].cam_pos. View v's command range, cmd_counts[v],
+ * heads_v and survivors_v are byte for byte what mip_cull_clusters(ctx, &f_v, visible_bitmaps[v] (a full bitmap where the entry
+ * is NULL), policy, NULL, {cmd_capacity = cmd_stride}) writes, whenever both calls run: an instance outside view v's bitmap
+ * has no survivor in view v and therefore no command.
+ * OVERFLOW. Some heads_v > cmd_stride: that view gets its first cmd_stride commands exactly as with room, the other views are
+ * complete, stats are true, the status is MIP_ERR_CAPACITY. W > work_capacity (0 = the library's own bound, N x the largest C
+ * of the table), or W >= 2^32: every count is 0, stats = {W mod 2^32, members, 0, ...}, no command is written,
+ * MIP_ERR_CAPACITY. WHO REPORTS is mip_cull_clusters' rule: a synchronous call reports its own overflow, once; an asynchronous
+ * call through the next mip_wait that has no other error to return. The call is not tied to a frame slot and has status words
+ * of its own: a mip_cull_clusters behind a frame slot is never charged with this call's overflow, nor this call with its.
+ * N = 0 writes n_views zero counts (and zero stats).
+ * REFUSED, nothing written, MIP_ERR_INVALID_ARGUMENT: NULL ctx / frames / visible_bitmaps / policy / out / cluster_cmds /
+ * cmd_counts; a wrong struct_size of either struct; unknown flags; a missing MIP_OUT_DEVICE; a misaligned output (4 bytes);
+ * n_views out of range; a policy mip_batch_draws_lods refuses. MIP_ERR_NOT_READY: no instances, no mesh table, or no valid
+ * cluster table.
+ * ORDERING: enqueued on the context's first stream, where mip_run_views runs, so the bitmaps a preceding mip_run_views writes
+ * need no wait. Scratch is the call's own, allocated at first use and grown by a larger call: (1 + n_views) x 8 bytes per 64
+ * work items of the bound plus 2 bytes per instance, beside the per-instance lists. No frame slot's cluster scratch is
+ * touched: a cluster call behind a frame slot and this call do not disturb each other.
+ * OUT OF SCOPE: a pyramid per view; the two phases; the per-triangle stream; cones; shards; skinned instances; mip_run_many
+ * and recorded graphs. */
+typedef struct MipClusterViewOutputs {
+  uint32_t struct_size;      /* = sizeof(MipClusterViewOutputs) */
+  uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
+  void* cluster_cmds;        /* DEVICE: n_views x cmd_stride MipDrawIndexedIndirectCommand */
+  uint32_t cmd_stride;       /* commands reserved per view */
+  uint32_t work_capacity;    /* the caller's bound on W (of the union of the views' members); 0 = N x the largest C of the table */
+  uint32_t* cmd_counts;      /* DEVICE: n_views words: commands written for view v = min(heads_v, cmd_stride) */
+  uint32_t* stats;           /* DEVICE, optional: 2 + 2 x n_views words: W, members, then heads and surviving clusters per view */
+} MipClusterViewOutputs;     /* 40 B */
+
+int32_t mip_cull_clusters_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps,
+                                uint32_t n_views, const MipLodPolicy* policy, const MipClusterViewOutputs* out);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every
  * frames_in_flight frames): it is where their errors surface. The MIP_ERR_CAPACITY of an asynchronous
- * mip_cull_clusters (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase) is returned
+ * mip_cull_clusters or mip_cull_clusters_views (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase) is returned
  * when there is no other error to return; otherwise by the mip_wait after. */
 int32_t mip_wait(MipContext* ctx);
 

@@ -105,6 +105,25 @@ int main(void) {
   batch.batch_count = &count;
   batch.instance_ids = bitmap;
   ok = ok && mip_batch_draws(ctx, &frame, bitmap, &batch) == MIP_ERR_INVALID_ARGUMENT && mip_instance_count(ctx) == N;
+  /* Cluster culling for several views (extension): after mip_set_geometry and mip_build_clusters, and behind a mip_run_views
+   * that wrote the views' bitmaps, with no wait,
+   *     MipClusterViewOutputs cv = { sizeof cv, MIP_OUT_DEVICE | MIP_OUT_ASYNC, cluster_cmds, cmd_stride, 0, cmd_counts, NULL };
+   *     mip_cull_clusters_views(ctx, frames, bitmaps_dev, n_views, &policy, &cv);
+   * and per view vkCmdDrawIndexedIndirectCount(cb, cluster_cmds, v * cmd_stride * 20, cmd_counts, v * 4, cmd_stride, 20).
+   * Here: the struct and the entry point link from C, and host pointers are refused without harming the context. */
+  MipClusterViewOutputs cluster_views;
+  const uint32_t* view_bitmaps[1] = {NULL};
+  MipLodPolicy policy;
+  memset(&policy, 0, sizeof policy);
+  policy.struct_size = sizeof policy;
+  memset(&cluster_views, 0, sizeof cluster_views);
+  cluster_views.struct_size = sizeof cluster_views;
+  cluster_views.flags = MIP_OUT_HOST;
+  cluster_views.cluster_cmds = cmds;
+  cluster_views.cmd_stride = 1;
+  cluster_views.cmd_counts = &count;
+  ok = ok && mip_cull_clusters_views(ctx, &frame, view_bitmaps, 1, &policy, &cluster_views) == MIP_ERR_INVALID_ARGUMENT &&
+       mip_instance_count(ctx) == N;
   printf("C_SMOKE %s instances=%d visible=%u commands=%u index_total=%u checksum=%08x\n", ok ? "OK" : "BAD", N, visible, count,
          index_total, sum);
   mip_destroy(ctx);

@@ -182,6 +182,18 @@ pub struct MipClusterOutputs {
     pub stats: *mut u32,
 }
 
+/// Outputs of mip_cull_clusters_views: view v's commands start at entry v x cmd_stride, device pointers (see the header).
+#[repr(C)]
+pub struct MipClusterViewOutputs {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub cluster_cmds: *mut c_void,
+    pub cmd_stride: u32,
+    pub work_capacity: u32,
+    pub cmd_counts: *mut u32,
+    pub stats: *mut u32,
+}
+
 /// Outputs of mip_cull_cluster_triangles: MipClusterOutputs' fields, then the culled index stream (see the header).
 #[repr(C)]
 pub struct MipClusterTriangleOutputs {
@@ -327,6 +339,10 @@ extern "C" {
                                   occ: *const MipOcclusion, cone: *const MipClusterCone, out: *const MipClusterOutputs) -> i32;
     pub fn mip_cull_cluster_triangles_cone(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
                                            occ: *const MipOcclusion, cone: *const MipClusterCone, out: *const MipClusterTriangleOutputs) -> i32;
+    /// mip_cull_clusters' frustum test for up to MIP_MAX_VIEWS views in one call: one LOD (frames[0].cam_pos) and one world box
+    /// per work item for all views, planes and first_instance_base per view; on the first stream, behind mip_run_views.
+    pub fn mip_cull_clusters_views(ctx: *mut MipContext, frames: *const MipFrame, visible_bitmaps: *const *const u32,
+                                   n_views: u32, policy: *const MipLodPolicy, out: *const MipClusterViewOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -344,6 +360,7 @@ const _: [u8; 28] = [0; std::mem::size_of::<MipSortPolicy>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipViewBatchOutputs>()];
 const _: [u8; 16] = [0; std::mem::size_of::<MipBatchChunkHeader>()];
 const _: [u8; 40] = [0; std::mem::size_of::<MipClusterOutputs>()];
+const _: [u8; 40] = [0; std::mem::size_of::<MipClusterViewOutputs>()];
 const _: [u8; 24] = [0; std::mem::size_of::<MipClusterRecord>()];
 const _: [u8; 56] = [0; std::mem::size_of::<MipClusterTriangleOutputs>()];
 const _: [u8; 24] = [0; std::mem::size_of::<MipClusterCone>()];

@@ -8,13 +8,17 @@
 // mip_build_cluster_cones gives every cluster of a valid table a normal cone, and mip_cull_clusters_cone /
 // mip_cull_cluster_triangles_cone are the two culls with the cone's back-face test in front of SURVIVES (one new kernel in
 // the cull kernel's place; every other launch is the plain call's).
+// mip_cull_clusters_views is the frustum test of mip_cull_clusters for several views in one call, on the context's first stream
+// with a scratch and a pair of status words of its own (cluster_views_kernel.hpp, cluster_views_plan.hpp).
 // cluster_plan.hpp, cluster_triangle_plan.hpp and cluster_cone_plan.hpp hold the arithmetic and the launch plans; the kernels
 // (cluster_kernel.hpp, cluster_triangle_kernel.hpp, cluster_cone_kernel.hpp) are instantiated here and only here.
 #include "context.hpp"
 #include "cluster_kernel.hpp"
 #include "cluster_triangle_kernel.hpp"
 #include "cluster_cone_kernel.hpp"
+#include "cluster_views_kernel.hpp"
 
+static_assert(sizeof(MipClusterViewOutputs) == 40, "MipClusterViewOutputs is part of the ABI");
 static_assert(sizeof(MipClusterOutputs) == 40, "MipClusterOutputs is part of the ABI");
 static_assert(sizeof(MipClusterRecord) == 24, "MipClusterRecord is part of the ABI");
 static_assert(sizeof(MipClusterTriangleOutputs) == 56, "MipClusterTriangleOutputs is part of the ABI");
@@ -379,20 +383,158 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   return MIP_OK;
 }
 
+// ---- mip_cull_clusters_views ----
+
+int32_t ensure_views_scratch(MipContext* ctx, MipContext::ClusterViewScratch& vs, const mip::ClusterViewsPlan& plan) {
+  const size_t cap = instance_cap(ctx);
+  if (!vs.d_instances) {
+    MIP_HIP(ctx, hipMalloc(&vs.d_instances, (4 * cap + 1) * 4));
+    MIP_HIP(ctx, hipMalloc(&vs.d_view_mask, cap * 2));
+    const size_t tiles = (cap + mip::kClusterInstanceTile - 1) / mip::kClusterInstanceTile;
+    MIP_HIP(ctx, hipMalloc(&vs.d_tile_items, tiles * 8));
+    MIP_HIP(ctx, hipMalloc(&vs.d_tile_members, tiles * 4));
+    MIP_HIP(ctx, hipMalloc(&vs.d_scalars, mip::kClusterScWords * 4));
+  }
+  if (int32_t rc = grow(ctx, &vs.d_view_words, &vs.words_cap, (size_t)plan.words, 8)) return rc;
+  if (int32_t rc = grow(ctx, &vs.d_tile_heads, &vs.head_rows_cap, (size_t)plan.tile_rows, 4)) return rc;
+  if (int32_t rc = grow(ctx, &vs.d_tile_survivors, &vs.survivor_rows_cap, (size_t)plan.tile_rows, 4)) return rc;
+  return MIP_OK;
+}
+
+template <class Kernel>
+int32_t launch_views(MipContext* ctx, Kernel kernel, const mip::ClusterViewsLaunch& l, hipStream_t stream, const mip::ClusterViewArgs& a) {
+  hipLaunchKernelGGL(kernel, dim3(l.blocks_x, l.blocks_y), dim3(mip::kClusterThreads), 0, stream, a);
+  MIP_HIP(ctx, hipGetLastError());
+  return MIP_OK;
+}
+
+// Every check first (a refused call writes nothing), then the seven launches of the plan on the context's first stream.
+int32_t cull_clusters_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps, uint32_t n_views,
+                            const MipLodPolicy* policy, const MipClusterViewOutputs* out) {
+  if (!frames || !visible_bitmaps || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frames/visible_bitmaps/out is NULL");
+  if (out->struct_size != sizeof(MipClusterViewOutputs))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterViewOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipClusterViewOutputs));
+  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipClusterViewOutputs flags 0x%x", out->flags);
+  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_cull_clusters_views needs MIP_OUT_DEVICE outputs");
+  if (!out->cluster_cmds || !out->cmd_counts) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cluster_cmds/cmd_counts is NULL");
+  if ((uintptr_t)out->cluster_cmds % 4u != 0u || (uintptr_t)out->cmd_counts % 4u != 0u || (uintptr_t)out->stats % 4u != 0u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "an output is not 4-byte aligned");
+  if (n_views == 0 || n_views > MIP_MAX_VIEWS) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "n_views %u outside 1..%u", n_views, (unsigned)MIP_MAX_VIEWS);
+  if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
+  if (!ctx->clusters.valid) return fail(ctx, MIP_ERR_NOT_READY, "no cluster table, or the mesh table / geometry changed since mip_build_clusters");
+  if (int32_t rc = bind_device(ctx)) return rc;
+
+  hipStream_t stream = ctx->stream;
+  const bool async = (out->flags & MIP_OUT_ASYNC) != 0;
+  const uint32_t n = ctx->n;
+  const size_t stats_bytes = (2 + 2 * (size_t)n_views) * 4;
+  if (n == 0) {  // nothing to test: zeros
+    MIP_HIP(ctx, hipMemsetAsync(out->cmd_counts, 0, (size_t)n_views * 4, stream));
+    if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, stats_bytes, stream));
+    return finish(ctx, stream, async);
+  }
+  if (!ctx->h_cluster_views_status) {
+    MIP_HIP(ctx, hipHostMalloc(&ctx->h_cluster_views_status, 2 * 4, hipHostMallocMapped));
+    std::memset(ctx->h_cluster_views_status, 0, 2 * 4);
+  }
+  const MipContext::ClusterTable& table = ctx->clusters;
+  const unsigned long long bound = mip::cluster_work_bound(n, table.max_clusters, out->work_capacity);
+  const mip::ClusterViewsPlan plan = mip::plan_cluster_views(n, bound, n_views);
+  MipContext::ClusterViewScratch& vs = ctx->cluster_views;
+  if (int32_t rc = ensure_views_scratch(ctx, vs, plan)) return rc;
+
+  mip::ClusterViewArgs va{};
+  mip::ClusterArgs& a = va.c;
+  a.lods.chain = ctx->d_mesh_chain;
+  a.lods.bucket_lod = ctx->d_bucket_lod;
+  std::memcpy(a.lods.switch_sq, policy->switch_sq, sizeof a.lods.switch_sq);
+  a.lods.pos = ctx->d_pos; a.lods.rot = ctx->d_rot; a.lods.scale = ctx->d_scale; a.lods.mesh_id = ctx->d_mesh_id;
+  a.lods.meshes = ctx->d_meshes; a.lods.mesh_draw = ctx->d_mesh_draw;
+  a.lods.n = n;
+  a.lods.n_tiles = plan.one.instance_tiles;
+  a.lods.n_buckets = (uint32_t)ctx->lod_buckets;
+  std::memcpy(a.lods.cam, frames[0].cam_pos, sizeof a.lods.cam);  // one level for all views
+  a.cluster_base = table.d_cluster_base;
+  a.boxes = table.d_boxes;
+  a.bound = bound;
+  const size_t cap = instance_cap(ctx);
+  a.items = vs.d_instances;
+  a.bucket = vs.d_instances + cap;
+  a.member_inst = vs.d_instances + 2 * cap;
+  a.member_first = vs.d_instances + 3 * cap;  // cap + 1 words
+  a.tile_items = vs.d_tile_items;
+  a.tile_members = vs.d_tile_members;
+  a.scalars = vs.d_scalars;
+  a.tile_heads = vs.d_tile_heads;
+  a.tile_survivors = vs.d_tile_survivors;
+  a.cmds = static_cast<uint32_t*>(out->cluster_cmds);
+  a.cmd_capacity = out->cmd_stride;
+  a.cmd_count = out->cmd_counts;
+  a.stats = out->stats;
+  va.n_views = n_views;
+  va.head_tiles = plan.one.head_tiles;
+  va.words_stride = plan.one.survive_words;
+  va.view_words = vs.d_view_words;
+  va.view_mask = vs.d_view_mask;
+  for (uint32_t v = 0; v < n_views; ++v) {
+    va.view_bitmap[v] = visible_bitmaps[v];
+    va.view_base[v] = frames[v].first_instance_base;
+    std::memcpy(va.view_planes[v], frames[v].planes, sizeof va.view_planes[v]);
+  }
+  volatile uint32_t* status = ctx->h_cluster_views_status + (async ? 0u : 1u);
+  MIP_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&a.status), const_cast<uint32_t*>(status), 0));
+  if (!async) *status = 0;  // (no synchronous call is in flight: each one drains the stream)
+#ifdef MIP_DEBUG_STAMPS
+  const DebugSwitches sw;
+  sw.tile_order(a.lods.n_tiles, a.lods.debug_tile_mult, a.lods.debug_tile_add);
+  a.debug_order = sw.reverse() ? mip::kClusterOrderReverse
+                  : (sw.order && std::strcmp(sw.order, "scramble") == 0) ? mip::kClusterOrderScramble : mip::kClusterOrderNone;
+#endif
+  const bool relative = policy->mode == MIP_LOD_RELATIVE;
+  for (const mip::ClusterViewsLaunch& l : plan.launches) {
+    int32_t rc = MIP_OK;
+    switch (l.kernel) {
+      case mip::ClusterViewsKernel::count:
+        rc = relative ? launch_views(ctx, mip::mip_cluster_views_count_kernel<MIP_LOD_RELATIVE>, l, stream, va)
+                      : launch_views(ctx, mip::mip_cluster_views_count_kernel<MIP_LOD_DISTANCE>, l, stream, va);
+        break;
+      // scan and members are the plain call's instantiations: they read the leading block only
+      case mip::ClusterViewsKernel::scan: rc = launch(ctx, mip::mip_cluster_scan_kernel<mip::kClusterPlain>, l.blocks_x, stream, a); break;
+      case mip::ClusterViewsKernel::members: rc = launch(ctx, mip::mip_cluster_members_kernel, l.blocks_x, stream, a); break;
+      case mip::ClusterViewsKernel::cull: rc = launch_views(ctx, mip::mip_cluster_views_cull_kernel, l, stream, va); break;
+      case mip::ClusterViewsKernel::heads: rc = launch_views(ctx, mip::mip_cluster_views_heads_kernel, l, stream, va); break;
+      case mip::ClusterViewsKernel::epilogue: rc = launch_views(ctx, mip::mip_cluster_views_epilogue_kernel, l, stream, va); break;
+      case mip::ClusterViewsKernel::commands: rc = launch_views(ctx, mip::mip_cluster_views_commands_kernel, l, stream, va); break;
+    }
+    if (rc) return rc;
+  }
+  if (int32_t rc = finish(ctx, stream, async)) return rc;
+  if (!async && *status) {  // this call's own word, and its stream has drained
+    *status = 0;
+    return fail(ctx, MIP_ERR_CAPACITY, "mip_cull_clusters_views: a view has more runs than cmd_stride (its first cmd_stride commands are written, the other views are complete), or more work items than work_capacity / 2^32 - 1 (nothing is written); stats holds the counts");
+  }
+  return MIP_OK;
+}
+
 }  // namespace
 
 // mip_wait, after every stream has drained. An overflow of an asynchronous call is reported when nothing else is: while `rc`
 // is another error the words stay as they are, and the mip_wait after it reports the overflow — it is never lost.
 int32_t cluster_wait_status(MipContext* ctx, int32_t rc) {
-  if (!ctx->h_cluster_status || rc != MIP_OK) return rc;
+  if (rc != MIP_OK) return rc;
   uint32_t raised = 0;
-  for (uint32_t k = 0; k < kStatusWords; k += 2) {
-    raised |= ((volatile uint32_t*)ctx->h_cluster_status)[k];
-    ((volatile uint32_t*)ctx->h_cluster_status)[k] = 0;
+  if (ctx->h_cluster_status)
+    for (uint32_t k = 0; k < kStatusWords; k += 2) {
+      raised |= ((volatile uint32_t*)ctx->h_cluster_status)[k];
+      ((volatile uint32_t*)ctx->h_cluster_status)[k] = 0;
+    }
+  if (ctx->h_cluster_views_status) {  // mip_cull_clusters_views' asynchronous word
+    raised |= ((volatile uint32_t*)ctx->h_cluster_views_status)[0];
+    ((volatile uint32_t*)ctx->h_cluster_views_status)[0] = 0;
   }
   if (!raised) return MIP_OK;
   if (raised & mip::kClusterStatusDevice) return fail(ctx, MIP_ERR_DEVICE, "asynchronous %s", kNotItsRecord);
-  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters had more runs than cmd_capacity, or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
+  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters or mip_cull_clusters_views had more runs than cmd_capacity, or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
 }
 
 void cluster_release(MipContext* ctx) {
@@ -416,6 +558,20 @@ void cluster_release(MipContext* ctx) {
     (void)hipFree(cs.d_tile_triangles);
   }
   ctx->cluster_scratch.clear();
+  {
+    MipContext::ClusterViewScratch& vs = ctx->cluster_views;
+    (void)hipFree(vs.d_instances);
+    (void)hipFree(vs.d_view_mask);
+    (void)hipFree(vs.d_tile_items);
+    (void)hipFree(vs.d_tile_members);
+    (void)hipFree(vs.d_scalars);
+    (void)hipFree(vs.d_view_words);
+    (void)hipFree(vs.d_tile_heads);
+    (void)hipFree(vs.d_tile_survivors);
+    vs = MipContext::ClusterViewScratch{};
+  }
+  if (ctx->h_cluster_views_status) (void)hipHostFree(ctx->h_cluster_views_status);
+  ctx->h_cluster_views_status = nullptr;
   if (ctx->h_cluster_status) (void)hipHostFree(ctx->h_cluster_status);
   ctx->h_cluster_status = nullptr;
   if (ctx->cluster_pyramid_ready) (void)hipEventDestroy(ctx->cluster_pyramid_ready);
@@ -498,6 +654,13 @@ int32_t mip_cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
   if (int32_t rc = check_policy(ctx, policy)) return rc;
   return cull_clusters(ctx, frame, visible_bitmap, policy, occ, out, nullptr, false);
+}
+
+int32_t mip_cull_clusters_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps, uint32_t n_views,
+                                const MipLodPolicy* policy, const MipClusterViewOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  return cull_clusters_views(ctx, frames, visible_bitmaps, n_views, policy, out);
 }
 
 uint64_t mip_cluster_record_bytes(uint64_t work_items) { return mip::cluster_record_bytes(work_items); }

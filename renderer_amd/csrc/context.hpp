@@ -9,7 +9,8 @@
 //                     (batch_kernel.hpp) under the key policies of batch_lods_kernel.hpp, batch_views_kernel.hpp and
 //                     batch_sorted_kernel.hpp, planned by batch_plan.hpp and run by one pass driver; mip_merge_batches
 //                     (batch_merge_kernel.hpp, batch_merge_plan.hpp)
-//   api_cluster.hip   the cluster-culling extension: mip_build_clusters, mip_cull_clusters, mip_cull_clusters_phase (cluster_kernel.hpp, cluster_plan.hpp)
+//   api_cluster.hip   the cluster-culling extension: mip_build_clusters, mip_cull_clusters, mip_cull_clusters_phase (cluster_kernel.hpp, cluster_plan.hpp),
+//                     mip_cull_clusters_views (cluster_views_kernel.hpp, cluster_views_plan.hpp)
 // (round 3 had all of it in one 2 224-line mip_api.hip)
 #pragma once
 
@@ -153,6 +154,21 @@ struct MipContext {
     size_t triangle_words_cap = 0, item_prefix_cap = 0, word_total_cap = 0, tile_triangles_cap = 0;
   };
   std::vector<ClusterScratch> cluster_scratch;
+  // mip_cull_clusters_views (cluster_views_plan.hpp): its own scratch on the first stream, as view_batch is — no frame slot's
+  // cluster scratch is touched. Allocated at first use, grown by a larger call.
+  struct ClusterViewScratch {
+    uint32_t* d_instances = nullptr;    // items, bucket, member_inst, member_first (+1): 4 x instance_cap + 1 words
+    uint16_t* d_view_mask = nullptr;    // instance_cap: the views whose bitmap holds the instance
+    unsigned long long* d_tile_items = nullptr;  // per instance tile
+    uint32_t* d_tile_members = nullptr;
+    uint32_t* d_scalars = nullptr;
+    unsigned long long* d_view_words = nullptr;  // (1 + n_views) planes of one word per 64 work items: start, then every view's survive words
+    uint32_t* d_tile_heads = nullptr;   // n_views rows of head tiles
+    uint32_t* d_tile_survivors = nullptr;
+    size_t words_cap = 0, head_rows_cap = 0, survivor_rows_cap = 0;
+  };
+  ClusterViewScratch cluster_views;
+  uint32_t* h_cluster_views_status = nullptr;  // pinned, device-visible, two words: the code an asynchronous / a synchronous mip_cull_clusters_views raised
   uint32_t* h_cluster_status = nullptr;  // pinned, device-visible, two words per frame slot: the code an asynchronous / a synchronous cull of the slot raised
   hipEvent_t cluster_pyramid_ready = nullptr;  // orders a cull behind a pyramid built on another slot's stream
   hipEvent_t cluster_record_written = nullptr;  // behind the last FIRST call of mip_cull_clusters_phase: its SECOND call waits for it, on whichever slot's stream

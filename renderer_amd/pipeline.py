@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
                    MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
@@ -151,6 +151,22 @@ def make_cluster_outputs(cluster_cmds, cmd_capacity, cmd_count, stats=0, work_ca
     o.cmd_capacity = int(cmd_capacity)
     o.work_capacity = int(work_capacity)
     o.cmd_count = cmd_count or None
+    o.stats = stats or None
+    return o
+
+
+def make_cluster_view_outputs(cluster_cmds, cmd_stride, cmd_counts, stats=0, work_capacity=0, async_=False):
+    """A MipClusterViewOutputs for cull_clusters_views: device pointers to room for n_views x cmd_stride commands (view v's
+    start at entry v x cmd_stride), to the n_views counts and (optional) to the 2 + 2 x n_views stats words {W, members, then
+    heads and surviving clusters per view}; work_capacity bounds the work items of the union of the views' members (0 = N x
+    the largest cluster count of a level, which is also what the call's scratch is sized by)."""
+    o = MipClusterViewOutputs()
+    o.struct_size = C.sizeof(MipClusterViewOutputs)
+    o.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+    o.cluster_cmds = cluster_cmds or None
+    o.cmd_stride = int(cmd_stride)
+    o.work_capacity = int(work_capacity)
+    o.cmd_counts = cmd_counts or None
     o.stats = stats or None
     return o
 
@@ -704,6 +720,22 @@ class InstancePipeline:
         exceed work_capacity."""
         self._check(self._lib.mip_cull_cluster_triangles(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                          C.addressof(occlusion) if occlusion is not None else None, C.addressof(outputs)))
+
+    def cull_clusters_views(self, frames, visible_bitmap_ptrs, policy, outputs):
+        """mip_cull_clusters_views: cull_clusters' frustum test for up to 16 views in one call. frames[v] (make_frame: planes
+        and first_instance_base are read; the level of every instance comes from frames[0]'s cam_pos for ALL views) goes with
+        visible_bitmap_ptrs[v], a device bitmap or 0 / None for every resident instance. View v's commands are entries
+        [v * cmd_stride, v * cmd_stride + cmd_counts[v]) of `outputs` (make_cluster_view_outputs). Enqueued on the context's
+        first stream, behind a run_views. MIP_ERR_CAPACITY (from wait() for an asynchronous call) when a view's runs do not
+        fit cmd_stride or the work items exceed work_capacity."""
+        k = len(frames)
+        if len(visible_bitmap_ptrs) != k:
+            raise ValueError("one bitmap pointer (or None) per frame")
+        fr = (MipFrame * max(k, 1))()
+        for v in range(k):
+            C.memmove(C.addressof(fr[v]), C.addressof(frames[v]), C.sizeof(MipFrame))
+        bm = (C.c_void_p * max(k, 1))(*[int(b) if b else None for b in visible_bitmap_ptrs])
+        self._check(self._lib.mip_cull_clusters_views(self._ctx, C.addressof(fr), C.addressof(bm), k, C.addressof(policy), C.addressof(outputs)))
 
     # -- cluster culling with normal cones (extension) --
     def build_cluster_cones(self):
