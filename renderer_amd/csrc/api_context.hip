@@ -71,15 +71,18 @@ int32_t check_device_error(MipContext* ctx) {
 // Number of instances of [first, first + count) of the resident columns that fail the finite test, and (bad_ids != null)
 // how many of them name a mesh outside a table of `m` entries.
 // Synchronous (uploads are): one small kernel and an 8-byte read-back on the upload stream.
-int32_t census(MipContext* ctx, uint32_t first, uint32_t count, uint32_t* out, uint32_t* bad_ids, uint32_t m) {
+int32_t census(MipContext* ctx, uint32_t first, uint32_t count, uint32_t* out, uint32_t* bad_ids, uint32_t m, bool narrow) {
   *out = 0;
   if (bad_ids) *bad_ids = 0;
   if (!count) return MIP_OK;
   MIP_HIP(ctx, hipMemsetAsync(ctx->d_census, 0, 8, ctx->stream));
   mip::CensusArgs c{};
   c.pos = ctx->d_pos; c.rot = ctx->d_rot; c.scale = ctx->d_scale;
-  c.mesh_id = bad_ids ? ctx->d_mesh_id : nullptr;
-  c.n_meshes = m;
+  narrow = narrow && ctx->d_frame_ids;
+  c.mesh_id = bad_ids || narrow ? ctx->d_mesh_id : nullptr;
+  c.narrow_ids = narrow ? ctx->d_frame_ids : nullptr;
+  c.narrow_bytes = ctx->frame_id_bytes;
+  c.n_meshes = bad_ids ? m : 0xffffffffu;
   c.first = first; c.count = count; c.out = ctx->d_census;
   c.box_abs = ctx->box_abs;
   uint32_t blocks = (count + 255u) / 256u;
@@ -110,6 +113,7 @@ void free_all(MipContext* ctx) {
   (void)hipFree(ctx->d_rot);
   (void)hipFree(ctx->d_scale);
   (void)hipFree(ctx->d_mesh_id);
+  (void)hipFree(ctx->d_frame_ids);
   (void)hipFree(ctx->d_meshes);
   (void)hipFree(ctx->d_census);
   (void)hipFree(ctx->d_help);
@@ -205,6 +209,9 @@ int32_t mip_create(const MipConfig* cfg, MipContext** out) {
     MIP_HIP(ctx, hipMalloc(&ctx->d_rot, cap * 16));
     MIP_HIP(ctx, hipMalloc(&ctx->d_scale, cap * 4));
     MIP_HIP(ctx, hipMalloc(&ctx->d_mesh_id, cap * 4));
+    // the frame kernel's narrow copy of the ids: 1 or 2 bytes per instance on top of the u32 column, which every other kernel keeps
+    ctx->frame_id_bytes = mip::plan_frame_id_bytes(ctx->max_meshes, std::getenv("MIP_TUNE_WIDE_IDS") != nullptr);
+    if (ctx->frame_id_bytes) MIP_HIP(ctx, hipMalloc(&ctx->d_frame_ids, (cap * ctx->frame_id_bytes + 3) / 4 * 4));  // whole words: the kernel reads the word an id lies in
     MIP_HIP(ctx, hipMalloc(&ctx->d_meshes, mcap * sizeof(mip::MeshEntry)));
     MIP_HIP(ctx, hipMalloc(&ctx->d_mesh_draw, mcap * sizeof(mip::MeshDraw)));
     MIP_HIP(ctx, hipMalloc(&ctx->d_mesh_chain, mcap * sizeof(mip::MeshChain)));
@@ -337,7 +344,8 @@ int32_t mip_set_mesh_table(MipContext* ctx, const MipMesh* meshes, uint32_t m) {
     MIP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the sources are locals
   }
   // recorded launches carry what follows from the table's SIZE in their arguments (n_meshes, the wire form's index bits, and whether
-  // the one entry of a one-mesh table is read as a scalar: KernelArgs.one_mesh): another size, another recording
+  // the one entry of a one-mesh table is read as a scalar: KernelArgs.id_mode — the id WIDTH and the id pointers never change
+  // during a context's life): another size, another recording
   if (m != ctx->m) ctx->graph_generation++;
   ctx->m = m;
   ctx->lod_buckets = bucket_lod.size();
@@ -427,7 +435,7 @@ static int32_t set_instances_common(MipContext* ctx, const void* pos, const void
     MIP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // stream-ordered copies: finished before any slot launches again
   }
   uint32_t bad = 0, bad_ids = 0;
-  if (int32_t rc = census(ctx, 0, n, &bad, &bad_ids, ctx->m)) return rc;
+  if (int32_t rc = census(ctx, 0, n, &bad, &bad_ids, ctx->m, true)) return rc;  // (and fills the frame kernel's narrow ids)
   if (bad_ids) {
     // the resident columns now hold ids the frame kernel would follow out of the mesh table: nothing is resident
     ctx->have_instances = false;
@@ -479,7 +487,7 @@ int32_t mip_update_instances(MipContext* ctx, uint32_t first, uint32_t count, co
     if (scale) MIP_HIP(ctx, hipMemcpyAsync(ctx->d_scale + first, scale, (size_t)count * 4, hipMemcpyHostToDevice, ctx->stream));
     if (mesh_id) MIP_HIP(ctx, hipMemcpyAsync(ctx->d_mesh_id + first, mesh_id, (size_t)count * 4, hipMemcpyHostToDevice, ctx->stream));
     MIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (int32_t rc = census(ctx, first, count, &bad_after)) return rc;
+    if (int32_t rc = census(ctx, first, count, &bad_after, nullptr, 0, mesh_id != nullptr)) return rc;  // (new ids: narrowed for the frame kernel too)
     const uint64_t total = ctx->nonfinite_instances - bad_before + bad_after;
     if ((total != 0) != (ctx->nonfinite_instances != 0)) ctx->graph_generation++;
     ctx->nonfinite_instances = total;

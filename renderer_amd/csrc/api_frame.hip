@@ -117,7 +117,10 @@ void fill_kernel_args(MipContext* ctx, MipContext::FrameSlot& sl, const mip::Lau
   a.n = n;
   a.bitmap_words = (n + 31u) / 32u;
   a.n_meshes = ctx->m;
-  a.one_mesh = ctx->m == 1u && !ctx->no_one_mesh ? 1u : 0u;
+  // the narrow ids for the stores-first order, whose launches are bound by the bytes they move; the commands-first order's are
+  // all latency and measured slower on them (plan_frame_id_mode)
+  a.id_mode = mip::plan_frame_id_mode(ctx->m, plan.order == 1 ? ctx->frame_id_bytes : 0u, ctx->no_one_mesh);
+  a.frame_ids = a.id_mode == mip::kIdsU8 || a.id_mode == mip::kIdsU16 ? ctx->d_frame_ids : ctx->d_mesh_id;
   a.wire_index_bits = mip_wire_index_bits(ctx->m);
   a.first_instance_base = frame->first_instance_base;
   a.first_index_base = frame->first_index_base;

@@ -179,6 +179,11 @@ struct MipContext {
   float4* d_rot = nullptr;
   float* d_scale = nullptr;
   uint32_t* d_mesh_id = nullptr;
+  // the frame kernel's copy of the ids, frame_id_bytes (1 | 2) each: plan_frame_id_bytes(max_meshes), fixed at creation; every
+  // upload that writes d_mesh_id writes it too (in the census kernel). 0 / null: max_meshes > 65 536, or
+  // MIP_TUNE_WIDE_IDS — the frame kernel reads d_mesh_id like every other kernel
+  void* d_frame_ids = nullptr;
+  uint32_t frame_id_bytes = 0;
   mip::MeshEntry* d_meshes = nullptr;
   mip::MeshDraw* d_mesh_draw = nullptr;
   mip::MeshChain* d_mesh_chain = nullptr;  // mip_batch_draws_lods: every level of every mesh (filled by mip_set_mesh_table)
@@ -355,7 +360,8 @@ int32_t sync_all(MipContext* ctx);
 int32_t check_device_error(MipContext* ctx);
 // Number of instances of [first, first + count) that fail the finite test, and (bad_ids != null) how many name a mesh
 // outside a table of `m` entries. Synchronous.
-int32_t census(MipContext* ctx, uint32_t first, uint32_t count, uint32_t* out, uint32_t* bad_ids = nullptr, uint32_t m = 0);
+// narrow: the kernel also writes the ids of the range into the frame kernel's narrow column (d_frame_ids), where the context has one.
+int32_t census(MipContext* ctx, uint32_t first, uint32_t count, uint32_t* out, uint32_t* bad_ids = nullptr, uint32_t m = 0, bool narrow = false);
 void drop_graphs(MipContext* ctx);                    // api_frame.hip
 // The tail of every entry point that enqueues on `stream`: asynchronous calls leave it to mip_wait, the others drain it.
 inline int32_t finish(MipContext* ctx, hipStream_t stream, bool async) {

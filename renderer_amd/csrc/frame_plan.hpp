@@ -102,6 +102,23 @@ inline uint32_t plan_wire_index_bits(uint32_t n_meshes) {
   return 31u - mesh_bits;
 }
 
+// The frame kernel's copy of the resident mesh ids (MipContext::d_frame_ids): as narrow as the context's max_meshes allows — the
+// table can never hold more entries than that, so the width is fixed for the life of the context and no id can outgrow it.
+// 0: no copy, the frame kernel reads the u32 column every other kernel reads.
+inline uint32_t plan_frame_id_bytes(uint32_t max_meshes, bool wide_ids = false) {
+  if (wide_ids) return 0u;  // MIP_TUNE_WIDE_IDS (A/B runs, tests of the u32 path)
+  return max_meshes <= 256u ? 1u : (max_meshes <= 65536u ? 2u : 0u);
+}
+// How the frame kernel gets an instance's mesh: the word that is its leading argument h_id_mode (and KernelArgs.id_mode)
+// (0 and 1 are what the word was while it only said "one mesh"; log2 of a width's bytes, which the kernel shifts by, is mode ^ 2)
+constexpr uint32_t kIdsU32 = 0, kIdsOneMesh = 1, kIdsU8 = 2, kIdsU16 = 3;
+constexpr uint32_t plan_frame_id_log_bytes(uint32_t mode) { return (mode ^ 2u) & 3u; }
+static_assert(plan_frame_id_log_bytes(kIdsU8) == 0 && plan_frame_id_log_bytes(kIdsU16) == 1 && plan_frame_id_log_bytes(kIdsU32) == 2, "id modes");
+inline uint32_t plan_frame_id_mode(uint32_t n_meshes, uint32_t id_bytes, bool no_one_mesh = false) {
+  if (n_meshes == 1u && !no_one_mesh) return kIdsOneMesh;  // the one entry is a scalar load: no id is read at all
+  return id_bytes == 1u ? kIdsU8 : (id_bytes == 2u ? kIdsU16 : kIdsU32);
+}
+
 inline LaunchPlan plan_refuse(int32_t status, const char* why) {
   LaunchPlan p;
   p.status = status;

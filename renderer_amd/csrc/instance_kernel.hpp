@@ -3,7 +3,7 @@
 // One fused, single-pass kernel per frame:
 //
 //   tile = 256 instances = one 256-thread workgroup (4 wave64), one instance per lane
-//   loads   : pos (12 B) + quat (16 B) + scale (4 B) + mesh id (4 B)            = 36 B
+//   loads   : pos (12 B) + quat (16 B) + scale (4 B) + mesh id (1, 2 or 4 B)    = 33 .. 36 B
 //   compute : M = T·R·S, 8-corner world AABB, 6-plane test, LOD pick             (VALU, no FMA)
 //   stores  : mat4 through an LDS transpose so every store instruction writes
 //             1 KiB contiguous (64 B per instance; buffer_store_dwordx4 ... sc1 nt), 1 visibility bit, and — after a one-hop look-up of
@@ -28,6 +28,8 @@
 
 #include <type_traits>
 #include <stdint.h>
+
+#include "frame_plan.hpp"  // the id modes (kIdsU32 ..): the pure rule the host picks them by lives there
 
 #pragma clang fp contract(off)
 
@@ -71,6 +73,23 @@ __device__ __forceinline__ MeshEntry mesh_entry(float4 mb0, float4 mb1) {
   mb.max_x = mb1.x; mb.max_y = mb1.y; mb.max_z = mb1.z; mb.len1 = __float_as_uint(mb1.w);
   return mb;
 }
+// Instance i's mesh from the frame kernel's id column (KernelArgs.frame_ids) in the width `mode` names (not kIdsOneMesh: no id
+// is read then): the aligned word that holds the element, then the element out of it — ONE load instruction whatever the
+// width, the width in scalar registers, no branch on `mode` in front of the load that starts the tile's longest dependency
+// chain (id -> table gather). A byte / halfword / word load each behind its own branch measured the same at 1 M and above.
+// The four lanes (two) that share a word read it with one request; the column's allocation is a whole number of words.
+// In two steps, so that the frame kernel can issue the load at its head and take the element out where it needs it.
+__device__ __forceinline__ uint32_t load_frame_id_word(const void* ids, uint32_t mode, uint32_t i) {
+  const size_t at = (size_t)i << plan_frame_id_log_bytes(mode);
+  return *reinterpret_cast<const uint32_t*>(static_cast<const char*>(ids) + (at & ~(size_t)3));
+}
+__device__ __forceinline__ uint32_t frame_id_of_word(uint32_t word, uint32_t mode, uint32_t i) {
+  const uint32_t log_bytes = plan_frame_id_log_bytes(mode);
+  return (word >> (((i << log_bytes) & 3u) * 8u)) & (0xffffffffu >> (32u - (8u << log_bytes)));
+}
+__device__ __forceinline__ uint32_t load_frame_id(const void* ids, uint32_t mode, uint32_t i) {
+  return frame_id_of_word(load_frame_id_word(ids, mode, i), mode, i);
+}
 __device__ __forceinline__ MeshEntry load_mesh_entry(const MeshEntry* meshes, uint32_t mesh) {
   return mesh_entry(*reinterpret_cast<const float4*>(&meshes[mesh].min_x), *reinterpret_cast<const float4*>(&meshes[mesh].max_x));
 }
@@ -99,7 +118,7 @@ struct KernelArgs {
   const float* pos;             // n*3
   const float4* rot;            // n  [i,j,k,w]
   const float* scale;           // n
-  const uint32_t* mesh_id;      // n
+  const uint32_t* mesh_id;      // n: the u32 column (the occluded frame kernel reads it; the frame kernel reads `frame_ids`)
   const MeshEntry* meshes;      // m
   const MeshDraw* mesh_draw;    // m (the commands-first order gathers from it at the tile's head)
   uint32_t* cmds;               // n*5 or null
@@ -133,12 +152,14 @@ struct KernelArgs {
   const unsigned long long* blas_address;  // m, BLAS device address per mesh (with tlas_instances)
   const float* box_override;    // n*8 or null: per-instance mesh-space box {min xyz, -, max xyz, -} that replaces the mesh table's (skinned instances)
   uint32_t wire_index_bits;     // MIP_OUT_WIRE_PACKED: bits of a record that hold the instance index (mesh id above them, LOD in bit 31)
-  uint32_t one_mesh;            // 1: the mesh table has one entry (the kernel's leading argument h_one_mesh)
+  uint32_t id_mode;             // kIdsU32 | kIdsOneMesh: the mesh table has one entry, no id is read | kIdsU8 | kIdsU16 (the leading argument h_id_mode)
   uint32_t first_mover_rule;    // 1: this launch follows the first-mover rule (the host's choice: api_frame.hip, MIP_TUNE_FIRST_MOVER)
   uint32_t* error_flag;         // host-mapped error words
   uint32_t* help_counter;       // DEVICE memory: tile aggregates that waiting tiles computed themselves (MipTimings.prefix_helps), kHelpShards words
   uint32_t* helps_seen;         // DEVICE memory, one word beside the prefix state: the help count the last launch that looked saw
   uint32_t* help_hint;          // host-mapped word (or null: nobody is told): note_helps_for_the_host
+  const void* frame_ids;        // n mesh ids as `id_mode` says: u8, u16, or the u32 column itself (the kernel's leading argument h_ids; read from
+                                // here by the cold path only. Last: no field the hot path reads from the block moved when it was added)
 #ifdef MIP_DEBUG_STAMPS
   unsigned long long* stamps;  // diagnostic build only: 8 realtime stamps per tile
   uint32_t debug_skip_publish_tile;  // diagnostic build only: tile index + 1 that never publishes (0 = off)
@@ -148,7 +169,7 @@ struct KernelArgs {
 #endif
 };
 
-// The frame kernel's leading scalar arguments (MIP_FRAME_HEAD_PARAMS, at the kernel): 6 pointers, n, one_mesh — to the block's
+// The frame kernel's leading scalar arguments (MIP_FRAME_HEAD_PARAMS, at the kernel): 6 pointers, n, id_mode — to the block's
 // alignment — where KernelArgs starts in the kernarg segment.
 constexpr uint32_t kFrameHeadBytes = 56;
 static_assert(alignof(KernelArgs) == 8 && 6 * sizeof(void*) + 2 * sizeof(uint32_t) <= kFrameHeadBytes && kFrameHeadBytes % alignof(KernelArgs) == 0, "argument layout");
@@ -866,7 +887,9 @@ __device__ __forceinline__ float separable_bound(const float (&r)[3][3], float p
 // launched as mip_instance_pipeline_kernel<.., .., kGeneral = false>.
 struct CensusArgs {
   const float* pos; const float4* rot; const float* scale;
-  const uint32_t* mesh_id;  // or null: ids not checked
+  const uint32_t* mesh_id;  // or null: ids neither checked nor narrowed
+  void* narrow_ids;         // or null: the frame kernel's id column (MipContext::d_frame_ids), written for [first, first + count)
+  uint32_t narrow_bytes;    //          1 | 2: its element. One byte or halfword store per instance: a range may start and end anywhere
   uint32_t n_meshes;
   uint32_t first, count;
   float box_abs;  // largest sum of |box coordinates| over the mesh table
@@ -885,7 +908,15 @@ static __global__ __launch_bounds__(256) __attribute__((unused)) void mip_count_
     const float px = a.pos[3 * i], py = a.pos[3 * i + 1], pz = a.pos[3 * i + 2], sc = a.scale[i];
     const bool ok = finite_magnitude(r, px, py, pz, sc) < kFiniteLimit && separable_bound(r, px, py, pz, sc, a.box_abs) < kSeparableLimit;
     bad += ok ? 0u : 1u;
-    if (a.mesh_id) bad_id += a.mesh_id[i] >= a.n_meshes ? 1u : 0u;
+    if (a.mesh_id) {
+      const uint32_t id = a.mesh_id[i];
+      bad_id += id >= a.n_meshes ? 1u : 0u;
+      // (an id outside the table is truncated here: the upload is refused and nothing stays resident)
+      if (a.narrow_ids) {
+        if (a.narrow_bytes == 1u) static_cast<uint8_t*>(a.narrow_ids)[i] = (uint8_t)id;
+        else static_cast<uint16_t*>(a.narrow_ids)[i] = (uint16_t)id;
+      }
+    }
   }
   bad = wave_sum(bad);
   bad_id = wave_sum(bad_id);
@@ -1120,7 +1151,8 @@ __device__ __forceinline__ unsigned long long help_tile_aggregate(uint32_t u, ui
   const float* pos = ka->pos;
   const float4* rot = ka->rot;
   const float* scale = ka->scale;
-  const uint32_t* mesh_id = ka->mesh_id;
+  const void* ids = ka->frame_ids;
+  const uint32_t id_mode = ka->id_mode;
   const MeshEntry* meshes = ka->meshes;
   const uint32_t n = ka->n;
   struct { const float* box_override; } box_args = {ka->box_override};
@@ -1134,7 +1166,7 @@ __device__ __forceinline__ unsigned long long help_tile_aggregate(uint32_t u, ui
     const float px = pos[3 * (size_t)jl + 0], py = pos[3 * (size_t)jl + 1], pz = pos[3 * (size_t)jl + 2];
     const float4 q = rot[jl];
     const float sc = scale[jl];
-    const uint32_t mesh = mesh_id[jl];
+    const uint32_t mesh = id_mode == kIdsOneMesh ? 0u : load_frame_id(ids, id_mode, jl);  // what the tile's owner reads
     MeshEntry mb = load_mesh_entry(meshes, mesh);
     float r[3][3];
     quat_to_rotation(q.x, q.y, q.z, q.w, r);
@@ -1174,14 +1206,14 @@ constexpr uint32_t kAggHelpedFirst = 1u << 16;  // a helping wave adds this tile
 // packed form (MIP_OUT_WIRE_PACKED, wire_packed_copy_out; KernelArgs.wire_index_bits); 0 = 20-byte commands. A template
 // parameter, not a run-time flag: as a flag it cost the plain frame 0.2 us at 100 k and at 1 M (profiles/r03_vs_r02_kbench.txt).
 // The kernel's arguments: what a tile needs before it can issue its first load — the input arrays, the tables, the command
-// pointer (is there a prefix at all), n and whether the mesh table has ONE entry — as LEADING SCALAR arguments, 14 dwords (a wave has 16 user SGPRs, two of them the
+// pointer (is there a prefix at all), n and how the mesh ids are stored (u8 / u16 / u32, or not read: a table of ONE entry) — as LEADING SCALAR arguments, 14 dwords (a wave has 16 user SGPRs, two of them the
 // kernarg segment's address: 14 can be preloaded), which the dispatcher preloads into SGPRs
 // (-mllvm -amdgpu-kernarg-preload-count=16: Makefile) before the wave's first instruction; then the argument block. Inside the
 // block the same values were a scalar load from the kernarg segment and a wait — a round trip in front of every tile's instance
 // loads (profiles/r05_tile_head.txt). The block keeps its copies: the cold path (help_tile_aggregate) and the late uses read those.
 #define MIP_FRAME_HEAD_PARAMS                                                                                              \
   const float* __restrict__ h_pos, const float4* __restrict__ h_rot, const float* __restrict__ h_scale,                    \
-      const uint32_t* __restrict__ h_mesh_id, const MeshEntry* __restrict__ h_meshes, uint32_t* h_cmds, uint32_t h_n, uint32_t h_one_mesh
+      const void* __restrict__ h_ids, const MeshEntry* __restrict__ h_meshes, uint32_t* h_cmds, uint32_t h_n, uint32_t h_id_mode
 
 // kFirstMover: the launch follows the first-mover rule (KernelArgs::kFirstMoverAdds above; the host launches this instantiation
 // when KernelArgs.first_mover_rule == 1). An instantiation of its own: as a run-time flag the rule's branches and the registers
@@ -1223,7 +1255,7 @@ __global__ __launch_bounds__(kTile, kGeneral ? MIP_MIN_WAVES_PER_SIMD : 8) void 
 #endif
   unsigned long long granule_before = 0;
 
-  // ---- loads: 36 B per instance. FIRST, from preloaded arguments: nothing is waited for in front of them. (Behind the frame
+  // ---- loads: 33 .. 36 B per instance. FIRST, from preloaded arguments: nothing is waited for in front of them. (Behind the frame
   //      below, with the pointers in the argument block, the compiler fetched `frame_ring`, waited, branched on it, and only then
   //      fetched the pointers: two scalar round trips in front of the first instance load. The planes now arrive under the loads.) ----
   const float px = h_pos[3 * (size_t)il + 0], py = h_pos[3 * (size_t)il + 1], pz = h_pos[3 * (size_t)il + 2];
@@ -1232,15 +1264,30 @@ __global__ __launch_bounds__(kTile, kGeneral ? MIP_MIN_WAVES_PER_SIMD : 8) void 
   // A mesh table of ONE entry (BASELINE configs[1]: 100 k instances of one mesh): every id is 0 (uploads with an id outside the
   // table are refused) and the entry is the same for every lane — a scalar load issued here, beside the instance loads, instead of
   // an id load and a gather BEHIND it: one dependent round trip and 4 of the 36 input bytes per instance less.
-  uint32_t mesh = 0;
+  // Every other table: the id from the resident copy that is as narrow as the context's max_meshes allows — 1 B up to 256 meshes,
+  // 2 B up to 65 536 (filled at every upload by mip_count_nonfinite_kernel), else the u32 column. The launch is bound by the bytes
+  // it moves; of a u32 id of a 64-mesh table three bytes carry nothing.
+  uint32_t mesh = 0, id_word = 0;
   float4 mb0, mb1;
-  if (!h_one_mesh) {
-    mesh = h_mesh_id[il];
-  } else {  // (through the constant address space: a uniform address there is a scalar load; the table is not written during a launch)
+  auto load_the_one_entry = [&]() {  // (through the constant address space: a uniform address there is a scalar load; the table is not written during a launch)
     typedef const __attribute__((address_space(4))) float* ConstWords;
     ConstWords e = (ConstWords)(unsigned long long)h_meshes;
     mb0 = make_float4(e[0], e[1], e[2], e[3]);
     mb1 = make_float4(e[4], e[5], e[6], e[7]);
+  };
+  // Only the stores-first order, whose launches are bound by the bytes they move, reads the narrow copy. The commands-first order's
+  // launches are all latency: the host hands them the u32 column (kIdsU32) and they read it with the code they always had. How the
+  // two branches are written decides where the compiler waits for loads: with the id loaded in one `if` and the entry in a second
+  // one, the commands-first order waited for its table gather 28 instructions early (a register that one path had loaded into
+  // counted as pending on the other) and lost 0.07 us at 100 k and 0.25 us at 524 288 (profiles/narrow_ids_ab.txt); the
+  // stores-first order written as if / else waited for every instance load in front of the one-mesh path's `mesh = 0`.
+  if constexpr (kOrder == 3) {
+    static_assert(kIdsU32 == 0, "the commands-first order is handed kIdsU32 or kIdsOneMesh, and tests the word as it always did");
+    if (!h_id_mode) mesh = static_cast<const uint32_t*>(h_ids)[il];
+    else load_the_one_entry();
+  } else {
+    if (h_id_mode != kIdsOneMesh) id_word = load_frame_id_word(h_ids, h_id_mode, il);
+    if (h_id_mode == kIdsOneMesh) load_the_one_entry();
   }
   // ---- the frame: kernel arguments, or (recorded launches) 128 B of device memory read by the
   //      first 32 lanes of every wave and broadcast, in flight together with the instance loads ----
@@ -1273,7 +1320,8 @@ __global__ __launch_bounds__(kTile, kGeneral ? MIP_MIN_WAVES_PER_SIMD : 8) void 
     __syncthreads();
   }
   // (a copy of small mesh tables in LDS was measured: no gain — profiles/r02_lds_pad_occupancy_and_mesh_cache_ab.txt)
-  if (!h_one_mesh) {
+  if (kOrder == 3 ? !h_id_mode : h_id_mode != kIdsOneMesh) {
+    if constexpr (kOrder == 1) mesh = frame_id_of_word(id_word, h_id_mode, il);
     mb0 = *reinterpret_cast<const float4*>(&h_meshes[mesh].min_x);
     mb1 = *reinterpret_cast<const float4*>(&h_meshes[mesh].max_x);
   }
