@@ -3,6 +3,8 @@ oracle. Bit-exact final commands, count and culled index stream."""
 import numpy as np
 import pytest
 
+from triangle_variants import force_variant as _force_variant
+
 pytestmark = pytest.mark.gpu
 
 
@@ -65,42 +67,6 @@ def test_triangle_cull_matches_oracle(ra, oracle_mod, config, n, allvis):
     assert np.array_equal(got_out, want_out)
     survivors = int(want_cmds["indexCount"].astype(np.int64).sum())
     assert 0 < survivors < int(r["draw_cmds"]["indexCount"].astype(np.int64).sum())  # something was culled, something survived
-
-
-def _force_variant(monkeypatch, mode):
-    """Forces one decomposition of the stage (tuning variables, read by mip_create and at launch)."""
-    if mode == "ranges":
-        pass                                                     # the default at this size: one range per wave
-    elif mode == "ranges_ticketed":
-        monkeypatch.setenv("MIP_TUNE_TRI_RANGE_SLOTS", "256")    # a long stream by this measure: 256-slot ranges, most of them pulled from the counter
-    elif mode == "recompact_three_launches":
-        monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_MAX", "0")
-        monkeypatch.setenv("MIP_TUNE_TRI_RECOMPACT_LAUNCHES", "3")  # round 4's count / scan / scatter instead of the one-launch re-compaction
-    elif mode in ("ranges_or_sorted_waves", "sorted_waves", "ranges_of_a_large_frame"):
-        monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_MAX", "0")        # the large-frame path: prepare + scatter kernels, one grid, the decomposition chosen on the device ...
-        if mode == "sorted_waves":
-            monkeypatch.setenv("MIP_TUNE_TRI_CHOICE", "waves")   # ... forced to the wave-per-command grid
-        elif mode == "ranges_of_a_large_frame":
-            monkeypatch.setenv("MIP_TUNE_TRI_CHOICE", "block")   # ... forced to the range kernel's
-            monkeypatch.setenv("MIP_TUNE_TRI_RANGE_SLOTS", "512")
-    else:
-        monkeypatch.setenv("MIP_TUNE_TRI_CHUNKS_FROM", "4294967295")  # the round-4 kernels
-    if mode in ("wave", "wave_only", "tickets", "tickets_x4"):
-        monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_MAX", "0")   # the large-frame path: both grids, one chosen on the device ...
-        monkeypatch.setenv("MIP_TUNE_TRI_PARTS_MAX", "0")
-        if mode == "wave":
-            monkeypatch.setenv("MIP_TUNE_TRI_CHOICE", "waves")  # ... forced to the wave-per-command grid
-        elif mode == "wave_only":
-            monkeypatch.setenv("MIP_TUNE_TRI_NO_CHOICE", "1")   # the second grid is not launched at all
-        else:
-            monkeypatch.setenv("MIP_TUNE_TRI_CHOICE", "block")  # ... to the ticket-pulling workgroup grid
-            if mode == "tickets_x4":
-                monkeypatch.setenv("MIP_TUNE_TRI_BATCH_FROM", "100")  # four consecutive commands per ticket (default: from 65 536 commands)
-    elif mode == "parts":  # 16 work items per command (small frames), forced onto this larger frame
-        monkeypatch.setenv("MIP_TUNE_TRI_PARTS_MAX", "100000000")
-    else:
-        monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_MAX", "100000000")
-        monkeypatch.setenv("MIP_TUNE_TRI_BLOCK_THREADS", mode[5:])
 
 
 @pytest.mark.parametrize("mode", ["ranges", "ranges_ticketed", "ranges_or_sorted_waves", "sorted_waves", "ranges_of_a_large_frame", "recompact_three_launches",
