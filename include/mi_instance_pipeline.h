@@ -266,7 +266,10 @@ void mip_destroy(MipContext* ctx);
 /* Copy the mesh table to the device (caller keeps its memory). m <= max_meshes.
  * Bounds must be finite and n_lods in 1..MIP_MAX_LODS. If the table is smaller than the one it replaces and a
  * resident instance names a mesh outside it, the instances stop being resident (upload the new scene's
- * next; a frame before that fails with MIP_ERR_NOT_READY): the kernels never gather outside the table. */
+ * next; a frame before that fails with MIP_ERR_NOT_READY): the kernels never gather outside the table.
+ * The BLAS addresses belong to the table they were set for: every call CLEARS them (all max_meshes entries, before it
+ * returns). MipOutputs.tlas_instances then carries accelerationStructureReference 0 — what it carries while no address
+ * was ever set — until mip_set_blas_addresses is called for the new table. */
 int32_t mip_set_mesh_table(MipContext* ctx, const MipMesh* meshes, uint32_t m);
 
 /* Upload the instance columns: SoA, tightly packed, draw_index = array index
@@ -294,7 +297,8 @@ int32_t mip_set_instances_device(MipContext* ctx, const void* pos_xyz, const voi
 
 /* Per-mesh bottom-level acceleration structure device addresses for MipOutputs.tlas_instances
  * (vkGetAccelerationStructureDeviceAddressKHR per GltfMesh, acceleration_strucures.rs:430-437).
- * m must equal the mesh table's size. Host pointer; copied. */
+ * m must equal the mesh table's size. Host pointer; copied. Call it AFTER mip_set_mesh_table, and again after every later
+ * mip_set_mesh_table: replacing the table clears the addresses (reference 0), whatever the new table's size or contents. */
 int32_t mip_set_blas_addresses(MipContext* ctx, const uint64_t* addresses, uint32_t m);
 
 /* Upload the consolidated geometry the per-triangle stage reads (ConsolidatedMeshBuffers'

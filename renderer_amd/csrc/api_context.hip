@@ -336,6 +336,12 @@ int32_t mip_set_mesh_table(MipContext* ctx, const MipMesh* meshes, uint32_t m) {
       ctx->graph_generation++;
     }
   }
+  if (ctx->d_blas) {
+    // the addresses belong to the table this call replaces: reference 0 (what a frame writes while none were ever set) until
+    // mip_set_blas_addresses is called for the new one. All max_meshes entries: a larger table finds no stale or unwritten word
+    MIP_HIP(ctx, hipMemsetAsync(ctx->d_blas, 0, (size_t)(ctx->max_meshes ? ctx->max_meshes : 1) * 8, ctx->stream));
+    MIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
   if (m) {
     MIP_HIP(ctx, hipMemcpyAsync(ctx->d_meshes, entries.data(), m * sizeof(mip::MeshEntry), hipMemcpyHostToDevice, ctx->stream));
     MIP_HIP(ctx, hipMemcpyAsync(ctx->d_mesh_draw, draw.data(), m * sizeof(mip::MeshDraw), hipMemcpyHostToDevice, ctx->stream));

@@ -189,7 +189,8 @@ struct MipContext {
   mip::MeshChain* d_mesh_chain = nullptr;  // mip_batch_draws_lods: every level of every mesh (filled by mip_set_mesh_table)
   uint32_t* d_bucket_lod = nullptr;        //   mesh << 3 | lod of every (mesh, LOD) bucket, MIP_MAX_LODS x max_meshes words
   unsigned long long lod_buckets = 0;      //   B = sum of n_lods over the table
-  unsigned long long* d_blas = nullptr;  // per-mesh BLAS device addresses (optional, row f-4)
+  unsigned long long* d_blas = nullptr;  // per-mesh BLAS device addresses (optional, row f-4): max_meshes entries, allocated by the first
+                                         // mip_set_blas_addresses; zeroed whole by every mip_set_mesh_table (the addresses are the old table's)
   // consolidated geometry for the per-triangle stage (row f-1)
   float* d_vertices = nullptr;
   uint32_t* d_indices = nullptr;

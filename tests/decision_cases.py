@@ -96,11 +96,30 @@ def tier(pos, rot, scale):
     return np.where(separable, 0, np.where(all_finite, 1, 2))
 
 
-def census_fallbacks(s):
-    """mip_count_nonfinite_kernel: the instances that make the host launch the kernels with the fall-back tiers."""
+def table_box_abs(meshes):
+    """MipContext::box_abs as mip_set_mesh_table computes it: the largest sum of |box coordinate| over the table, every mesh's
+    summed in float32 axis by axis, (|min| + |max|) added to the running sum; 0 for an empty table."""
+    best = F(0.0)
+    for k in range(len(meshes)):
+        total = F(0.0)
+        for a in range(3):
+            total = F(total + F(np.abs(F(meshes["aabb_min"][k][a])) + np.abs(F(meshes["aabb_max"][k][a]))))
+        if total > best:
+            best = total
+    return best
+
+
+def census_fails(pos, rot, scale, box_abs=BOX_ABS):
+    """mip_count_nonfinite_kernel, per instance: True where the instance fails the census under a table whose box_abs this is."""
     with np.errstate(all="ignore"):
-        ok = (finite_magnitude(s["pos"], s["rot"], s["scale"]) < FINITE_LIMIT) & (separable_bound(s["pos"], s["rot"], s["scale"]) < SEPARABLE_LIMIT)
-    return int((~ok).sum())
+        ok = (finite_magnitude(pos, rot, scale) < FINITE_LIMIT) & (separable_bound(pos, rot, scale, box_abs) < SEPARABLE_LIMIT)
+    return ~ok
+
+
+def census_fallbacks(s, box_abs=BOX_ABS):
+    """mip_count_nonfinite_kernel: the instances that make the host launch the kernels with the fall-back tiers. box_abs: the
+    resident table's (table_box_abs); the default is that of this module's table."""
+    return int(census_fails(s["pos"], s["rot"], s["scale"], box_abs).sum())
 
 
 # ---- the restatement's decisions, and its five mutants ----
