@@ -310,7 +310,13 @@ int32_t mip_set_geometry(MipContext* ctx, const float* vertex_xyz, uint32_t n_ve
 
 /* One frame: model matrices, world AABBs, visibility, compacted draw commands.
  * Call from one thread at a time per context. Synchronous on return unless
- * MIP_OUT_ASYNC. */
+ * MIP_OUT_ASYNC.
+ * Every output pointer of `out` is optional and independent of the others, except that draw_cmds and draw_count go
+ * together and draw_index_total needs them; a NULL output is not computed-and-dropped into anything, it is not written.
+ * With EVERY pointer NULL the call is valid: it returns MIP_OK, writes nothing (the frame's kernel still runs over the
+ * resident instances and stores nothing; it takes no prefix tag) and leaves the context usable — the next frame is what it
+ * would have been without it. With no resident instances (n = 0) nothing is launched: draw_count (and draw_index_total)
+ * are zeroed, nothing else is touched. */
 int32_t mip_run(MipContext* ctx, const MipFrame* frame, const MipOutputs* out);
 
 /* Enqueue `steps` frames back to back from compiled code — the renderer's 'frame: loop

@@ -389,11 +389,13 @@ class InstancePipeline:
         self._check(self._lib.mip_run(self._ctx, C.byref(frame), C.byref(out)))
 
     def prepare_outputs(self, model=0, visible_bitmap=0, draw_cmds=0, draw_count=0, draw_index_total=0,
-                        world_aabb=0, async_=True, culled_index_buffer=0, culled_index_capacity=0):
+                        world_aabb=0, async_=True, culled_index_buffer=0, culled_index_capacity=0, tlas_instances=0, wire=False):
         """A reusable MipOutputs (device pointers) for run_prepared: keeps the per-frame host cost
-        to one foreign call."""
+        to one foreign call. tlas_instances and wire as run_device takes them."""
         out = MipOutputs()
-        out.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+        form = wire_form(wire)
+        out.flags = (_lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0) | (_lib.MIP_OUT_WIRE if form else 0)
+                     | (_lib.MIP_OUT_WIRE_PACKED if form == 2 else 0))
         out.model = model or None
         out.visible_bitmap = visible_bitmap or None
         out.draw_cmds = draw_cmds or None
@@ -402,6 +404,7 @@ class InstancePipeline:
         out.world_aabb = world_aabb or None
         out.culled_index_buffer = culled_index_buffer or None
         out.culled_index_capacity = int(culled_index_capacity)
+        out.tlas_instances = tlas_instances or None
         out._as_parameter_ = C.c_void_p(C.addressof(out))  # lets ctypes pass the struct by address
         return out
 

@@ -127,10 +127,20 @@ class OraclePipeline:
         self.s = scene
         self.n = scene["n"]
         self.n_meshes = len(scene["meshes"])
+        self.blas = None
+
+    def set_blas_addresses(self, addresses):
+        self.blas = np.ascontiguousarray(addresses, dtype=np.uint64).reshape(-1)
 
     def run_device(self, frame, model=0, visible_bitmap=0, draw_cmds=0, draw_count=0, draw_index_total=0,
-                   world_aabb=0, async_=False, wire=False):
+                   world_aabb=0, async_=False, wire=False, tlas_instances=0):
         s = self.s
+        if self.n == 0:   # as mip_run: the counts are zeroed, nothing else is touched
+            if draw_cmds:
+                _view(draw_count, 4, np.uint32)[0] = 0
+                if draw_index_total:
+                    _view(draw_index_total, 4, np.uint32)[0] = 0
+            return
         r = oracle.run(s["pos"], s["rot"], s["scale"], s["mesh_id"], s["meshes"], np.array(frame.planes[:], np.float32),
                        np.array(frame.cam_pos[:], np.float32), first_instance_base=frame.first_instance_base,
                        first_index_base=frame.first_index_base)
@@ -139,6 +149,11 @@ class OraclePipeline:
             _view(model, n * 64, np.float32)[:] = r["model"].reshape(-1)
         if visible_bitmap:
             _view(visible_bitmap, ((n + 31) // 32) * 4, np.uint32)[:] = r["visible_bitmap"]
+        if world_aabb:
+            _view(world_aabb, n * 24, np.float32)[:] = r["world_aabb"].reshape(-1)
+        if tlas_instances:   # a row for EVERY instance, visible or not; address 0 while no BLAS addresses are set
+            rows = oracle.tlas_instances(r["model"], s["mesh_id"], self.blas, first_instance_base=frame.first_instance_base)
+            _view(tlas_instances, n * 64, np.uint32)[:] = rows.reshape(-1)
         if draw_cmds and wire:
             c = r["draw_count"]
             inst = (r["draw_cmds"]["firstInstance"] - np.uint32(frame.first_instance_base)).astype(np.int64)

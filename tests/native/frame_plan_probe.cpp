@@ -6,6 +6,7 @@
 //     cu_count=256 n=1000 n_meshes=64 frame_slots=1 max_lod_tris=0 max_instances=<n> n_joints=0
 //     nonfinite=0 force_general=0 force_order=0 tri_chunks_from=0 tri_block_max=65536 tri_parts_max=1024 tri_block_threads=0
 //     request=model,bitmap,cmds,aabb,tlas,triangles,skinned,wire,packed,async,host   (cmds implies count and index_total)
+//             draw_cmds,count,index_total   (each pointer of the command outputs on its own: every combination, refused ones too)
 //     sweep=FIRST:LAST:STEP   instead of n=: one line per n = FIRST, FIRST+STEP, ... <= LAST
 // The constants of the prefix structure that are no plan field (tile, level-1 window) are printed with every line.
 #include "../../renderer_amd/csrc/frame_plan.hpp"
@@ -36,9 +37,9 @@ static const char* recompact_name(Recompact r) { return r == Recompact::none ? "
 
 static void print_plan(const PlanState& st, const LaunchPlan& p) {
   std::printf("{\"n\": %u, \"status\": %d, \"empty\": %d, \"n_tiles\": %u, \"order\": %d, \"general\": %d, \"box_override\": %d, \"wire\": %d, "
-              "\"group_shift\": %u, \"tri\": \"%s\", \"tri_threads\": %u, \"tri_blocks\": %u, \"tri_block_tickets\": %d, \"tri_either_blocks\": %u, "
+              "\"group_shift\": %u, \"uses_prefix_state\": %d, \"tri\": \"%s\", \"tri_threads\": %u, \"tri_blocks\": %u, \"tri_block_tickets\": %d, \"tri_either_blocks\": %u, "
               "\"recompact\": \"%s\", \"recompact_blocks\": %u, \"skin\": %d, \"tile\": %u, \"level1_window\": %u}\n",
-              st.n, (int)p.status, (int)p.empty, p.n_tiles, p.order, (int)p.general, (int)p.box_override, p.wire, p.group_shift, tri_name(p.tri),
+              st.n, (int)p.status, (int)p.empty, p.n_tiles, p.order, (int)p.general, (int)p.box_override, p.wire, p.group_shift, (int)p.uses_prefix_state, tri_name(p.tri),
               p.tri_threads, p.tri_blocks, (int)p.tri_block_tickets, p.tri_either_blocks, recompact_name(p.recompact), p.recompact_blocks,
               (int)p.skin, kPlanTile, kProbeLevel1Window);
 }
@@ -89,6 +90,9 @@ int main(int argc, char** argv) {
         if (w == "model") rq.model = true;
         else if (w == "bitmap") rq.bitmap = true;
         else if (w == "cmds") rq.cmds = rq.count = rq.index_total = true;
+        else if (w == "draw_cmds") rq.cmds = true;
+        else if (w == "count") rq.count = true;
+        else if (w == "index_total") rq.index_total = true;
         else if (w == "aabb") rq.aabb = true;
         else if (w == "tlas") rq.tlas = true;
         else if (w == "triangles") rq.triangles = true;
