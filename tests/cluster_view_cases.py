@@ -181,9 +181,14 @@ def view_cams(s, n_views):
     return [(np.asarray(s["cam_pos"], F) + (rng.normal(0, 15, 3) if v else 0)).astype(F) for v in range(n_views)]
 
 
-def view_bases(n_views):
-    """A first_instance_base per view; from view 2 on base + i wraps inside a scene of a few thousand instances."""
-    return [(0x40000000 * v + 1000 * v + 7) & 0xFFFFFFFF if v < 2 else (0xFFFFFFFF - 100 * v) & 0xFFFFFFFF for v in range(n_views)]
+def view_bases(n_views, n=0):
+    """A first_instance_base per view; from view 2 on base + i wraps inside a scene of a few thousand instances. Given the
+    scene's n >= 2, the last view's base is 2^32 - n // 2 as well: base + i wraps in the middle of THIS scene, whatever its
+    size and however few views the call has."""
+    out = [(0x40000000 * v + 1000 * v + 7) & 0xFFFFFFFF if v < 2 else (0xFFFFFFFF - 100 * v) & 0xFFFFFFFF for v in range(n_views)]
+    if n >= 2:
+        out[-1] = (1 << 32) - n // 2
+    return out
 
 
 # (heads, surviving clusters) of the first six turns for config 3 under "strips", full bitmaps, the pin policy: checked on the

@@ -112,11 +112,12 @@ def _views_call(p, s, boxes, n_views, mode, sw, what, kinds=("culled", "shared",
     """mip_run_views over the views that take a culled bitmap, then — with no wait — mip_cull_clusters_views over all of them.
     View v's bitmap is kinds[v % len(kinds)]: "culled" (its own view of mip_run_views), "shared" (view 0's pointer, under view
     v's own planes), "null" (every resident instance). The outputs whole against the restatement, then against one
-    mip_cull_clusters call per view. The cameras behind view 0 are somewhere else: they are not read."""
+    mip_cull_clusters call per view. The cameras behind view 0 are somewhere else: they are not read. The last view's
+    first_instance_base wraps in the middle of the scene (cluster_view_cases.view_bases)."""
     import torch
 
     n = s["n"]
-    cams, frusta, bases = cv.view_cams(s, n_views), cv.frusta(s["planes"], n_views), cv.view_bases(n_views)
+    cams, frusta, bases = cv.view_cams(s, n_views), cv.frusta(s["planes"], n_views), cv.view_bases(n_views, n)
     frames = [make_frame(frusta[v], cams[v], first_instance_base=bases[v]) for v in range(n_views)]
     kind = [kinds[v % len(kinds)] for v in range(n_views)]
     assert "shared" not in kind or kind[0] == "culled"
