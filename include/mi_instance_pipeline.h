@@ -817,7 +817,7 @@ int32_t mip_merge_batches(MipContext* ctx, const void* chunks, uint32_t n_chunks
  * items), so a scene of large meshes should state its bound.
  * OUT OF SCOPE: shards, skinned instances, mip_run_many and recorded graphs; batch_model. (The per-triangle test on
  * surviving clusters is mip_cull_cluster_triangles; the normal-cone back-face test is mip_cull_clusters_cone; several views
- * in one call are mip_cull_clusters_views.) */
+ * in one call are mip_cull_clusters_views; a flat list of the surviving clusters for ONE indirect draw is mip_list_clusters.) */
 #define MIP_CLUSTER_TRIANGLES 64u
 typedef struct MipClusterOutputs {
   uint32_t struct_size;      /* = sizeof(MipClusterOutputs) */
@@ -1067,11 +1067,72 @@ typedef struct MipClusterViewOutputs {
 int32_t mip_cull_clusters_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps,
                                 uint32_t n_views, const MipLodPolicy* policy, const MipClusterViewOutputs* out);
 
+/* ---- Extension: the visible-cluster list for one indirect draw ------------------------------------------------------------
+ * mip_cull_clusters ends in one command per run of surviving clusters. A renderer that culls per cluster rather submits ONE
+ * vkCmdDrawIndirect (or one mesh-task dispatch) over a flat list of the visible clusters, and its vertex shader pulls the
+ * indices itself. mip_list_clusters is mip_cull_clusters (cone == NULL) or mip_cull_clusters_cone (cone given) with that list
+ * in the commands' place: one 16-byte MipClusterEntry per surviving work item, and the arguments of the one draw. NOT a
+ * reference behaviour; checked against this repository's restatement (tests/cluster_list_restatement.py) only. MEMBERS, WORK
+ * ITEMS, W and SURVIVES are the words of mip_cull_clusters above; every entry point above is unchanged.
+ *
+ * SURVIVES: with cone == NULL that of mip_cull_clusters (the planes, and the pyramid when occ is given); with a cone that of
+ * mip_cull_clusters_cone (the cone test in front of it). frame, visible_bitmap, policy and occ are mip_cull_clusters', cone is
+ * mip_cull_clusters_cone's.
+ * ENTRIES: one per surviving work item, in (i, c) order, packed from entry 0. instance = first_instance_base + i (wraps as
+ * firstInstance does), first_index = index_offset[lod] + 192 x c (the source mesh's own range), vertex_offset = the mesh's,
+ * index_count = 3 x the triangles of cluster c (192, or fewer in the last cluster of a level): exactly firstInstance,
+ * firstIndex, vertexOffset and indexCount of the command mip_cull_clusters would write for a run of that one cluster. The list
+ * is therefore the cluster-by-cluster expansion of the command list of mip_cull_clusters / mip_cull_clusters_cone for the same
+ * arguments. entry_count = min(survivors, entry_capacity); entries at or behind it are never touched.
+ * draw_args (optional, 4 words): VkDrawIndirectCommand {vertexCount = 192, instanceCount = entry_count, 0, 0}.
+ * stats (optional, 3 words): {survivors, W, members}.
+ * ENTRY OVERFLOW (survivors > entry_capacity): the first entry_capacity entries are written exactly as they would be with room,
+ * entry_count = entry_capacity and draw_args[1] holds the same value, stats holds the true values, and the status is
+ * MIP_ERR_CAPACITY, reported by WHO REPORTS AN OVERFLOW of mip_cull_clusters: the same status words, the same mip_wait route.
+ * WORK OVERFLOW (W > work_capacity — 0 = the library's own bound, N x the largest C of the table — or W >= 2^32):
+ * MIP_ERR_CAPACITY, entry_count = 0, draw_args = {192, 0, 0, 0}, stats = {0, W mod 2^32, members}; nothing else is written
+ * and the context stays usable.
+ * N = 0 writes a zero count, {192, 0, 0, 0} and zero stats.
+ * REFUSED, nothing written: everything mip_cull_clusters refuses (cluster_entries and entry_count in cluster_cmds' and
+ * cmd_count's place; draw_args 4-byte aligned like the other words); everything mip_cull_clusters_cone refuses about a
+ * non-NULL cone; cluster_entries not 16-byte aligned: MIP_ERR_INVALID_ARGUMENT. MIP_ERR_NOT_READY as for those calls: no
+ * instances, no mesh table, a missing or stale cluster table, and with a cone a missing or stale cone table.
+ * ORDERING and scratch are mip_cull_clusters': the stream of the frame issued last, scratch per frame slot that grows lazily —
+ * 8 bytes per 64 work items of the bound on top of mip_cull_clusters' 16 — and is freed with the rest.
+ *
+ * THE CONSUMER: vkCmdDrawIndirect(cmd, draw_args, 0, 1, 16) with a triangle-list pipeline and no index buffer bound, and
+ *   MipClusterEntry e = entries[gl_InstanceIndex];
+ *   if (gl_VertexIndex < e.index_count) { v = vertices[indices[e.first_index + gl_VertexIndex] + e.vertex_offset];
+ *                                         model = models[e.instance - first_instance_base]; ... }   // (the subtraction wraps as the sum did)
+ *   else gl_Position = vec4(0);   // a degenerate vertex: the triangles of a short last cluster's tail have no area
+ * OUT OF SCOPE: the two-phase record (mip_cull_clusters_phase); several views (mip_cull_clusters_views); the per-triangle test
+ * (mip_cull_cluster_triangles); shards, skinned instances, mip_run_many and recorded graphs. */
+typedef struct MipClusterEntry {
+  uint32_t instance;         /* first_instance_base + i (wraps as firstInstance does) */
+  uint32_t first_index;      /* index_offset[lod] + 192 x c: the source mesh's own range */
+  int32_t vertex_offset;     /* the mesh's */
+  uint32_t index_count;      /* 3 x the triangles of cluster c: 192, or fewer in the last cluster of a level */
+} MipClusterEntry;           /* 16 B: what a one-cluster command of mip_cull_clusters holds */
+typedef struct MipClusterListOutputs {
+  uint32_t struct_size;      /* = sizeof(MipClusterListOutputs) */
+  uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
+  void* cluster_entries;     /* DEVICE, 16-byte aligned: room for entry_capacity MipClusterEntry */
+  uint32_t entry_capacity;   /* entries that fit */
+  uint32_t work_capacity;    /* the caller's bound on W; 0 = N x the largest C of the table */
+  uint32_t* entry_count;     /* DEVICE: entries written = min(survivors, entry_capacity) */
+  uint32_t* draw_args;       /* DEVICE, optional, 4 words: VkDrawIndirectCommand {192, entry_count, 0, 0} */
+  uint32_t* stats;           /* DEVICE, optional, 3 words: survivors, W, members */
+} MipClusterListOutputs;     /* 48 B */
+
+int32_t mip_list_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                          const MipOcclusion* occ /* or NULL */, const MipClusterCone* cone /* or NULL */,
+                          const MipClusterListOutputs* out);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every
  * frames_in_flight frames): it is where their errors surface. The MIP_ERR_CAPACITY of an asynchronous
- * mip_cull_clusters or mip_cull_clusters_views (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase) is returned
+ * mip_cull_clusters, mip_list_clusters or mip_cull_clusters_views (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase) is returned
  * when there is no other error to return; otherwise by the mip_wait after. */
 int32_t mip_wait(MipContext* ctx);
 

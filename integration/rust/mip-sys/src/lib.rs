@@ -231,6 +231,30 @@ pub struct MipClusterCone {
     pub facing: f32,
 }
 
+/// One entry of mip_list_clusters' list: what a one-cluster command of mip_cull_clusters holds; the vertex shader reads it
+/// by gl_InstanceIndex and pulls indices[first_index + gl_VertexIndex] + vertex_offset while gl_VertexIndex < index_count.
+#[repr(C)]
+pub struct MipClusterEntry {
+    pub instance: u32,
+    pub first_index: u32,
+    pub vertex_offset: i32,
+    pub index_count: u32,
+}
+
+/// Outputs of mip_list_clusters: the flat list of surviving clusters and the one VkDrawIndirectCommand over it, device
+/// pointers (see the header).
+#[repr(C)]
+pub struct MipClusterListOutputs {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub cluster_entries: *mut c_void,
+    pub entry_capacity: u32,
+    pub work_capacity: u32,
+    pub entry_count: *mut u32,
+    pub draw_args: *mut u32,
+    pub stats: *mut u32,
+}
+
 /// Per-frame parameters of the occlusion test (mip_cull_clusters reads pyramid, width, height and pv).
 #[repr(C)]
 pub struct MipOcclusion {
@@ -343,6 +367,10 @@ extern "C" {
     /// per work item for all views, planes and first_instance_base per view; on the first stream, behind mip_run_views.
     pub fn mip_cull_clusters_views(ctx: *mut MipContext, frames: *const MipFrame, visible_bitmaps: *const *const u32,
                                    n_views: u32, policy: *const MipLodPolicy, out: *const MipClusterViewOutputs) -> i32;
+    /// mip_cull_clusters (cone null) or mip_cull_clusters_cone with one 16-byte entry per surviving cluster in the commands'
+    /// place, and the arguments of the one indirect draw over the list.
+    pub fn mip_list_clusters(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
+                             occ: *const MipOcclusion, cone: *const MipClusterCone, out: *const MipClusterListOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -364,6 +392,8 @@ const _: [u8; 40] = [0; std::mem::size_of::<MipClusterViewOutputs>()];
 const _: [u8; 24] = [0; std::mem::size_of::<MipClusterRecord>()];
 const _: [u8; 56] = [0; std::mem::size_of::<MipClusterTriangleOutputs>()];
 const _: [u8; 24] = [0; std::mem::size_of::<MipClusterCone>()];
+const _: [u8; 16] = [0; std::mem::size_of::<MipClusterEntry>()];
+const _: [u8; 48] = [0; std::mem::size_of::<MipClusterListOutputs>()];
 const _: [u8; 104] = [0; std::mem::size_of::<MipOcclusion>()];
 
 impl Pipeline {

@@ -8,6 +8,8 @@
 // mip_build_cluster_cones gives every cluster of a valid table a normal cone, and mip_cull_clusters_cone /
 // mip_cull_cluster_triangles_cone are the two culls with the cone's back-face test in front of SURVIVES (one new kernel in
 // the cull kernel's place; every other launch is the plain call's).
+// mip_list_clusters is mip_cull_clusters / mip_cull_clusters_cone with one 16-byte entry per surviving cluster and the arguments
+// of one indirect draw in the commands' place (cluster_list_kernel.hpp, cluster_list_plan.hpp: four new kernels behind the cull).
 // mip_cull_clusters_views is the frustum test of mip_cull_clusters for several views in one call, on the context's first stream
 // with a scratch and a pair of status words of its own (cluster_views_kernel.hpp, cluster_views_plan.hpp).
 // cluster_plan.hpp, cluster_triangle_plan.hpp and cluster_cone_plan.hpp hold the arithmetic and the launch plans; the kernels
@@ -17,12 +19,15 @@
 #include "cluster_triangle_kernel.hpp"
 #include "cluster_cone_kernel.hpp"
 #include "cluster_views_kernel.hpp"
+#include "cluster_list_kernel.hpp"
 
 static_assert(sizeof(MipClusterViewOutputs) == 40, "MipClusterViewOutputs is part of the ABI");
 static_assert(sizeof(MipClusterOutputs) == 40, "MipClusterOutputs is part of the ABI");
 static_assert(sizeof(MipClusterRecord) == 24, "MipClusterRecord is part of the ABI");
 static_assert(sizeof(MipClusterTriangleOutputs) == 56, "MipClusterTriangleOutputs is part of the ABI");
 static_assert(sizeof(MipClusterCone) == 24, "MipClusterCone is part of the ABI");
+static_assert(sizeof(MipClusterEntry) == 16 && sizeof(MipClusterEntry) == sizeof(uint4), "MipClusterEntry is part of the ABI: one 16-byte store");
+static_assert(sizeof(MipClusterListOutputs) == 48, "MipClusterListOutputs is part of the ABI");
 static_assert(sizeof(mip::ClusterConeEntry) == 2 * sizeof(float4), "a cone is the two 16-byte words the kernels load");
 static_assert(mip::kClusterFirst == MIP_CLUSTER_PHASE_FIRST && mip::kClusterSecond == MIP_CLUSTER_PHASE_SECOND, "cluster_kernel.hpp restates the header");
 static_assert(MIP_CLUSTER_TRIANGLES == mip::kClusterTriangles, "cluster_plan.hpp restates the header");
@@ -171,6 +176,14 @@ int32_t ensure_triangle_scratch(MipContext* ctx, MipContext::ClusterScratch& cs,
   return MIP_OK;
 }
 
+// What mip_list_clusters takes on top (cluster_list_plan.hpp): 8 bytes per 64 work items of the bound.
+int32_t ensure_list_scratch(MipContext* ctx, MipContext::ClusterScratch& cs, const mip::ClusterListPlan& plan) {
+  if (int32_t rc = grow(ctx, &cs.d_word_member, &cs.word_member_cap, (size_t)plan.words, 4)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_word_rank, &cs.word_rank_cap, (size_t)plan.words, 4)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_list_tiles, &cs.list_tiles_cap, (size_t)plan.list_tiles, 4)) return rc;
+  return MIP_OK;
+}
+
 // The event a SECOND call waits for: behind everything the FIRST call enqueued.
 int32_t record_written(MipContext* ctx, hipStream_t stream) {
   if (!ctx->cluster_record_written) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_record_written, hipEventDisableTiming));
@@ -191,9 +204,11 @@ int32_t launch(MipContext* ctx, Kernel kernel, uint32_t blocks, hipStream_t stre
 // commands into the culled stream take the place of the epilogue and the commands kernel (nine launches).
 // cone != null (`coned`: the entry point, which refuses a null cone): the cone calls — mip_cluster_cone_cull_kernel in the
 // cull kernel's place, nothing else differs.
+// list != null: mip_list_clusters — `out` holds its fields under mip_cull_clusters' names; the word members, the count, the
+// list's epilogue and the write take the place of heads, epilogue and commands (eight launches). cone may be null or not.
 int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy, const MipOcclusion* occ,
                       const MipClusterOutputs* out, const MipClusterRecord* rec, bool phased, const MipClusterTriangleOutputs* tri = nullptr,
-                      const MipClusterCone* cone = nullptr, bool coned = false) {
+                      const MipClusterCone* cone = nullptr, bool coned = false, const MipClusterListOutputs* list = nullptr) {
   if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
   if (coned)
     if (int32_t rc = check_cone(ctx, cone)) return rc;
@@ -236,7 +251,11 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   const uint32_t n = ctx->n;
   if (n == 0) {  // nothing to test: zeros
     MIP_HIP(ctx, hipMemsetAsync(out->cmd_count, 0, 4, stream));
-    if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, tri ? 4 * mip::kClusterTriangleStats : 16, stream));
+    if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, tri ? 4 * mip::kClusterTriangleStats : list ? 12 : 16, stream));
+    if (list && list->draw_args) {  // {192, 0, 0, 0}
+      MIP_HIP(ctx, hipMemsetAsync(list->draw_args, 0, 16, stream));
+      MIP_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(list->draw_args), (int)mip::kClusterListDrawVertices, 1, stream));
+    }
     if (first) {
       MIP_HIP(ctx, hipMemsetAsync(rec->record, 0, mip::kClusterRecordHeaderBytes, stream));
       if (int32_t rc = record_written(ctx, stream)) return rc;
@@ -260,6 +279,9 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   const mip::ClusterTrianglePlan tri_plan = mip::plan_cluster_triangles(n, bound);
   if (tri)
     if (int32_t rc = ensure_triangle_scratch(ctx, cs, tri_plan)) return rc;
+  const mip::ClusterListPlan list_plan = mip::plan_cluster_list(bound);
+  if (list)
+    if (int32_t rc = ensure_list_scratch(ctx, cs, list_plan)) return rc;
   if (occ && ctx->next_slot != slot) {
     // a pyramid built for the next run sits on that slot's stream: this call goes behind what that stream holds now
     if (!ctx->cluster_pyramid_ready) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_pyramid_ready, hipEventDisableTiming));
@@ -340,10 +362,26 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
                    : first ? launch(ctx, mip::mip_cluster_cull_kernel<true>, plan.cull_blocks, stream, a)
                            : launch(ctx, mip::mip_cluster_cull_kernel<false>, plan.cull_blocks, stream, a))
     return rc;
-  if (int32_t rc = first ? launch(ctx, mip::mip_cluster_heads_kernel<true>, plan.head_blocks, stream, a)
-                         : launch(ctx, mip::mip_cluster_heads_kernel<false>, plan.head_blocks, stream, a))
-    return rc;
-  if (tri) {
+  if (!list)  // (the list counts survivors, not heads)
+    if (int32_t rc = first ? launch(ctx, mip::mip_cluster_heads_kernel<true>, plan.head_blocks, stream, a)
+                           : launch(ctx, mip::mip_cluster_heads_kernel<false>, plan.head_blocks, stream, a))
+      return rc;
+  if (list) {
+    mip::ClusterListArgs la{};
+    la.c = a;
+    la.word_member = cs.d_word_member;
+    la.word_rank = cs.d_word_rank;
+    la.list_tiles = cs.d_list_tiles;
+    la.entries = static_cast<uint4*>(list->cluster_entries);
+    la.entry_capacity = list->entry_capacity;
+    la.entry_count = list->entry_count;
+    la.draw_args = list->draw_args;
+    la.list_stats = list->stats;
+    if (int32_t rc = launch(ctx, mip::mip_cluster_list_word_members_kernel, list_plan.word_blocks, stream, la)) return rc;
+    if (int32_t rc = launch(ctx, mip::mip_cluster_list_count_kernel, list_plan.word_blocks, stream, la)) return rc;
+    if (int32_t rc = launch(ctx, mip::mip_cluster_list_epilogue_kernel, 1, stream, la)) return rc;
+    if (int32_t rc = launch(ctx, mip::mip_cluster_list_write_kernel, list_plan.write_blocks, stream, la)) return rc;
+  } else if (tri) {
     mip::ClusterTriangleArgs ta{};
     ta.c = a;
     ta.vertices = ctx->d_vertices;
@@ -376,6 +414,8 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
     const uint32_t code = *status;
     *status = 0;
     if (code & mip::kClusterStatusDevice) return fail(ctx, MIP_ERR_DEVICE, "%s", kNotItsRecord);
+    if (list)
+      return fail(ctx, MIP_ERR_CAPACITY, "mip_list_clusters: more surviving clusters than entry_capacity (the first entry_capacity entries are written), or more work items than work_capacity / 2^32 - 1 (nothing is written); stats holds the counts");
     if (tri)
       return fail(ctx, MIP_ERR_CAPACITY, "mip_cull_cluster_triangles: more surviving indices than index_capacity or 2^32 - 1 (no command and no index is written; stats[4] holds the surviving triangles), more runs than cmd_capacity (the first cmd_capacity commands and the whole stream are written), or more work items than work_capacity / 2^32 - 1 (nothing is written)");
     return fail(ctx, MIP_ERR_CAPACITY, "mip_cull_clusters: more runs than cmd_capacity (the first cmd_capacity commands are written), or more work items than work_capacity / 2^32 - 1 / the record has words for (nothing is written); stats holds the counts");
@@ -534,7 +574,7 @@ int32_t cluster_wait_status(MipContext* ctx, int32_t rc) {
   }
   if (!raised) return MIP_OK;
   if (raised & mip::kClusterStatusDevice) return fail(ctx, MIP_ERR_DEVICE, "asynchronous %s", kNotItsRecord);
-  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters or mip_cull_clusters_views had more runs than cmd_capacity, or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
+  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters, mip_list_clusters or mip_cull_clusters_views had more runs than cmd_capacity (more surviving clusters than entry_capacity), or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
 }
 
 void cluster_release(MipContext* ctx) {
@@ -556,6 +596,9 @@ void cluster_release(MipContext* ctx) {
     (void)hipFree(cs.d_item_prefix);
     (void)hipFree(cs.d_word_total);
     (void)hipFree(cs.d_tile_triangles);
+    (void)hipFree(cs.d_word_member);
+    (void)hipFree(cs.d_word_rank);
+    (void)hipFree(cs.d_list_tiles);
   }
   ctx->cluster_scratch.clear();
   {
@@ -661,6 +704,32 @@ int32_t mip_cull_clusters_views(MipContext* ctx, const MipFrame* frames, const u
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
   if (int32_t rc = check_policy(ctx, policy)) return rc;
   return cull_clusters_views(ctx, frames, visible_bitmaps, n_views, policy, out);
+}
+
+// mip_list_clusters: the checks of its own fields, then the call it shares with mip_cull_clusters / mip_cull_clusters_cone
+int32_t mip_list_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                          const MipOcclusion* occ, const MipClusterCone* cone, const MipClusterListOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  if (!out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
+  if (out->struct_size != sizeof(MipClusterListOutputs))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterListOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipClusterListOutputs));
+  if (!out->cluster_entries || !out->entry_count) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cluster_entries/entry_count is NULL");
+  if ((uintptr_t)out->cluster_entries % 16u != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cluster_entries is not 16-byte aligned");
+  // the fields it shares with MipClusterOutputs, checked here so that a refusal names this call and this struct
+  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipClusterListOutputs flags 0x%x", out->flags);
+  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_list_clusters needs MIP_OUT_DEVICE outputs");
+  if ((uintptr_t)out->entry_count % 4u != 0u || (uintptr_t)out->draw_args % 4u != 0u || (uintptr_t)out->stats % 4u != 0u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "entry_count, draw_args or stats is not 4-byte aligned");
+  MipClusterOutputs shared{};  // the fields the two structs share, for the checks and the launches they share
+  shared.struct_size = sizeof(MipClusterOutputs);
+  shared.flags = out->flags;
+  shared.cluster_cmds = out->cluster_entries;
+  shared.cmd_capacity = out->entry_capacity;
+  shared.work_capacity = out->work_capacity;
+  shared.cmd_count = out->entry_count;
+  shared.stats = out->stats;
+  return cull_clusters(ctx, frame, visible_bitmap, policy, occ, &shared, nullptr, false, nullptr, cone, cone != nullptr, out);
 }
 
 uint64_t mip_cluster_record_bytes(uint64_t work_items) { return mip::cluster_record_bytes(work_items); }

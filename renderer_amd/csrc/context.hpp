@@ -152,6 +152,11 @@ struct MipContext {
     uint32_t* d_word_total = nullptr;   // per survive word: the surviving triangles of its 64 items
     uint32_t* d_tile_triangles = nullptr;  // per item tile: surviving triangles (then their prefix), behind them the tested ones
     size_t triangle_words_cap = 0, item_prefix_cap = 0, word_total_cap = 0, tile_triangles_cap = 0;
+    // mip_list_clusters (cluster_list_plan.hpp): 8 bytes per 64 work items of the call's bound on top
+    uint32_t* d_word_member = nullptr;  // per survive word: the member of its first work item
+    uint32_t* d_word_rank = nullptr;    // per survive word: the survivors of its list tile in front of it
+    uint32_t* d_list_tiles = nullptr;   // per list tile: survivors, then their prefix
+    size_t word_member_cap = 0, word_rank_cap = 0, list_tiles_cap = 0;
   };
   std::vector<ClusterScratch> cluster_scratch;
   // mip_cull_clusters_views (cluster_views_plan.hpp): its own scratch on the first stream, as view_batch is — no frame slot's

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterListOutputs, MipClusterOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
                    MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
@@ -26,6 +26,14 @@ DRAW_CMD_DTYPE = np.dtype(
         ("firstIndex", "<u4"),
         ("vertexOffset", "<i4"),
         ("firstInstance", "<u4"),
+    ]
+)
+CLUSTER_ENTRY_DTYPE = np.dtype(  # MipClusterEntry: one entry of list_clusters' list
+    [
+        ("instance", "<u4"),
+        ("first_index", "<u4"),
+        ("vertex_offset", "<i4"),
+        ("index_count", "<u4"),
     ]
 )
 SHARD_HEADER_BYTES = 32
@@ -151,6 +159,22 @@ def make_cluster_outputs(cluster_cmds, cmd_capacity, cmd_count, stats=0, work_ca
     o.cmd_capacity = int(cmd_capacity)
     o.work_capacity = int(work_capacity)
     o.cmd_count = cmd_count or None
+    o.stats = stats or None
+    return o
+
+
+def make_cluster_list_outputs(cluster_entries, entry_capacity, entry_count, draw_args=0, stats=0, work_capacity=0, async_=False):
+    """A MipClusterListOutputs for list_clusters: device pointers to room for entry_capacity 16-byte entries (CLUSTER_ENTRY_DTYPE,
+    16-byte aligned), to the count, (optional) to the four words of the one VkDrawIndirectCommand {192, entry_count, 0, 0} and
+    (optional) to the three stats words {survivors, W, members}; work_capacity as in make_cluster_outputs."""
+    o = MipClusterListOutputs()
+    o.struct_size = C.sizeof(MipClusterListOutputs)
+    o.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+    o.cluster_entries = cluster_entries or None
+    o.entry_capacity = int(entry_capacity)
+    o.work_capacity = int(work_capacity)
+    o.entry_count = entry_count or None
+    o.draw_args = draw_args or None
     o.stats = stats or None
     return o
 
@@ -766,6 +790,16 @@ class InstancePipeline:
         self._check(self._lib.mip_cull_cluster_triangles_cone(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                               C.addressof(occlusion) if occlusion is not None else None,
                                                               C.addressof(cone) if cone is not None else None, C.addressof(outputs)))
+
+    # -- the visible-cluster list (extension) --
+    def list_clusters(self, frame, visible_bitmap_ptr, policy, outputs, occlusion=None, cone=None):
+        """mip_list_clusters: cull_clusters (or, with `cone`, cull_clusters_cone) with a flat list in the commands' place: one
+        16-byte entry per surviving cluster, in (instance, cluster) order, and the arguments of the ONE vkCmdDrawIndirect that
+        draws them, into `outputs` (make_cluster_list_outputs). The list is the cluster-by-cluster expansion of what
+        cull_clusters / cull_clusters_cone write for the same arguments."""
+        self._check(self._lib.mip_list_clusters(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                C.addressof(occlusion) if occlusion is not None else None,
+                                                C.addressof(cone) if cone is not None else None, C.addressof(outputs)))
 
     # -- diagnostics --
     def timings(self):
