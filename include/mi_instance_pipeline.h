@@ -1105,7 +1105,8 @@ int32_t mip_cull_clusters_views(MipContext* ctx, const MipFrame* frames, const u
  *   if (gl_VertexIndex < e.index_count) { v = vertices[indices[e.first_index + gl_VertexIndex] + e.vertex_offset];
  *                                         model = models[e.instance - first_instance_base]; ... }   // (the subtraction wraps as the sum did)
  *   else gl_Position = vec4(0);   // a degenerate vertex: the triangles of a short last cluster's tail have no area
- * OUT OF SCOPE: the two-phase record (mip_cull_clusters_phase); several views (mip_cull_clusters_views); the per-triangle test
+ * OUT OF SCOPE: the two-phase record (mip_cull_clusters_phase); several views in THIS call (mip_list_clusters_views below;
+ * commands per view: mip_cull_clusters_views); the per-triangle test
  * (mip_cull_cluster_triangles); shards, skinned instances, mip_run_many and recorded graphs. */
 typedef struct MipClusterEntry {
   uint32_t instance;         /* first_instance_base + i (wraps as firstInstance does) */
@@ -1128,11 +1129,66 @@ int32_t mip_list_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t
                           const MipOcclusion* occ /* or NULL */, const MipClusterCone* cone /* or NULL */,
                           const MipClusterListOutputs* out);
 
+/* ---- Extension: visible-cluster lists for several views in one call --------------------------------------------------------
+ * mip_cull_clusters_views with mip_list_clusters' flat list in the commands' place: for n_views views — cascades, cube faces,
+ * stereo eyes — ONE call forms the level, the work items and the world box of every (instance, cluster) once, tests them
+ * against every view's planes, and writes one list of 16-byte MipClusterEntry and one VkDrawIndirectCommand per view. NOT a
+ * reference behaviour; checked against this repository's restatement (tests/cluster_views_list_restatement.py), byte for byte.
+ * Every entry point above is unchanged.
+ *
+ * VIEWS, ONE LOD FOR ALL VIEWS (frames[0].cam_pos), MEMBERS, WORK ITEMS, W and SURVIVES_v are the words of
+ * mip_cull_clusters_views, unchanged. There is no pyramid and no cone.
+ * ENTRIES: view v's entries are [v * entry_stride, v * entry_stride + entry_counts[v]) of cluster_entries: one
+ * MipClusterEntry per work item with SURVIVES_v, in (i, c) order. The fields are mip_list_clusters' with instance =
+ * frames[v].first_instance_base + i (wraps as firstInstance does). entry_counts[v] = min(survivors_v, entry_stride); entries
+ * at or behind a view's count are never touched.
+ * draw_args (optional, n_views x 4 words): draw_args[4v .. 4v+3] = VkDrawIndirectCommand {vertexCount = 192, instanceCount =
+ * entry_counts[v], firstVertex = 0, firstInstance = v * entry_stride}. firstInstance is the view's first entry: Vulkan's
+ * gl_InstanceIndex includes firstInstance, so every view's shader reads entries[gl_InstanceIndex] from the one buffer.
+ * stats (optional, 2 + n_views words): {W, members, survivors_0, survivors_1, ...}.
+ * THE CONSUMER: mip_list_clusters' shader, with one vkCmdDrawIndirect(cmd, draw_args, 16 * v, 1, 16) per view into its own
+ * target, or one call with drawCount = n_views in a layered pass with gl_DrawID as the view.
+ * THE TWO EQUIVALENCES: let f_v = frames[v] with cam_pos replaced by frames[0].cam_pos. (a) View v's entries, entry_counts[v]
+ * and survivors_v are byte for byte what mip_list_clusters(ctx, &f_v, visible_bitmaps[v] (a full bitmap where the entry is
+ * NULL), policy, NULL, NULL, {entry_capacity = entry_stride}) writes, whenever both calls run. (b) View v's entries are the
+ * cluster-by-cluster expansion of view v's command range of mip_cull_clusters_views with the same arguments.
+ * ENTRY OVERFLOW (some survivors_v > entry_stride): that view keeps its first entry_stride entries exactly as with room,
+ * entry_counts[v] = draw_args[4v+1] = entry_stride, the other views are complete, stats are true, and the status is
+ * MIP_ERR_CAPACITY.
+ * WORK OVERFLOW (W > work_capacity — 0 = the library's own bound, N x the largest C of the table — or W >= 2^32): every count
+ * is 0, draw_args of view v = {192, 0, 0, v * entry_stride}, stats = {W mod 2^32, members, 0, ...}, no entry is written,
+ * MIP_ERR_CAPACITY; the context stays usable.
+ * WHO REPORTS is mip_cull_clusters_views' rule, on that call's own pair of status words: both several-view calls share the
+ * pair. Neither is ever charged to a frame slot's cluster call, nor the other way round.
+ * N = 0 writes n_views zero counts, {192, 0, 0, v * entry_stride} per view and zero stats.
+ * REFUSED, nothing written, MIP_ERR_INVALID_ARGUMENT: everything mip_cull_clusters_views refuses (cluster_entries,
+ * entry_stride and entry_counts in cluster_cmds', cmd_stride's and cmd_counts' places; draw_args 4-byte aligned like the other
+ * words); cluster_entries not 16-byte aligned; n_views x entry_stride >= 2^32 (the last view's firstInstance would not fit).
+ * MIP_ERR_NOT_READY as for that call.
+ * ORDERING: enqueued on the context's first stream, as mip_run_views and mip_cull_clusters_views are. Scratch is the
+ * several-view call's own, grown by this call: on top of mip_cull_clusters_views' planes, (1 + n_views) x 4 bytes per 64 work
+ * items of the bound. Both several-view calls run on the one stream, so sharing the scratch is ordered.
+ * OUT OF SCOPE: a pyramid per view; cones; the two phases; the per-triangle stream; one list packed tightly over all views;
+ * shards; skinned instances; mip_run_many and recorded graphs. */
+typedef struct MipClusterViewListOutputs {
+  uint32_t struct_size;      /* = sizeof(MipClusterViewListOutputs) */
+  uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
+  void* cluster_entries;     /* DEVICE, 16-byte aligned: n_views x entry_stride MipClusterEntry */
+  uint32_t entry_stride;     /* entries reserved per view */
+  uint32_t work_capacity;    /* bound on W of the union of the views' members; 0 = N x the largest C */
+  uint32_t* entry_counts;    /* DEVICE: n_views words: min(survivors_v, entry_stride) */
+  uint32_t* draw_args;       /* DEVICE, optional: n_views x 4 words */
+  uint32_t* stats;           /* DEVICE, optional: 2 + n_views words: W, members, survivors_0 ... */
+} MipClusterViewListOutputs; /* 48 B */
+
+int32_t mip_list_clusters_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps,
+                                uint32_t n_views, const MipLodPolicy* policy, const MipClusterViewListOutputs* out);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every
  * frames_in_flight frames): it is where their errors surface. The MIP_ERR_CAPACITY of an asynchronous
- * mip_cull_clusters, mip_list_clusters or mip_cull_clusters_views (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase) is returned
+ * mip_cull_clusters, mip_list_clusters, mip_cull_clusters_views or mip_list_clusters_views (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase) is returned
  * when there is no other error to return; otherwise by the mip_wait after. */
 int32_t mip_wait(MipContext* ctx);
 

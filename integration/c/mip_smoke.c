@@ -124,6 +124,20 @@ int main(void) {
   cluster_views.cmd_counts = &count;
   ok = ok && mip_cull_clusters_views(ctx, &frame, view_bitmaps, 1, &policy, &cluster_views) == MIP_ERR_INVALID_ARGUMENT &&
        mip_instance_count(ctx) == N;
+  /* The visible-cluster lists of several views (extension): the same place in a frame, with
+   *     MipClusterViewListOutputs lv = { sizeof lv, MIP_OUT_DEVICE | MIP_OUT_ASYNC, entries, entry_stride, 0, entry_counts, draw_args, NULL };
+   *     mip_list_clusters_views(ctx, frames, bitmaps_dev, n_views, &policy, &lv);
+   * and per view vkCmdDrawIndirect(cb, draw_args, 16 * v, 1, 16): firstInstance = v * entry_stride is the view's first entry.
+   * Here: the struct and the entry point link from C, and host pointers are refused without harming the context. */
+  MipClusterViewListOutputs list_views;
+  memset(&list_views, 0, sizeof list_views);
+  list_views.struct_size = sizeof list_views;
+  list_views.flags = MIP_OUT_HOST;
+  list_views.cluster_entries = cmds;
+  list_views.entry_stride = 1;
+  list_views.entry_counts = &count;
+  ok = ok && mip_list_clusters_views(ctx, &frame, view_bitmaps, 1, &policy, &list_views) == MIP_ERR_INVALID_ARGUMENT &&
+       mip_instance_count(ctx) == N;
   printf("C_SMOKE %s instances=%d visible=%u commands=%u index_total=%u checksum=%08x\n", ok ? "OK" : "BAD", N, visible, count,
          index_total, sum);
   mip_destroy(ctx);

@@ -255,6 +255,20 @@ pub struct MipClusterListOutputs {
     pub stats: *mut u32,
 }
 
+/// Outputs of mip_list_clusters_views: one list of surviving clusters and one VkDrawIndirectCommand per view, device pointers;
+/// view v's entries start at entry v x entry_stride, which is also firstInstance of its draw (see the header).
+#[repr(C)]
+pub struct MipClusterViewListOutputs {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub cluster_entries: *mut c_void,
+    pub entry_stride: u32,
+    pub work_capacity: u32,
+    pub entry_counts: *mut u32,
+    pub draw_args: *mut u32,
+    pub stats: *mut u32,
+}
+
 /// Per-frame parameters of the occlusion test (mip_cull_clusters reads pyramid, width, height and pv).
 #[repr(C)]
 pub struct MipOcclusion {
@@ -371,6 +385,10 @@ extern "C" {
     /// place, and the arguments of the one indirect draw over the list.
     pub fn mip_list_clusters(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
                              occ: *const MipOcclusion, cone: *const MipClusterCone, out: *const MipClusterListOutputs) -> i32;
+    /// mip_cull_clusters_views with mip_list_clusters' entries in the commands' place: one list and one indirect draw per view,
+    /// the located work item and three of the four entry fields shared by all views; on the first stream.
+    pub fn mip_list_clusters_views(ctx: *mut MipContext, frames: *const MipFrame, visible_bitmaps: *const *const u32,
+                                   n_views: u32, policy: *const MipLodPolicy, out: *const MipClusterViewListOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -394,6 +412,7 @@ const _: [u8; 56] = [0; std::mem::size_of::<MipClusterTriangleOutputs>()];
 const _: [u8; 24] = [0; std::mem::size_of::<MipClusterCone>()];
 const _: [u8; 16] = [0; std::mem::size_of::<MipClusterEntry>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipClusterListOutputs>()];
+const _: [u8; 48] = [0; std::mem::size_of::<MipClusterViewListOutputs>()];
 const _: [u8; 104] = [0; std::mem::size_of::<MipOcclusion>()];
 
 impl Pipeline {

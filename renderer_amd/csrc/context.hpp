@@ -171,9 +171,14 @@ struct MipContext {
     uint32_t* d_tile_heads = nullptr;   // n_views rows of head tiles
     uint32_t* d_tile_survivors = nullptr;
     size_t words_cap = 0, head_rows_cap = 0, survivor_rows_cap = 0;
+    // mip_list_clusters_views (cluster_views_list_plan.hpp), grown by that call: both several-view calls run on `stream`
+    uint32_t* d_word_member = nullptr;  // one plane: per 64 work items, the member of the word's first item
+    uint32_t* d_word_rank = nullptr;    // n_views planes
+    uint32_t* d_list_tiles = nullptr;   // n_views rows of list tiles
+    size_t word_member_cap = 0, word_rank_cap = 0, list_tiles_cap = 0;
   };
   ClusterViewScratch cluster_views;
-  uint32_t* h_cluster_views_status = nullptr;  // pinned, device-visible, two words: the code an asynchronous / a synchronous mip_cull_clusters_views raised
+  uint32_t* h_cluster_views_status = nullptr;  // pinned, device-visible, two words: the code an asynchronous / a synchronous mip_cull_clusters_views or mip_list_clusters_views raised
   uint32_t* h_cluster_status = nullptr;  // pinned, device-visible, two words per frame slot: the code an asynchronous / a synchronous cull of the slot raised
   hipEvent_t cluster_pyramid_ready = nullptr;  // orders a cull behind a pyramid built on another slot's stream
   hipEvent_t cluster_record_written = nullptr;  // behind the last FIRST call of mip_cull_clusters_phase: its SECOND call waits for it, on whichever slot's stream

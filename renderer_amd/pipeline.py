@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterListOutputs, MipClusterOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterListOutputs, MipClusterOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipClusterViewListOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
                    MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
@@ -191,6 +191,23 @@ def make_cluster_view_outputs(cluster_cmds, cmd_stride, cmd_counts, stats=0, wor
     o.cmd_stride = int(cmd_stride)
     o.work_capacity = int(work_capacity)
     o.cmd_counts = cmd_counts or None
+    o.stats = stats or None
+    return o
+
+
+def make_cluster_view_list_outputs(cluster_entries, entry_stride, entry_counts, draw_args=0, stats=0, work_capacity=0, async_=False):
+    """A MipClusterViewListOutputs for list_clusters_views: device pointers to room for n_views x entry_stride 16-byte entries
+    (CLUSTER_ENTRY_DTYPE, 16-byte aligned; view v's start at entry v x entry_stride), to the n_views counts, (optional) to the
+    n_views x 4 words of one VkDrawIndirectCommand {192, entry_counts[v], 0, v x entry_stride} per view and (optional) to the
+    2 + n_views stats words {W, members, then the surviving clusters per view}; work_capacity as in make_cluster_view_outputs."""
+    o = MipClusterViewListOutputs()
+    o.struct_size = C.sizeof(MipClusterViewListOutputs)
+    o.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+    o.cluster_entries = cluster_entries or None
+    o.entry_stride = int(entry_stride)
+    o.work_capacity = int(work_capacity)
+    o.entry_counts = entry_counts or None
+    o.draw_args = draw_args or None
     o.stats = stats or None
     return o
 
@@ -800,6 +817,22 @@ class InstancePipeline:
         self._check(self._lib.mip_list_clusters(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                 C.addressof(occlusion) if occlusion is not None else None,
                                                 C.addressof(cone) if cone is not None else None, C.addressof(outputs)))
+
+    def list_clusters_views(self, frames, visible_bitmap_ptrs, policy, outputs):
+        """mip_list_clusters_views: cull_clusters_views with list_clusters' flat list in the commands' place, one list and one
+        indirect draw per view. frames and visible_bitmap_ptrs are cull_clusters_views' (one level for ALL views, from
+        frames[0]'s cam_pos). View v's entries are [v * entry_stride, v * entry_stride + entry_counts[v]) of `outputs`
+        (make_cluster_view_list_outputs), and draw_args[4 v ..] = {192, entry_counts[v], 0, v * entry_stride}. Enqueued on the
+        context's first stream, behind a run_views. MIP_ERR_CAPACITY (from wait() for an asynchronous call) when a view's
+        survivors do not fit entry_stride or the work items exceed work_capacity."""
+        k = len(frames)
+        if len(visible_bitmap_ptrs) != k:
+            raise ValueError("one bitmap pointer (or None) per frame")
+        fr = (MipFrame * max(k, 1))()
+        for v in range(k):
+            C.memmove(C.addressof(fr[v]), C.addressof(frames[v]), C.sizeof(MipFrame))
+        bm = (C.c_void_p * max(k, 1))(*[int(b) if b else None for b in visible_bitmap_ptrs])
+        self._check(self._lib.mip_list_clusters_views(self._ctx, C.addressof(fr), C.addressof(bm), k, C.addressof(policy), C.addressof(outputs)))
 
     # -- diagnostics --
     def timings(self):
