@@ -882,7 +882,8 @@ int32_t mip_cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t
  * THE FRAME that composes instance phases and cluster phases: (1) mip_run_occluded with last frame's pyramid, then FIRST over
  * its bitmap; (2) draw, rebuild the pyramid; (3) mip_run_occluded with the inverted candidates, then plain mip_cull_clusters
  * over ITS bitmap under the new pyramid (instances phase 1 never saw as visible have no record); (4) SECOND over phase 1's
- * bitmap. */
+ * bitmap.
+ * OUT OF SCOPE here: the flat list of the visible clusters in two phases (mip_list_clusters_phase below). */
 #define MIP_CLUSTER_PHASE_FIRST  1u
 #define MIP_CLUSTER_PHASE_SECOND 2u
 typedef struct MipClusterRecord {
@@ -1105,7 +1106,7 @@ int32_t mip_cull_clusters_views(MipContext* ctx, const MipFrame* frames, const u
  *   if (gl_VertexIndex < e.index_count) { v = vertices[indices[e.first_index + gl_VertexIndex] + e.vertex_offset];
  *                                         model = models[e.instance - first_instance_base]; ... }   // (the subtraction wraps as the sum did)
  *   else gl_Position = vec4(0);   // a degenerate vertex: the triangles of a short last cluster's tail have no area
- * OUT OF SCOPE: the two-phase record (mip_cull_clusters_phase); several views in THIS call (mip_list_clusters_views below;
+ * OUT OF SCOPE: the two-phase record and an entry base (mip_list_clusters_phase below); several views in THIS call (mip_list_clusters_views below;
  * commands per view: mip_cull_clusters_views); the per-triangle test
  * (mip_cull_cluster_triangles); shards, skinned instances, mip_run_many and recorded graphs. */
 typedef struct MipClusterEntry {
@@ -1184,11 +1185,73 @@ typedef struct MipClusterViewListOutputs {
 int32_t mip_list_clusters_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps,
                                 uint32_t n_views, const MipLodPolicy* policy, const MipClusterViewListOutputs* out);
 
+/* ---- Extension: the visible-cluster list in two phases ---------------------------------------------------------------------
+ * mip_cull_clusters_phase with mip_list_clusters' flat list in the commands' place: FIRST writes one MipClusterEntry per work
+ * item that survives under last frame's pyramid and records the items hidden by occlusion alone; SECOND, after the pyramid is
+ * rebuilt, writes one entry per recorded item that is visible now — and can append them behind FIRST's entries in the same
+ * buffer without the host reading FIRST's count. NOT a reference behaviour; checked against this repository's restatement
+ * (tests/cluster_list_phase_restatement.py) only. Every entry point above is unchanged.
+ *
+ * BORROWED TERMS: MEMBERS, WORK ITEMS, W, SURVIVES, SURVIVES2, THE RECORD (its header, its words, mip_cluster_record_bytes) and
+ * the folding of record_bytes into the bound on W are mip_cull_clusters_phase's, unchanged. ENTRIES and their four fields are
+ * mip_list_clusters'. frame, visible_bitmap, policy, occ (required) and rec are mip_cull_clusters_phase's.
+ * FIRST (rec->phase = MIP_CLUSTER_PHASE_FIRST): one entry per work item with SURVIVES (frame->planes and the pyramid of occ),
+ * in (i, c) order. The record is byte for byte what mip_cull_clusters_phase FIRST writes for the same ctx, frame,
+ * visible_bitmap, policy, occ and rec, header included. A record written by either call is accepted by SECOND of either call.
+ * SECOND (rec->phase = MIP_CLUSTER_PHASE_SECOND): one entry per work item with SURVIVES2 (its record bit is set AND its world
+ * box is not occluded under occ, the new pyramid), in (i, c) order. frame->planes is NOT read. The record is never modified.
+ * ENTRY BASE: let b = *entry_base, or 0 when entry_base is NULL. b is read ON THE DEVICE when the call's kernels run: behind
+ * everything enqueued earlier on that stream, and for SECOND behind the FIRST call (ORDERING). entry_base may therefore be the
+ * FIRST call's entry_count. It must not be THIS call's entry_count and must not lie inside this call's draw_args or stats:
+ * those are refused. room = entry_capacity - min(b, entry_capacity): entry_capacity counts the BUFFER's entries from entry 0.
+ * The entries go to [b, b + entry_count) of cluster_entries, entry_count = min(survivors, room), and nothing outside that
+ * range is touched.
+ * draw_args (optional, 4 words) = VkDrawIndirectCommand {192, entry_count, 0, b}: firstInstance is the list's first entry, as
+ * in mip_list_clusters_views, so the shader reads entries[gl_InstanceIndex]. THE CONSUMER is mip_list_clusters' otherwise.
+ * stats (optional, 4 words) = {survivors, W, members, candidates}; candidates is the record header's word: written in FIRST,
+ * read in SECOND.
+ * ENTRY OVERFLOW (survivors > room): the first `room` entries are written exactly as they would be with room, entry_count =
+ * draw_args[1] = room, stats holds the true values, MIP_ERR_CAPACITY. In FIRST the record stays complete and valid.
+ * WORK OVERFLOW (as mip_cull_clusters_phase: W > work_capacity or the library's own bound, W >= 2^32, or record_bytes <
+ * mip_cluster_record_bytes(W)): MIP_ERR_CAPACITY, entry_count = 0, draw_args = {192, 0, 0, b}, stats = {0, W mod 2^32,
+ * members, 0}; no entry is written; FIRST's header becomes {0xFFFFFFFF, 0, 0, 0} and no record word is defined.
+ * NOT THIS CALL'S RECORD (SECOND; the header's W or members differs from the call's): MIP_ERR_DEVICE, entry_count = 0,
+ * draw_args = {192, 0, 0, b}, stats = {0, W, members, 0} (the call's own); nothing else is written.
+ * N = 0: a zero count, {192, 0, 0, b} and zero stats; FIRST writes the header {0, 0, 0, 0}.
+ * WHO REPORTS follows mip_cull_clusters: the same per-slot status words, the same mip_wait route (MIP_ERR_DEVICE before
+ * MIP_ERR_CAPACITY when asynchronous calls raised both). The context stays usable.
+ * REFUSED, nothing written, MIP_ERR_INVALID_ARGUMENT: everything mip_list_clusters (cone == NULL) and mip_cull_clusters_phase
+ * refuse (a wrong MipClusterPhaseListOutputs.struct_size in the outputs' place); an entry_base that is this call's entry_count
+ * or lies inside its draw_args or stats; an entry_base that is not 4-byte aligned. MIP_ERR_NOT_READY as for those calls.
+ * ORDERING: as mip_cull_clusters_phase: both calls go on the stream of the frame issued last; FIRST records the context's
+ * record event, SECOND waits for it on the device, so with two frames in flight no host wait is needed between them. Scratch
+ * is mip_list_clusters' per frame slot plus one word per list tile.
+ * THE FRAME, mip_cull_clusters_phase's four steps with lists: (1) mip_run_occluded with last frame's pyramid, then FIRST over
+ * its bitmap with entry_base = NULL; (2) draw FIRST's list, rebuild the pyramid; (3) mip_run_occluded with the inverted
+ * candidates, then plain mip_list_clusters over ITS bitmap under the new pyramid into a buffer of its own; (4) SECOND over
+ * phase 1's bitmap with entry_base = FIRST's entry_count into FIRST's buffer: one more indirect draw from SECOND's draw_args.
+ * OUT OF SCOPE: cones, several views, shards, skinned instances, the per-triangle stream, mip_run_many and recorded graphs, and
+ * an entry_base for mip_list_clusters. */
+typedef struct MipClusterPhaseListOutputs {
+  uint32_t struct_size;       /* = sizeof(MipClusterPhaseListOutputs) */
+  uint32_t flags;             /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
+  void* cluster_entries;      /* DEVICE, 16-byte aligned: room for entry_capacity MipClusterEntry */
+  uint32_t entry_capacity;    /* entries the BUFFER holds, counted from entry 0 */
+  uint32_t work_capacity;     /* as MipClusterListOutputs */
+  uint32_t* entry_count;      /* DEVICE: entries this call wrote = min(survivors, room) */
+  uint32_t* draw_args;        /* DEVICE, optional, 4 words: VkDrawIndirectCommand {192, entry_count, 0, b} */
+  uint32_t* stats;            /* DEVICE, optional, 4 words: survivors, W, members, candidates */
+  const uint32_t* entry_base; /* DEVICE, optional: the entry this call's list starts at; NULL = 0 */
+} MipClusterPhaseListOutputs; /* 56 B */
+
+int32_t mip_list_clusters_phase(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                const MipOcclusion* occ, const MipClusterPhaseListOutputs* out, const MipClusterRecord* rec);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every
  * frames_in_flight frames): it is where their errors surface. The MIP_ERR_CAPACITY of an asynchronous
- * mip_cull_clusters, mip_list_clusters, mip_cull_clusters_views or mip_list_clusters_views (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase) is returned
+ * mip_cull_clusters, mip_list_clusters, mip_list_clusters_phase, mip_cull_clusters_views or mip_list_clusters_views (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase or mip_list_clusters_phase) is returned
  * when there is no other error to return; otherwise by the mip_wait after. */
 int32_t mip_wait(MipContext* ctx);
 

@@ -269,6 +269,21 @@ pub struct MipClusterViewListOutputs {
     pub stats: *mut u32,
 }
 
+/// Outputs of mip_list_clusters_phase: mip_list_clusters' list in two phases. The list starts at entry *entry_base, read on
+/// the device (null: 0) — SECOND appends behind FIRST with entry_base = FIRST's entry_count; stats has four words (see the header).
+#[repr(C)]
+pub struct MipClusterPhaseListOutputs {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub cluster_entries: *mut c_void,
+    pub entry_capacity: u32,
+    pub work_capacity: u32,
+    pub entry_count: *mut u32,
+    pub draw_args: *mut u32,
+    pub stats: *mut u32,
+    pub entry_base: *const u32,
+}
+
 /// Per-frame parameters of the occlusion test (mip_cull_clusters reads pyramid, width, height and pv).
 #[repr(C)]
 pub struct MipOcclusion {
@@ -389,6 +404,10 @@ extern "C" {
     /// the located work item and three of the four entry fields shared by all views; on the first stream.
     pub fn mip_list_clusters_views(ctx: *mut MipContext, frames: *const MipFrame, visible_bitmaps: *const *const u32,
                                    n_views: u32, policy: *const MipLodPolicy, out: *const MipClusterViewListOutputs) -> i32;
+    /// mip_cull_clusters_phase with mip_list_clusters' entries in the commands' place: FIRST lists the survivors and writes the
+    /// record, SECOND lists the recorded clusters visible under the new pyramid, from entry *out.entry_base on.
+    pub fn mip_list_clusters_phase(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
+                                   occ: *const MipOcclusion, out: *const MipClusterPhaseListOutputs, rec: *const MipClusterRecord) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -413,6 +432,7 @@ const _: [u8; 24] = [0; std::mem::size_of::<MipClusterCone>()];
 const _: [u8; 16] = [0; std::mem::size_of::<MipClusterEntry>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipClusterListOutputs>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipClusterViewListOutputs>()];
+const _: [u8; 56] = [0; std::mem::size_of::<MipClusterPhaseListOutputs>()];
 const _: [u8; 104] = [0; std::mem::size_of::<MipOcclusion>()];
 
 impl Pipeline {

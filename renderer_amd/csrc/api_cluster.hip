@@ -14,6 +14,8 @@
 // with a scratch and a pair of status words of its own (cluster_views_kernel.hpp, cluster_views_plan.hpp).
 // mip_list_clusters_views is that call's front with the list's entries behind it, one list and one indirect draw per view, on the
 // same stream, scratch and status words (cluster_views_list_kernel.hpp, cluster_views_list_plan.hpp: three new kernels).
+// mip_list_clusters_phase is mip_cull_clusters_phase with the list's entries in the commands' place, the list started at an entry
+// base read on the device (cluster_list_phase_kernel.hpp, cluster_list_phase_plan.hpp: the front and the list tail of its own).
 // cluster_plan.hpp, cluster_triangle_plan.hpp and cluster_cone_plan.hpp hold the arithmetic and the launch plans; the kernels
 // (cluster_kernel.hpp, cluster_triangle_kernel.hpp, cluster_cone_kernel.hpp) are instantiated here and only here.
 #include "context.hpp"
@@ -23,6 +25,7 @@
 #include "cluster_views_kernel.hpp"
 #include "cluster_list_kernel.hpp"
 #include "cluster_views_list_kernel.hpp"
+#include "cluster_list_phase_kernel.hpp"
 
 static_assert(sizeof(MipClusterViewOutputs) == 40, "MipClusterViewOutputs is part of the ABI");
 static_assert(sizeof(MipClusterOutputs) == 40, "MipClusterOutputs is part of the ABI");
@@ -32,6 +35,7 @@ static_assert(sizeof(MipClusterCone) == 24, "MipClusterCone is part of the ABI")
 static_assert(sizeof(MipClusterEntry) == 16 && sizeof(MipClusterEntry) == sizeof(uint4), "MipClusterEntry is part of the ABI: one 16-byte store");
 static_assert(sizeof(MipClusterListOutputs) == 48, "MipClusterListOutputs is part of the ABI");
 static_assert(sizeof(MipClusterViewListOutputs) == 48, "MipClusterViewListOutputs is part of the ABI");
+static_assert(sizeof(MipClusterPhaseListOutputs) == 56, "MipClusterPhaseListOutputs is part of the ABI");
 static_assert(sizeof(mip::ClusterConeEntry) == 2 * sizeof(float4), "a cone is the two 16-byte words the kernels load");
 static_assert(mip::kClusterFirst == MIP_CLUSTER_PHASE_FIRST && mip::kClusterSecond == MIP_CLUSTER_PHASE_SECOND, "cluster_kernel.hpp restates the header");
 static_assert(MIP_CLUSTER_TRIANGLES == mip::kClusterTriangles, "cluster_plan.hpp restates the header");
@@ -44,7 +48,7 @@ namespace {
 // that fitted is never blamed for another's overflow, and no overflow is reported twice. A word holds a code: the bits
 // kClusterStatusCapacity (an overflow) and kClusterStatusDevice (a SECOND call met a record that is not its own).
 constexpr uint32_t kStatusWords = 2 * MIP_MAX_FRAMES_IN_FLIGHT;
-constexpr const char* kNotItsRecord = "mip_cull_clusters_phase: the record's header names another W or another member count than this SECOND call's: it is not the record of the FIRST call over these members (a zero count is written, stats holds the call's W and members)";
+constexpr const char* kNotItsRecord = "mip_cull_clusters_phase / mip_list_clusters_phase: the record's header names another W or another member count than this SECOND call's: it is not the record of the FIRST call over these members (a zero count is written, stats holds the call's W and members)";
 
 // Every level of every mesh against the host copies of the geometry, as check_geometry (api_frame.hip) checks LODs 0 and 1:
 // the level's range inside the uploaded indices, every vertex its triangles name inside the uploaded vertices.
@@ -707,6 +711,199 @@ int32_t list_clusters_views(MipContext* ctx, const MipFrame* frames, const uint3
   return MIP_OK;
 }
 
+// ---- mip_list_clusters_phase ----
+
+// What mip_list_clusters_phase takes on top of the list's scratch (cluster_list_phase_plan.hpp).
+int32_t ensure_list_phase_scratch(MipContext* ctx, MipContext::ClusterScratch& cs, const mip::ClusterListPhasePlan& plan) {
+  if (!cs.d_list_phase_scalars) MIP_HIP(ctx, hipMalloc(&cs.d_list_phase_scalars, plan.scalar_words * 4));
+  if (plan.first)
+    if (int32_t rc = grow(ctx, &cs.d_list_candidates, &cs.list_candidates_cap, (size_t)plan.candidate_rows, 4)) return rc;
+  return MIP_OK;
+}
+
+// Whether the word at `p` lies inside the `words` words at `at` (either may be null)
+bool inside_words(const uint32_t* p, const uint32_t* at, uint32_t words) {
+  return p && at && (uintptr_t)p >= (uintptr_t)at && (uintptr_t)p < (uintptr_t)at + 4u * (uintptr_t)words;
+}
+
+// Every check first (a refused call writes nothing), then the eight launches of the plan on the stream of the frame issued last:
+// mip_cull_clusters_phase's front with the list's tail. The argument block is filled here as cull_clusters fills it —
+// duplicated, so that call stays as it is.
+int32_t list_clusters_phase(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy, const MipOcclusion* occ,
+                            const MipClusterPhaseListOutputs* out, const MipClusterRecord* rec) {
+  if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
+  if (out->struct_size != sizeof(MipClusterPhaseListOutputs))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterPhaseListOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipClusterPhaseListOutputs));
+  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipClusterPhaseListOutputs flags 0x%x", out->flags);
+  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_list_clusters_phase needs MIP_OUT_DEVICE outputs");
+  if (!out->cluster_entries || !out->entry_count) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cluster_entries/entry_count is NULL");
+  if ((uintptr_t)out->cluster_entries % 16u != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cluster_entries is not 16-byte aligned");
+  if ((uintptr_t)out->entry_count % 4u != 0u || (uintptr_t)out->draw_args % 4u != 0u || (uintptr_t)out->stats % 4u != 0u || (uintptr_t)out->entry_base % 4u != 0u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "entry_count, draw_args, stats or entry_base is not 4-byte aligned");
+  if (out->entry_base && (out->entry_base == out->entry_count || inside_words(out->entry_base, out->draw_args, 4) || inside_words(out->entry_base, out->stats, 4)))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "entry_base is this call's entry_count or lies inside its draw_args or stats");
+  if (!occ) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_list_clusters_phase needs a MipOcclusion: both phases test against a pyramid");
+  if (occ->struct_size != sizeof(MipOcclusion))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipOcclusion.struct_size %u != %zu", occ->struct_size, sizeof(MipOcclusion));
+  if (occ->width < 1u || occ->height < 1u || occ->width > MIP_MAX_DEPTH_EXTENT || occ->height > MIP_MAX_DEPTH_EXTENT)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "depth extent %ux%u outside 1..%u", occ->width, occ->height, (unsigned)MIP_MAX_DEPTH_EXTENT);
+  if (!occ->pyramid) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "pyramid is NULL");
+  if (occ->flags || occ->candidates || occ->occluded_bitmap)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_list_clusters_phase takes no MipOcclusion flags, candidates or occluded_bitmap");
+  if (!rec) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "rec is NULL");
+  if (rec->struct_size != sizeof(MipClusterRecord))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterRecord.struct_size %u != %zu", rec->struct_size, sizeof(MipClusterRecord));
+  if (rec->phase != MIP_CLUSTER_PHASE_FIRST && rec->phase != MIP_CLUSTER_PHASE_SECOND)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipClusterRecord.phase %u", rec->phase);
+  if (!rec->record || (uintptr_t)rec->record % 16u != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "record is NULL or not 16-byte aligned");
+  if (rec->record_bytes < mip::kClusterRecordHeaderBytes) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "record_bytes %llu < 16", (unsigned long long)rec->record_bytes);
+  const bool first = rec->phase == MIP_CLUSTER_PHASE_FIRST;
+  if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
+  if (!ctx->clusters.valid) return fail(ctx, MIP_ERR_NOT_READY, "no cluster table, or the mesh table / geometry changed since mip_build_clusters");
+  if (int32_t rc = bind_device(ctx)) return rc;
+
+  const uint32_t slot = ctx->last_slot;
+  hipStream_t stream = ctx->slots[slot].stream;
+  const bool async = (out->flags & MIP_OUT_ASYNC) != 0;
+  const uint32_t n = ctx->n;
+  // SECOND goes behind the FIRST call that wrote the record (and its entry_count, which may be this call's entry_base),
+  // whichever slot's stream that call ran on
+  if (!first && ctx->cluster_record_written) MIP_HIP(ctx, hipStreamWaitEvent(stream, ctx->cluster_record_written, 0));
+  if (n == 0) {  // nothing to test: a zero count, {192, 0, 0, b}, zero stats; FIRST: a zero header
+    MIP_HIP(ctx, hipMemsetAsync(out->entry_count, 0, 4, stream));
+    if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, 16, stream));
+    if (out->draw_args) {
+      MIP_HIP(ctx, hipMemsetAsync(out->draw_args, 0, 16, stream));
+      MIP_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out->draw_args), (int)mip::kClusterListDrawVertices, 1, stream));
+      if (out->entry_base) MIP_HIP(ctx, hipMemcpyAsync(out->draw_args + 3, out->entry_base, 4, hipMemcpyDeviceToDevice, stream));  // b, on the device
+    }
+    if (first) {
+      MIP_HIP(ctx, hipMemsetAsync(rec->record, 0, mip::kClusterRecordHeaderBytes, stream));
+      if (int32_t rc = record_written(ctx, stream)) return rc;
+    }
+    return finish(ctx, stream, async);
+  }
+  if (!ctx->h_cluster_status) {
+    MIP_HIP(ctx, hipHostMalloc(&ctx->h_cluster_status, kStatusWords * 4, hipHostMallocMapped));
+    std::memset(ctx->h_cluster_status, 0, kStatusWords * 4);
+  }
+  const MipContext::ClusterTable& table = ctx->clusters;
+  unsigned long long bound = mip::cluster_work_bound(n, table.max_clusters, out->work_capacity);
+  {  // a W the record has no words for is a work overflow
+    const unsigned long long room = mip::cluster_record_items(rec->record_bytes);
+    bound = room < bound ? room : bound;
+  }
+  const mip::ClusterListPhasePlan plan = mip::plan_cluster_list_phase(n, bound, first);
+  if (ctx->cluster_scratch.size() != ctx->slots.size()) ctx->cluster_scratch.resize(ctx->slots.size());
+  MipContext::ClusterScratch& cs = ctx->cluster_scratch[slot];
+  if (int32_t rc = ensure_scratch(ctx, cs, plan.front, false)) return rc;
+  if (int32_t rc = ensure_list_scratch(ctx, cs, plan.list)) return rc;
+  if (int32_t rc = ensure_list_phase_scratch(ctx, cs, plan)) return rc;
+  if (ctx->next_slot != slot) {
+    // a pyramid built for the next run sits on that slot's stream: this call goes behind what that stream holds now
+    if (!ctx->cluster_pyramid_ready) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_pyramid_ready, hipEventDisableTiming));
+    MIP_HIP(ctx, hipEventRecord(ctx->cluster_pyramid_ready, ctx->slots[ctx->next_slot].stream));
+    MIP_HIP(ctx, hipStreamWaitEvent(stream, ctx->cluster_pyramid_ready, 0));
+  }
+
+  mip::ClusterListPhaseArgs pa{};
+  mip::ClusterListArgs& la = pa.l;
+  mip::ClusterArgs& a = la.c;
+  a.lods.chain = ctx->d_mesh_chain;
+  a.lods.bucket_lod = ctx->d_bucket_lod;
+  std::memcpy(a.lods.switch_sq, policy->switch_sq, sizeof a.lods.switch_sq);
+  a.lods.pos = ctx->d_pos; a.lods.rot = ctx->d_rot; a.lods.scale = ctx->d_scale; a.lods.mesh_id = ctx->d_mesh_id;
+  a.lods.meshes = ctx->d_meshes; a.lods.mesh_draw = ctx->d_mesh_draw;
+  a.lods.bitmap = visible_bitmap;
+  a.lods.n = n;
+  a.lods.n_tiles = plan.front.instance_tiles;
+  a.lods.n_buckets = (uint32_t)ctx->lod_buckets;
+  a.lods.first_instance_base = frame->first_instance_base;
+  std::memcpy(a.lods.cam, frame->cam_pos, sizeof a.lods.cam);
+  a.cluster_base = table.d_cluster_base;
+  a.boxes = table.d_boxes;
+  if (first) std::memcpy(a.planes, frame->planes, sizeof a.planes);  // SECOND does not read them
+  std::memcpy(a.pv, occ->pv, sizeof a.pv);
+  a.pyramid = static_cast<const float*>(occ->pyramid);
+  a.width = occ->width;
+  a.height = occ->height;
+  a.bound = bound;
+  const size_t cap = instance_cap(ctx);
+  a.items = cs.d_instances;
+  a.bucket = cs.d_instances + cap;
+  a.member_inst = cs.d_instances + 2 * cap;
+  a.member_first = cs.d_instances + 3 * cap;  // cap + 1 words
+  a.tile_items = cs.d_tile_items;
+  a.tile_members = cs.d_tile_members;
+  a.scalars = cs.d_scalars;
+  a.words = static_cast<ulonglong2*>(cs.d_words);
+  a.record_header = static_cast<uint32_t*>(rec->record);
+  a.record_words = reinterpret_cast<unsigned long long*>(static_cast<char*>(rec->record) + mip::kClusterRecordHeaderBytes);
+  la.word_member = cs.d_word_member;
+  la.word_rank = cs.d_word_rank;
+  la.list_tiles = cs.d_list_tiles;
+  la.entries = static_cast<uint4*>(out->cluster_entries);
+  la.entry_capacity = out->entry_capacity;
+  la.entry_count = out->entry_count;
+  la.draw_args = out->draw_args;
+  la.list_stats = out->stats;
+  pa.entry_base = out->entry_base;
+  pa.list_candidates = cs.d_list_candidates;
+  pa.phase_scalars = cs.d_list_phase_scalars;
+  volatile uint32_t* status = ctx->h_cluster_status + 2u * slot + (async ? 0u : 1u);  // slot < MIP_MAX_FRAMES_IN_FLIGHT
+  MIP_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&a.status), const_cast<uint32_t*>(status), 0));
+  if (!async) *status = 0;  // (no synchronous call of the slot is in flight: each one drains its stream)
+#ifdef MIP_DEBUG_STAMPS
+  const DebugSwitches sw;
+  sw.tile_order(a.lods.n_tiles, a.lods.debug_tile_mult, a.lods.debug_tile_add);
+  a.debug_order = sw.reverse() ? mip::kClusterOrderReverse
+                  : (sw.order && std::strcmp(sw.order, "scramble") == 0) ? mip::kClusterOrderScramble : mip::kClusterOrderNone;
+#endif
+  const bool relative = policy->mode == MIP_LOD_RELATIVE;
+  for (const mip::ClusterListPhaseLaunch& l : plan.launches) {
+    int32_t rc = MIP_OK;
+    switch (l.kernel) {
+      // count, scan and members are mip_cull_clusters_phase's instantiations, word_members is mip_list_clusters': they read
+      // the leading blocks only
+      case mip::ClusterListPhaseKernel::count:
+        rc = relative ? launch(ctx, mip::mip_cluster_count_kernel<MIP_LOD_RELATIVE>, l.blocks, stream, a)
+                      : launch(ctx, mip::mip_cluster_count_kernel<MIP_LOD_DISTANCE>, l.blocks, stream, a);
+        break;
+      case mip::ClusterListPhaseKernel::scan:
+        rc = first ? launch(ctx, mip::mip_cluster_scan_kernel<mip::kClusterPlain>, l.blocks, stream, a)
+                   : launch(ctx, mip::mip_cluster_scan_kernel<mip::kClusterSecond>, l.blocks, stream, a);
+        break;
+      case mip::ClusterListPhaseKernel::members: rc = launch(ctx, mip::mip_cluster_members_kernel, l.blocks, stream, a); break;
+      case mip::ClusterListPhaseKernel::word_members: rc = launch(ctx, mip::mip_cluster_list_word_members_kernel, l.blocks, stream, la); break;
+      case mip::ClusterListPhaseKernel::front:
+        rc = first ? launch(ctx, mip::mip_cluster_list_phase_cull_kernel, l.blocks, stream, pa)
+                   : launch(ctx, mip::mip_cluster_list_phase_retest_kernel, l.blocks, stream, pa);
+        break;
+      case mip::ClusterListPhaseKernel::list_count:
+        rc = first ? launch(ctx, mip::mip_cluster_list_phase_count_kernel<true>, l.blocks, stream, pa)
+                   : launch(ctx, mip::mip_cluster_list_phase_count_kernel<false>, l.blocks, stream, pa);
+        break;
+      case mip::ClusterListPhaseKernel::list_epilogue:
+        rc = first ? launch(ctx, mip::mip_cluster_list_phase_epilogue_kernel<true>, l.blocks, stream, pa)
+                   : launch(ctx, mip::mip_cluster_list_phase_epilogue_kernel<false>, l.blocks, stream, pa);
+        break;
+      case mip::ClusterListPhaseKernel::list_write: rc = launch(ctx, mip::mip_cluster_list_phase_write_kernel, l.blocks, stream, pa); break;
+    }
+    if (rc) return rc;
+  }
+  if (first)
+    if (int32_t rc = record_written(ctx, stream)) return rc;
+  if (int32_t rc = finish(ctx, stream, async)) return rc;
+  if (!async && *status) {  // this call's own word, and its stream has drained
+    const uint32_t code = *status;
+    *status = 0;
+    if (code & mip::kClusterStatusDevice)
+      return fail(ctx, MIP_ERR_DEVICE, "mip_list_clusters_phase: the record's header names another W or another member count than this SECOND call's: it is not the record of the FIRST call over these members (a zero count is written, stats holds the call's W and members)");
+    return fail(ctx, MIP_ERR_CAPACITY, "mip_list_clusters_phase: more surviving clusters than the room behind entry_base (the first `room` entries are written), or more work items than work_capacity / 2^32 - 1 / the record has words for (no entry is written); stats holds the counts");
+  }
+  return MIP_OK;
+}
+
 }  // namespace
 
 // mip_wait, after every stream has drained. An overflow of an asynchronous call is reported when nothing else is: while `rc`
@@ -725,7 +922,7 @@ int32_t cluster_wait_status(MipContext* ctx, int32_t rc) {
   }
   if (!raised) return MIP_OK;
   if (raised & mip::kClusterStatusDevice) return fail(ctx, MIP_ERR_DEVICE, "asynchronous %s", kNotItsRecord);
-  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters, mip_list_clusters, mip_cull_clusters_views or mip_list_clusters_views had more runs than cmd_capacity (more surviving clusters than entry_capacity / entry_stride), or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
+  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters, mip_list_clusters, mip_list_clusters_phase, mip_cull_clusters_views or mip_list_clusters_views had more runs than cmd_capacity (more surviving clusters than entry_capacity / entry_stride / the room behind entry_base), or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
 }
 
 void cluster_release(MipContext* ctx) {
@@ -750,6 +947,8 @@ void cluster_release(MipContext* ctx) {
     (void)hipFree(cs.d_word_member);
     (void)hipFree(cs.d_word_rank);
     (void)hipFree(cs.d_list_tiles);
+    (void)hipFree(cs.d_list_candidates);
+    (void)hipFree(cs.d_list_phase_scalars);
   }
   ctx->cluster_scratch.clear();
   {
@@ -900,6 +1099,13 @@ int32_t mip_cull_clusters_phase(MipContext* ctx, const MipFrame* frame, const ui
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
   if (int32_t rc = check_policy(ctx, policy)) return rc;
   return cull_clusters(ctx, frame, visible_bitmap, policy, occ, out, rec, true);
+}
+
+int32_t mip_list_clusters_phase(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                const MipOcclusion* occ, const MipClusterPhaseListOutputs* out, const MipClusterRecord* rec) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  return list_clusters_phase(ctx, frame, visible_bitmap, policy, occ, out, rec);
 }
 
 // mip_cull_cluster_triangles and its cone form: the checks of the trailing fields, then the call the two structs share

@@ -157,6 +157,10 @@ struct MipContext {
     uint32_t* d_word_rank = nullptr;    // per survive word: the survivors of its list tile in front of it
     uint32_t* d_list_tiles = nullptr;   // per list tile: survivors, then their prefix
     size_t word_member_cap = 0, word_rank_cap = 0, list_tiles_cap = 0;
+    // mip_list_clusters_phase (cluster_list_phase_plan.hpp) on top of the list's: a row of list tiles and two words
+    uint32_t* d_list_candidates = nullptr;  // per list tile: the candidates of its record words (FIRST)
+    uint32_t* d_list_phase_scalars = nullptr;  // the entry base and the room, from the epilogue to the write kernel
+    size_t list_candidates_cap = 0;
   };
   std::vector<ClusterScratch> cluster_scratch;
   // mip_cull_clusters_views (cluster_views_plan.hpp): its own scratch on the first stream, as view_batch is — no frame slot's

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterListOutputs, MipClusterOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipClusterViewListOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterListOutputs, MipClusterOutputs, MipClusterPhaseListOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipClusterViewListOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
                    MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
@@ -176,6 +176,24 @@ def make_cluster_list_outputs(cluster_entries, entry_capacity, entry_count, draw
     o.entry_count = entry_count or None
     o.draw_args = draw_args or None
     o.stats = stats or None
+    return o
+
+
+def make_cluster_phase_list_outputs(cluster_entries, entry_capacity, entry_count, draw_args=0, stats=0, work_capacity=0, async_=False, entry_base=0):
+    """A MipClusterPhaseListOutputs for list_clusters_phase: make_cluster_list_outputs' fields — entry_capacity counts the
+    BUFFER's entries from entry 0, draw_args becomes {192, entry_count, 0, b}, stats has FOUR words {survivors, W, members,
+    candidates} — and entry_base, a device pointer to the word b the list starts at (0 / None: b = 0); it may be the FIRST
+    call's entry_count, so that SECOND appends behind FIRST's entries without the host reading the count."""
+    o = MipClusterPhaseListOutputs()
+    o.struct_size = C.sizeof(MipClusterPhaseListOutputs)
+    o.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+    o.cluster_entries = cluster_entries or None
+    o.entry_capacity = int(entry_capacity)
+    o.work_capacity = int(work_capacity)
+    o.entry_count = entry_count or None
+    o.draw_args = draw_args or None
+    o.stats = stats or None
+    o.entry_base = entry_base or None
     return o
 
 
@@ -833,6 +851,17 @@ class InstancePipeline:
             C.memmove(C.addressof(fr[v]), C.addressof(frames[v]), C.sizeof(MipFrame))
         bm = (C.c_void_p * max(k, 1))(*[int(b) if b else None for b in visible_bitmap_ptrs])
         self._check(self._lib.mip_list_clusters_views(self._ctx, C.addressof(fr), C.addressof(bm), k, C.addressof(policy), C.addressof(outputs)))
+
+    def list_clusters_phase(self, frame, visible_bitmap_ptr, policy, outputs, occlusion, record):
+        """mip_list_clusters_phase: cull_clusters_phase with list_clusters' flat list in the commands' place. With a FIRST
+        `record` (make_cluster_record) one entry per cluster that survives under `occlusion` (last frame's pyramid), and the
+        record cull_clusters_phase writes; with a SECOND record one entry per recorded cluster that is visible under the new
+        `occlusion`. The list starts at entry *entry_base of `outputs` (make_cluster_phase_list_outputs), read on the device:
+        with entry_base = FIRST's entry_count SECOND appends behind FIRST's entries. MIP_ERR_CAPACITY / MIP_ERR_DEVICE as for
+        list_clusters and cull_clusters_phase (from wait() for an asynchronous call)."""
+        self._check(self._lib.mip_list_clusters_phase(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                      C.addressof(occlusion) if occlusion is not None else None, C.addressof(outputs),
+                                                      C.addressof(record) if record is not None else None))
 
     # -- diagnostics --
     def timings(self):
