@@ -255,6 +255,7 @@ int32_t mip_create(const MipConfig* cfg, MipContext** out) {
       const uint32_t v = (uint32_t)std::strtoul(env, nullptr, 10) / 64u * 64u;
       if (v >= 256u && v <= 8192u) ctx->tri_ticket_slots = v;
     }
+    if (const char* env = std::getenv("MIP_TUNE_TRI_RANGE_BLOCKS")) ctx->tri_range_blocks = (uint32_t)std::strtoul(env, nullptr, 10);  // (the plan ignores a value outside the resident grid)
     if (const char* env = std::getenv("MIP_TUNE_TRI_CHUNKS_FROM")) ctx->tri_chunks_from = (uint32_t)std::strtoul(env, nullptr, 10);
     if (const char* env = std::getenv("MIP_TUNE_TRI_NO_CHOICE")) ctx->tri_no_choice = std::atoi(env) != 0;
     if (const char* env = std::getenv("MIP_TUNE_TRI_CHOICE")) ctx->tri_force_choice = env[0] == 'b' ? 1 : (env[0] == 'w' ? 2 : 0);

@@ -52,6 +52,7 @@ mip::PlanState plan_state(const MipContext* ctx) {
   st.tri_parts_max = ctx->tri_parts_max;
   st.tri_chunks_from = ctx->tri_chunks_from;
   st.tri_chunk_blocks_per_cu = mip::triangle_chunks_blocks_per_cu();
+  st.tri_range_blocks = ctx->tri_range_blocks;
   st.tri_no_choice = ctx->tri_no_choice;
   st.max_lod_tris = ctx->max_lod_tris;
   st.n_joints = ctx->n_joints;

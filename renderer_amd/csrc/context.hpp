@@ -242,6 +242,7 @@ struct MipContext {
   uint32_t tri_parts_max = 1024;   // instance counts up to this use the parts kernel (16 work items per command), 0 = off
   bool tri_recompact_three_launches = false;  // MIP_TUNE_TRI_RECOMPACT_LAUNCHES=3: round 4's count / scan / scatter instead of the one-launch form (A/B, tests)
   uint32_t tri_ticket_slots = 4096; // long triangle streams: slots per range of the range kernel (MIP_TUNE_TRI_RANGE_SLOTS: 256 .. 8192, whole steps of 64)
+  uint32_t tri_range_blocks = 0;   // MIP_TUNE_TRI_RANGE_BLOCKS: workgroups of the range grid and the large-frame stage grid (tests); 0 = the resident grid
   uint32_t tri_chunks_from = 0;    // instance counts from this use the range kernel; MIP_TUNE_TRI_CHUNKS_FROM (4294967295 = never: the round-4 kernels)
   bool tri_no_choice = false;      // tuning (MIP_TUNE_TRI_NO_CHOICE): large frames always take the wave-per-command kernel
   int tri_force_choice = 0;        // tuning (MIP_TUNE_TRI_CHOICE=block|waves): 1 / 2 force the device-side choice of the large-frame grid

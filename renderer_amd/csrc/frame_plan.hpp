@@ -37,6 +37,8 @@ struct PlanState {
   uint32_t tri_parts_max = 1024;   // instance counts up to this use the parts kernel, 0 = off
   uint32_t tri_chunks_from = 0;    // instance counts from this use the chunk kernel (round 5); 0xffffffff = never (MIP_TUNE_TRI_CHUNKS_FROM)
   uint32_t tri_chunk_blocks_per_cu = 8;  // workgroups of the chunk kernel a CU holds at once (asked of the runtime)
+  uint32_t tri_range_blocks = 0;   // MIP_TUNE_TRI_RANGE_BLOCKS: workgroups of the range grid and of the large-frame stage grid, 1 .. the resident
+                                   // grid; 0 or beyond = the resident grid (tests: a small grid puts the range edges within reach of small streams)
   bool tri_no_choice = false;      // MIP_TUNE_TRI_NO_CHOICE: large frames always take the wave-per-command kernel (A/B)
   uint32_t max_lod_tris = 0;       // largest triangle count of LOD 0 / LOD 1 over the mesh table
   uint32_t n_joints = 0;           // skinned frames
@@ -159,6 +161,36 @@ constexpr bool plan_tri_choice_is_block(uint32_t max_lod_tris, uint32_t index_to
   return 10ull * walk > 7ull * total_tris || (unsigned long long)max_lod_tris * command_count > 4ull * total_tris;
 }
 
+// ---- the range decomposition and the size-class sort of the per-triangle stage: the rules the kernels (triangle_kernels.hpp) and
+// the host's sizing share (constexpr: device code calls them as they stand; tests/native/frame_plan_probe.cpp prints them) ----
+// Slots per range, in whole steps of 64. A stream that gives every wave of the (resident) grid at most `ticket_slots` slots is cut
+// into one range per wave, dealt statically; a longer stream is cut into ranges of `ticket_slots`, a wave's first range its own,
+// the others pulled from a counter (triangle_kernels.hpp has the measurements).
+constexpr uint32_t kRangeMinSlots = 256;
+constexpr uint32_t kRangeMaxSlots = 8192;   // = kRangeMaskSteps * 64: a continuing segment's masks always fit
+constexpr uint32_t range_slots(uint32_t total, uint32_t n_waves, uint32_t ticket_slots) {
+  const uint32_t one = (uint32_t)((((unsigned long long)total + n_waves - 1u) / n_waves + 63u) / 64u) * 64u;
+  if (one <= ticket_slots) return one < kRangeMinSlots ? kRangeMinSlots : one;
+  return ticket_slots;
+}
+// The size class of a command: floor(log2(triangles)); commands without a triangle share class 0.
+constexpr uint32_t tri_size_class(uint32_t index_count) {
+  const uint32_t n_tris = index_count / 3u;
+  return n_tris ? 31u - (uint32_t)__builtin_clz(n_tris) : 0u;
+}
+// Commands per ticket of class k: a ticket is worth ~4 096 triangles, and at most 16 commands (a small command costs its start-up
+// latency, not its triangles).
+constexpr uint32_t plan_tri_sort_batch(uint32_t k) {
+  const uint32_t batch = k >= 12u ? 1u : 4096u >> k;
+  return batch > 16u ? 16u : batch;
+}
+// Workgroups of the range grid and of the large-frame stage grid: resident as a whole (a range's predecessors are running when it
+// looks for them), or the tuned count where that lies inside it.
+constexpr uint32_t plan_tri_range_blocks(uint32_t cu_count, uint32_t blocks_per_cu, uint32_t tuned) {
+  const uint32_t resident = cu_count * blocks_per_cu;
+  return tuned >= 1u && tuned <= resident ? tuned : resident;
+}
+
 // The whole decision. Order of the checks = order of the error messages round 3's validate_run produced.
 inline LaunchPlan plan_frame(const PlanState& st, const PlanRequest& rq) {
   if (!st.have_instances || !st.have_meshes) return plan_refuse(MIP_ERR_NOT_READY, "instances or mesh table not set");
@@ -239,7 +271,7 @@ inline LaunchPlan plan_frame(const PlanState& st, const PlanRequest& rq) {
       p.need_chunk_scratch = true;
       p.tri_reset_ticket = true;  // long streams: a wave's later ranges are pulled from the counter (and the sorted commands are)
       p.tri_map_blocks = (n + 255u) / 256u;
-      p.tri_blocks = st.cu_count * st.tri_chunk_blocks_per_cu;  // resident as a whole: a range's predecessors are running when it looks for them
+      p.tri_blocks = plan_tri_range_blocks(st.cu_count, st.tri_chunk_blocks_per_cu, st.tri_range_blocks);
     } else if (parts) {
       p.tri = TriangleKernel::parts;
       p.tri_threads = 256;

@@ -280,11 +280,6 @@ __device__ __forceinline__ bool tri_choice_is_block(const TriangleArgs& a) {
 #ifndef MIP_TRI_WAVE_KERNEL_WAVES_PER_SIMD
 #define MIP_TRI_WAVE_KERNEL_WAVES_PER_SIMD 8
 #endif
-__device__ __forceinline__ uint32_t tri_size_class(uint32_t index_count) {
-  const uint32_t n_tris = index_count / 3u;
-  return n_tris ? 31u - (uint32_t)__builtin_clz(n_tris) : 0u;
-}
-
 // One wave per command (the body of mip_triangle_cull_kernel, and of mip_triangle_stage_kernel when the frame is not the range kernel's).
 __device__ __forceinline__ void triangle_waves_body(const TriangleArgs& a, uint32_t count) {
   const uint32_t lane = threadIdx.x & 63u;
@@ -403,9 +398,7 @@ __global__ __launch_bounds__(256) void mip_triangle_sort_scatter_kernel(const Tr
         if (q < copy) below += h;
       }
     }
-    // a ticket is worth ~4 096 triangles, and at most 16 commands (a small command costs its start-up latency, not its triangles)
-    uint32_t batch = k >= 12u ? 1u : 4096u >> k;
-    if (batch > 16u) batch = 16u;
+    const uint32_t batch = plan_tri_sort_batch(k);  // (frame_plan.hpp)
     const uint32_t start = wave_inclusive_scan(total) - total;
     const uint32_t tickets = tid < 32u ? (total + batch - 1u) / batch : 0u;
     const uint32_t tickets_upto = wave_inclusive_scan(tickets);
@@ -939,8 +932,8 @@ __global__ __launch_bounds__(256, 4) void mip_triangle_cull_parts_kernel(const T
 // cull_pipeline.rs:560-576 dispatches ceil(tris / wg) of them): every unit of work is the same size. Rounds 1-4 handed a
 // WHOLE command (up to tens of thousands of triangles) to one wave or one workgroup from a ticket counter, and a launch
 // ended with waves walking their last command alone (up to 19 % of it: profiles/r04_triangle_bound_experiments.txt).
-// Here the frame's triangle stream is cut into equal RANGES, one per wave of a grid that is resident as a whole (a few
-// per wave when MIP_TUNE_TRI_RANGES_PER_WAVE says so); no ticket (11 ns per same-address atomic), no tail. Command c owns
+// Here the frame's triangle stream is cut into equal RANGES, one per wave of a grid that is resident as a whole (long
+// streams: a wave's later ranges come from a counter, below); no tail. Command c owns
 // the SLOTS
 //     [slot0(c), slot0(c) + indexCount(c) / 3),   slot0(c) = (firstIndex(c) - first_index_base) / 3
 // of that stream (firstIndex is already the running sum of indexCount over the emitted commands — the instance kernel's
@@ -965,13 +958,7 @@ __global__ __launch_bounds__(256, 4) void mip_triangle_cull_parts_kernel(const T
 // at the same rate (the SIMD issues its oldest wave first: equal static shares ended 1.1 .. 3.1 ms apart on the 300 k
 // frame, profiles/r05_wave_kernel_lifetimes.txt), and a ticket per 4 096 triangles is one per ~20 ns of the launch, above
 // the ~11 ns a same-address atomic takes.
-constexpr uint32_t kRangeMinSlots = 256;
-constexpr uint32_t kRangeMaxSlots = 8192;   // = kRangeMaskSteps * 64: a continuing segment's masks always fit
-__host__ __device__ __forceinline__ uint32_t range_slots(uint32_t total, uint32_t n_waves, uint32_t ticket_slots) {
-  const uint32_t one = (uint32_t)((((unsigned long long)total + n_waves - 1u) / n_waves + 63u) / 64u) * 64u;
-  if (one <= ticket_slots) return one < kRangeMinSlots ? kRangeMinSlots : one;
-  return ticket_slots;
-}
+// The rule itself — range_slots, kRangeMinSlots, kRangeMaxSlots — is in frame_plan.hpp.
 
 // (range b starts with the first command whose slots END behind b * S)
 // The kernel in front of the stage, one thread per command: for the range decomposition the map of range -> first command; for
@@ -1010,10 +997,9 @@ __global__ __launch_bounds__(256) void mip_triangle_prepare_kernel(const Triangl
 constexpr uint32_t kChunkPolls = 128;        // x (s_sleep 2 + one load): some tens of microseconds
 constexpr uint32_t kRangeMaskSteps = kRangeMaxSlots / 64u;  // keep masks of a continuing segment: 1 KB of LDS per wave and buffer
 
-// The same walk without the software pipeline and with the path chosen at run time: the rare paths (a range's share
-// counted for a wave that has not published; the tail of a continuing segment beyond the mask buffer).
-template <bool kWrite>
-__device__ __forceinline__ uint32_t chunk_rewalk(const TriangleArgs& a, uint32_t base, const float (&pv)[16], uint32_t c, uint32_t b, uint32_t e, size_t dst_tri) {
+// The same walk without the software pipeline, with the path chosen at run time and nothing written: the rare path (a range's
+// share counted for a wave that has not published). Returns the survivors of triangles [b, e) of command c.
+__device__ __forceinline__ uint32_t chunk_rewalk(const TriangleArgs& a, uint32_t base, const float (&pv)[16], uint32_t c, uint32_t b, uint32_t e) {
   const uint32_t lane = threadIdx.x & 63u;
   const ChunkCmd m = chunk_load_cmd(a, base, c);
   float model[16];
@@ -1030,14 +1016,7 @@ __device__ __forceinline__ uint32_t chunk_rewalk(const TriangleArgs& a, uint32_t
       j0 = ip[0]; j1 = ip[1]; j2 = ip[2];
     }
     const bool keep = valid && !triangle_culled(affine, model, pv, a.vertices, (long long)m.vertex_offset, j0, j1, j2);
-    const unsigned long long mask = __ballot(keep);
-    if constexpr (kWrite) {
-      if (keep) {
-        uint32_t* dst = a.out_indices + (dst_tri + survivors + lanes_below(mask)) * 3;
-        dst[0] = j0; dst[1] = j1; dst[2] = j2;
-      }
-    }
-    survivors += (uint32_t)__popcll(mask);
+    survivors += (uint32_t)__popcll(__ballot(keep));
   }
   return survivors;
 }
@@ -1113,7 +1092,7 @@ __device__ __forceinline__ uint32_t chunk_lookback(const TriangleChunkArgs& ca, 
       if ((uint32_t)(g >> 32) != ca.epoch) {
         const uint32_t b_slot = jj * S > p.slot0 ? jj * S : p.slot0;
         const uint32_t b = b_slot - p.slot0, e = (jj + 1u) * S - p.slot0;  // (the command goes on past range jj: e < n_tris)
-        const uint32_t survivors = chunk_rewalk<false>(a, ca.first_index_base, pv, p.c, b, e, 0);
+        const uint32_t survivors = chunk_rewalk(a, ca.first_index_base, pv, p.c, b, e);
         g = ((unsigned long long)ca.epoch << 32) | survivors;
         if (lane == 0u) {
           __hip_atomic_store(&ca.range_status[jj], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

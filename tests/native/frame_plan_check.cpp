@@ -22,6 +22,39 @@ static unsigned long long combos = 0, refused = 0, planned = 0;
     }                                                                           \
   } while (0)
 
+// plan_frame as it was before PlanState.tri_range_blocks existed: the range grid is the resident one. (Every other field is
+// checked against rules restated in check_one; this one pins "unset changes nothing" and "set changes only the range grid".)
+static bool same_plan_but_grid(const LaunchPlan& a, const LaunchPlan& b) {
+  LaunchPlan x = a, y = b;
+  x.tri_blocks = y.tri_blocks = 0;
+  return x.status == y.status && std::strcmp(x.why, y.why) == 0 && x.device_out == y.device_out && x.async == y.async && x.empty == y.empty &&
+         x.n_tiles == y.n_tiles && x.order == y.order && x.general == y.general && x.box_override == y.box_override && x.wire == y.wire &&
+         x.group_shift == y.group_shift && x.uses_prefix_state == y.uses_prefix_state && x.skin == y.skin && x.skin_blocks == y.skin_blocks &&
+         x.tri == y.tri && x.tri_threads == y.tri_threads && x.tri_map_blocks == y.tri_map_blocks && x.tri_block_tickets == y.tri_block_tickets &&
+         x.tri_either_blocks == y.tri_either_blocks && x.tri_reset_ticket == y.tri_reset_ticket && x.recompact == y.recompact &&
+         x.recompact_blocks == y.recompact_blocks && x.need_staging == y.need_staging && x.need_tri_scratch == y.need_tri_scratch &&
+         x.need_part_status == y.need_part_status && x.need_chunk_scratch == y.need_chunk_scratch && x.need_skin_box == y.need_skin_box;
+}
+
+static void check_one(const PlanState& st, const PlanRequest& rq);
+
+// The state as given, and with every value of the tuned range grid that matters: inside the resident grid, its edges, beyond.
+static void check_range_blocks(PlanState st, const PlanRequest& rq) {
+  st.tri_range_blocks = 0;
+  const LaunchPlan unset = plan_frame(st, rq);
+  const uint32_t resident = st.cu_count * st.tri_chunk_blocks_per_cu;
+  const bool range_grid = unset.tri == TriangleKernel::chunks || unset.tri == TriangleKernel::sorted;
+  if (range_grid) CHECK(unset.tri_blocks == resident, "unset: the range grid is the resident one");
+  for (uint32_t b : {1u, 2u, resident - 1u, resident, resident + 1u, 0xffffffffu}) {
+    st.tri_range_blocks = b;
+    check_one(st, rq);
+    const LaunchPlan p = plan_frame(st, rq);
+    CHECK(same_plan_but_grid(unset, p), "the tuned range grid changes nothing but tri_blocks (%u)", b);
+    const uint32_t want = range_grid && b >= 1u && b <= resident ? b : unset.tri_blocks;
+    CHECK(p.tri_blocks == want, "tuned range grid %u: tri_blocks %u, expected %u", b, p.tri_blocks, want);
+  }
+}
+
 static void check_one(const PlanState& st, const PlanRequest& rq) {
   ++combos;
   const LaunchPlan p = plan_frame(st, rq);
@@ -81,7 +114,9 @@ static void check_one(const PlanState& st, const PlanRequest& rq) {
     if (p.tri == TriangleKernel::chunks || p.tri == TriangleKernel::sorted) {
       CHECK(st.n >= st.tri_chunks_from && !st.tri_block_threads, "range kernel preconditions");
       CHECK((p.tri == TriangleKernel::sorted) == (st.n > st.tri_block_max), "sorted commands + device-side choice above tri_block_max");
-      CHECK(p.tri_blocks == st.cu_count * st.tri_chunk_blocks_per_cu && p.tri_threads == 256, "chunk grid: resident as a whole");
+      const uint32_t resident = st.cu_count * st.tri_chunk_blocks_per_cu;
+      CHECK(p.tri_threads == 256 && p.tri_blocks == (st.tri_range_blocks >= 1u && st.tri_range_blocks <= resident ? st.tri_range_blocks : resident),
+            "chunk grid: resident as a whole, or the tuned grid inside it");
       CHECK((uint64_t)p.tri_map_blocks * 256u >= st.n && (uint64_t)(p.tri_map_blocks - 1u) * 256u < st.n, "chunk map: one thread per possible command");
     } else if (p.tri == TriangleKernel::parts) {
       CHECK(st.n < st.tri_chunks_from || st.tri_block_threads, "the chunk kernel comes first where it is switched on");
@@ -138,6 +173,23 @@ static void check_tri_choice() {
     }
 }
 
+// The rules the range kernel and the size-class sort share with the host (moved here from triangle_kernels.hpp: same values).
+static void check_range_rules() {
+  static_assert(kRangeMinSlots == 256 && kRangeMaxSlots == 8192, "range size limits");
+  static_assert(range_slots(1, 8192, 4096) == 256 && range_slots(0, 4, 4096) == 256, "short streams: the smallest range");
+  static_assert(range_slots(8192u * 256u, 8192, 4096) == 256 && range_slots(8192u * 256u + 1u, 8192, 4096) == 320, "one range per wave, whole steps of 64");
+  static_assert(range_slots(8192u * 4096u, 8192, 4096) == 4096 && range_slots(8192u * 4096u + 1u, 8192, 4096) == 4096, "long streams: ticket_slots");
+  static_assert(range_slots(4u * 300u, 4, 300) == 300 && range_slots(4u * 257u, 4, 300) == 300 && range_slots(4u * 256u, 4, 300) == 256, "a ticket size that is no multiple of 64 is taken as it is");
+  static_assert(range_slots(0xffffffffu, 4, 8192) == 8192, "no overflow at the end of 32 bits");
+  static_assert(tri_size_class(0) == 0 && tri_size_class(2) == 0 && tri_size_class(3) == 0 && tri_size_class(5) == 0 && tri_size_class(6) == 1 &&
+                tri_size_class(3 * 65535) == 15 && tri_size_class(3 * 65536) == 16 && tri_size_class(3 * 65536 + 2) == 16 && tri_size_class(0xffffffffu) == 30, "size classes");
+  static_assert(plan_tri_sort_batch(0) == 16 && plan_tri_sort_batch(8) == 16 && plan_tri_sort_batch(9) == 8 && plan_tri_sort_batch(10) == 4 &&
+                plan_tri_sort_batch(11) == 2 && plan_tri_sort_batch(12) == 1 && plan_tri_sort_batch(31) == 1, "commands per ticket");
+  for (uint32_t k = 0; k < 32; ++k) CHECK(plan_tri_sort_batch(k) >= 1 && plan_tri_sort_batch(k) <= 16, "batch of class %u", k);
+  static_assert(plan_tri_range_blocks(256, 8, 0) == 2048 && plan_tri_range_blocks(256, 8, 1) == 1 && plan_tri_range_blocks(256, 8, 2048) == 2048 &&
+                plan_tri_range_blocks(256, 8, 2049) == 2048, "tuned range grid");
+}
+
 int main() {
   check_tri_choice();
   const uint32_t sizes[] = {0u, 1u, 257u, 768u, 1025u, 3073u, 65537u, 327680u, 327681u, 524288u, 524289u, 1114112u, 1114113u, 0x3fffffffu};  // the order thresholds at 256 CUs
@@ -183,6 +235,7 @@ int main() {
                       rq.flags = flags;
                       rq.cmds_address = rq.cmds ? 0x7f0000001000ull : 0ull;
                       check_one(st, rq);
+                      if (rq.triangles && flags == MIP_OUT_DEVICE) check_range_blocks(st, rq);
                       if (rq.cmds && (flags & MIP_OUT_WIRE)) {  // the same with a list that is only 4-byte aligned
                         rq.cmds_address += 4;
                         check_one(st, rq);
@@ -205,8 +258,10 @@ int main() {
           for (bool no_choice : {false, true}) {
             st.tri_no_choice = no_choice;
             check_one(st, rq);
+            check_range_blocks(st, rq);
           }
         }
+  check_range_rules();
   CHECK(plan_wire_index_bits(0) == 31 && plan_wire_index_bits(1) == 31 && plan_wire_index_bits(2) == 30 && plan_wire_index_bits(64) == 25 &&
         plan_wire_index_bits(65) == 24 && plan_wire_index_bits(0xffffffffu) == 0, "index bits of a packed record");
   std::printf("PLAN OK %llu combinations (%llu planned, %llu refused)\n", combos, planned, refused);

@@ -8,6 +8,10 @@
 //     request=model,bitmap,cmds,aabb,tlas,triangles,skinned,wire,packed,async,host   (cmds implies count and index_total)
 //             draw_cmds,count,index_total   (each pointer of the command outputs on its own: every combination, refused ones too)
 //     sweep=FIRST:LAST:STEP   instead of n=: one line per n = FIRST, FIRST+STEP, ... <= LAST
+//     tri_range_blocks=0 tri_chunk_blocks_per_cu=8
+//     rules=TOTAL:N_WAVES:TICKET_SLOTS[:INDEX_COUNT,INDEX_COUNT,...]   instead of a plan: one JSON line with the rules of the range
+//             decomposition and of the size-class sort — range_slots(TOTAL, N_WAVES, TICKET_SLOTS), its limits, the commands per
+//             ticket of every class, the class of every INDEX_COUNT, and the range grid of the state given so far
 // The constants of the prefix structure that are no plan field (tile, level-1 window) are printed with every line.
 #include "../../renderer_amd/csrc/frame_plan.hpp"
 
@@ -76,6 +80,32 @@ int main(int argc, char** argv) {
     else if (key == "tri_block_max") st.tri_block_max = u;
     else if (key == "tri_parts_max") st.tri_parts_max = u;
     else if (key == "tri_block_threads") st.tri_block_threads = u;
+    else if (key == "tri_range_blocks") st.tri_range_blocks = u;
+    else if (key == "tri_chunk_blocks_per_cu") st.tri_chunk_blocks_per_cu = u;
+    else if (key == "rules") {
+      unsigned long total = 0, n_waves = 0, ticket_slots = 0;
+      int used = 0;
+      if (std::sscanf(val, "%lu:%lu:%lu%n", &total, &n_waves, &ticket_slots, &used) != 3 || n_waves == 0) {
+        std::fprintf(stderr, "frame_plan_probe: rules=TOTAL:N_WAVES:TICKET_SLOTS[:INDEX_COUNT,...]\n");
+        return 2;
+      }
+      std::printf("{\"range_slots\": %u, \"range_min_slots\": %u, \"range_max_slots\": %u, \"range_blocks\": %u, \"sort_batch\": [",
+                  range_slots((uint32_t)total, (uint32_t)n_waves, (uint32_t)ticket_slots), kRangeMinSlots, kRangeMaxSlots,
+                  plan_tri_range_blocks(st.cu_count, st.tri_chunk_blocks_per_cu, st.tri_range_blocks));
+      for (uint32_t k = 0; k < 32u; ++k) std::printf("%s%u", k ? ", " : "", plan_tri_sort_batch(k));
+      std::printf("], \"size_class\": [");
+      const char* at = val + used;
+      for (bool first_one = true; *at == ':' || *at == ',';) {
+        char* end = nullptr;
+        const uint32_t index_count = (uint32_t)std::strtoul(at + 1, &end, 10);
+        if (end == at + 1) break;
+        std::printf("%s%u", first_one ? "" : ", ", tri_size_class(index_count));
+        first_one = false;
+        at = end;
+      }
+      std::printf("]}\n");
+      return 0;
+    }
     else if (key == "sweep") {
       if (std::sscanf(val, "%lu:%lu:%lu", &first, &last, &step) != 3 || step == 0) {
         std::fprintf(stderr, "frame_plan_probe: sweep=FIRST:LAST:STEP\n");
