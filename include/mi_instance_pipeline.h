@@ -1053,7 +1053,7 @@ int32_t mip_cull_cluster_triangles_cone(MipContext* ctx, const MipFrame* frame, 
  * need no wait. Scratch is the call's own, allocated at first use and grown by a larger call: (1 + n_views) x 8 bytes per 64
  * work items of the bound plus 2 bytes per instance, beside the per-instance lists. No frame slot's cluster scratch is
  * touched: a cluster call behind a frame slot and this call do not disturb each other.
- * OUT OF SCOPE: a pyramid per view; the two phases; the per-triangle stream; cones; shards; skinned instances; mip_run_many
+ * OUT OF SCOPE: a pyramid per view (mip_list_clusters_views_occluded below); the two phases; the per-triangle stream; cones; shards; skinned instances; mip_run_many
  * and recorded graphs. */
 typedef struct MipClusterViewOutputs {
   uint32_t struct_size;      /* = sizeof(MipClusterViewOutputs) */
@@ -1169,7 +1169,7 @@ int32_t mip_list_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t
  * ORDERING: enqueued on the context's first stream, as mip_run_views and mip_cull_clusters_views are. Scratch is the
  * several-view call's own, grown by this call: on top of mip_cull_clusters_views' planes, (1 + n_views) x 4 bytes per 64 work
  * items of the bound. Both several-view calls run on the one stream, so sharing the scratch is ordered.
- * OUT OF SCOPE: a pyramid per view; cones; the two phases; the per-triangle stream; one list packed tightly over all views;
+ * OUT OF SCOPE: a pyramid per view (mip_list_clusters_views_occluded below); cones; the two phases; the per-triangle stream; one list packed tightly over all views;
  * shards; skinned instances; mip_run_many and recorded graphs. */
 typedef struct MipClusterViewListOutputs {
   uint32_t struct_size;      /* = sizeof(MipClusterViewListOutputs) */
@@ -1184,6 +1184,70 @@ typedef struct MipClusterViewListOutputs {
 
 int32_t mip_list_clusters_views(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps,
                                 uint32_t n_views, const MipLodPolicy* policy, const MipClusterViewListOutputs* out);
+
+/* ---- Extension: visible-cluster lists for several views, a depth pyramid per view ------------------------------------------
+ * mip_list_clusters_views with the OCCLUSION TEST behind the plane test of every view that brings a pyramid: a renderer with
+ * stereo eyes, cube faces or cascades holds one depth image per view, and ONE call forms the level, the work items and the
+ * world box of every (instance, cluster) once, tests them against every view's planes and — for a view with a pyramid —
+ * against that view's pyramid, and writes one list of 16-byte MipClusterEntry and one VkDrawIndirectCommand per view. NOT a
+ * reference behaviour; checked against this repository's restatement (tests/cluster_views_occluded_restatement.py), byte for
+ * byte. Every entry point above is unchanged.
+ *
+ * BORROWED TERMS: VIEWS, ONE LOD FOR ALL VIEWS (frames[0].cam_pos), MEMBERS (the union of the views' bitmaps, a NULL bitmap
+ * counting as every instance), WORK ITEMS, W and the world box are the words of mip_cull_clusters_views, unchanged. A view's
+ * pyramid never changes membership, W or the work items.
+ * occs: a HOST array of n_views HOST pointers. occs[v] == NULL: view v is tested against its planes alone. A non-NULL entry
+ * is read as mip_cull_clusters reads its occ: pyramid, width, height and pv are read; candidates and occluded_bitmap must be
+ * NULL and flags 0. Two views may share a pyramid pointer, with the same or different pv.
+ * PASSES_v(i, c): bit i of view v is set, AND the shared world box is not culled by the plane test against frames[v].planes
+ * (SURVIVES_v of mip_cull_clusters_views).
+ * SURVIVES_v(i, c) = PASSES_v(i, c) AND (occs[v] is NULL OR the world box is not occluded under occs[v]). "Occluded" is
+ * steps 1-9 of the OCCLUSION TEST above, on the world box, under occs[v]'s pv, pyramid and extents.
+ * hidden (optional, n_views words): hidden[v] = the number of work items with PASSES_v and not SURVIVES_v; 0 for a view
+ * without a pyramid. An exact integer count whatever the order of execution.
+ * ENTRIES, entry_counts, draw_args and stats ({W, members, survivors_0, survivors_1, ...}, 2 + n_views words) are
+ * mip_list_clusters_views' rules with this SURVIVES_v; THE CONSUMER is that call's.
+ * ENTRY OVERFLOW (some survivors_v > entry_stride): that view keeps its first entry_stride entries exactly as with room,
+ * entry_counts[v] = draw_args[4v+1] = entry_stride, the other views are complete, stats and hidden are true, and the status is
+ * MIP_ERR_CAPACITY.
+ * WORK OVERFLOW (W > work_capacity — 0 = the library's own bound, N x the largest C of the table — or W >= 2^32): every count
+ * is 0, draw_args of view v = {192, 0, 0, v * entry_stride}, stats = {W mod 2^32, members, 0, ...}, hidden is all zero, no
+ * entry is written, MIP_ERR_CAPACITY; the context stays usable.
+ * WHO REPORTS is mip_cull_clusters_views' rule, on the pair of status words both several-view calls already share. None of
+ * the several-view calls is ever charged to a frame slot's cluster call, nor the other way round.
+ * N = 0 writes n_views zero counts, {192, 0, 0, v * entry_stride} per view, zero stats and zero hidden.
+ * THE THREE EQUIVALENCES: let f_v = frames[v] with cam_pos replaced by frames[0].cam_pos. (a) View v's entries,
+ * entry_counts[v] and survivors_v are byte for byte what mip_list_clusters(ctx, &f_v, visible_bitmaps[v] (a full bitmap where
+ * the entry is NULL), policy, occs[v], NULL, {entry_capacity = entry_stride}) writes, whenever both calls run. (b) With every
+ * occs[v] NULL every output is byte for byte mip_list_clusters_views' and hidden is zero. (c) View v's list is a subsequence
+ * of the list mip_list_clusters_views writes for view v, and survivors_v + hidden[v] equals that call's survivors_v.
+ * REFUSED, nothing written, MIP_ERR_INVALID_ARGUMENT: everything mip_list_clusters_views refuses (n_views x entry_stride >=
+ * 2^32 among it); a NULL occs (for no pyramid at all pass an array of NULLs, or use the plain call); any non-NULL entry that
+ * mip_cull_clusters would refuse — a wrong struct_size, candidates, occluded_bitmap or flags set, an extent of 0 or above
+ * MIP_MAX_DEPTH_EXTENT, a NULL pyramid — and the message names the view; hidden not 4-byte aligned; hidden inside stats,
+ * draw_args or entry_counts. MIP_ERR_NOT_READY as for mip_list_clusters_views.
+ * ORDERING: enqueued on the context's first stream, as the other several-view calls are. When a non-NULL occs entry exists
+ * and the stream of the frame slot the next run takes — where mip_build_depth_pyramid enqueues — is not the first stream, the
+ * call goes behind what that stream holds now (an event recorded there, waited for on the device): V pyramids built with
+ * mip_build_depth_pyramid (asynchronous) need no mip_wait in front of this call. Scratch is the several-view scratch,
+ * unchanged in size: no new plane.
+ * OUT OF SCOPE: commands per view under a pyramid; a two-phase record per view; cones; the per-triangle stream; shards;
+ * skinned instances; mip_run_many and recorded graphs. */
+typedef struct MipClusterViewOccludedListOutputs {
+  uint32_t struct_size;      /* = sizeof(MipClusterViewOccludedListOutputs) */
+  uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
+  void* cluster_entries;     /* DEVICE, 16-byte aligned: n_views x entry_stride MipClusterEntry */
+  uint32_t entry_stride;     /* entries reserved per view */
+  uint32_t work_capacity;    /* bound on W of the union of the views' members; 0 = N x the largest C */
+  uint32_t* entry_counts;    /* DEVICE: n_views words: min(survivors_v, entry_stride) */
+  uint32_t* draw_args;       /* DEVICE, optional: n_views x 4 words */
+  uint32_t* stats;           /* DEVICE, optional: 2 + n_views words: W, members, survivors_0 ... */
+  uint32_t* hidden;          /* DEVICE, optional: n_views words: work items that passed view v's planes and are occluded */
+} MipClusterViewOccludedListOutputs; /* 56 B */
+
+int32_t mip_list_clusters_views_occluded(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps,
+                                         const MipOcclusion* const* occs, uint32_t n_views, const MipLodPolicy* policy,
+                                         const MipClusterViewOccludedListOutputs* out);
 
 /* ---- Extension: the visible-cluster list in two phases ---------------------------------------------------------------------
  * mip_cull_clusters_phase with mip_list_clusters' flat list in the commands' place: FIRST writes one MipClusterEntry per work
@@ -1251,7 +1315,7 @@ int32_t mip_list_clusters_phase(MipContext* ctx, const MipFrame* frame, const ui
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every
  * frames_in_flight frames): it is where their errors surface. The MIP_ERR_CAPACITY of an asynchronous
- * mip_cull_clusters, mip_list_clusters, mip_list_clusters_phase, mip_cull_clusters_views or mip_list_clusters_views (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase or mip_list_clusters_phase) is returned
+ * mip_cull_clusters, mip_list_clusters, mip_list_clusters_phase, mip_cull_clusters_views, mip_list_clusters_views or mip_list_clusters_views_occluded (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase or mip_list_clusters_phase) is returned
  * when there is no other error to return; otherwise by the mip_wait after. */
 int32_t mip_wait(MipContext* ctx);
 

@@ -138,6 +138,21 @@ int main(void) {
   list_views.entry_counts = &count;
   ok = ok && mip_list_clusters_views(ctx, &frame, view_bitmaps, 1, &policy, &list_views) == MIP_ERR_INVALID_ARGUMENT &&
        mip_instance_count(ctx) == N;
+  /* ... and with a depth pyramid per view (extension): `occs` is a host array of n_views host pointers, NULL for a view that
+   * is tested against its planes alone; V pyramids built with mip_build_depth_pyramid need no wait in front of
+   *     MipClusterViewOccludedListOutputs lo = { sizeof lo, MIP_OUT_DEVICE | MIP_OUT_ASYNC, entries, entry_stride, 0, entry_counts, draw_args, NULL, hidden };
+   *     mip_list_clusters_views_occluded(ctx, frames, bitmaps_dev, occs, n_views, &policy, &lo);
+   * Here: the struct and the entry point link from C, and host pointers are refused without harming the context. */
+  MipClusterViewOccludedListOutputs list_occluded;
+  const MipOcclusion* view_occs[1] = {NULL};
+  memset(&list_occluded, 0, sizeof list_occluded);
+  list_occluded.struct_size = sizeof list_occluded;
+  list_occluded.flags = MIP_OUT_HOST;
+  list_occluded.cluster_entries = cmds;
+  list_occluded.entry_stride = 1;
+  list_occluded.entry_counts = &count;
+  ok = ok && mip_list_clusters_views_occluded(ctx, &frame, view_bitmaps, view_occs, 1, &policy, &list_occluded) == MIP_ERR_INVALID_ARGUMENT &&
+       mip_instance_count(ctx) == N;
   printf("C_SMOKE %s instances=%d visible=%u commands=%u index_total=%u checksum=%08x\n", ok ? "OK" : "BAD", N, visible, count,
          index_total, sum);
   mip_destroy(ctx);

@@ -269,6 +269,21 @@ pub struct MipClusterViewListOutputs {
     pub stats: *mut u32,
 }
 
+/// Outputs of mip_list_clusters_views_occluded: MipClusterViewListOutputs' fields and `hidden`, optional, n_views words: per
+/// view the work items that passed the view's planes and are occluded under the view's pyramid (see the header).
+#[repr(C)]
+pub struct MipClusterViewOccludedListOutputs {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub cluster_entries: *mut c_void,
+    pub entry_stride: u32,
+    pub work_capacity: u32,
+    pub entry_counts: *mut u32,
+    pub draw_args: *mut u32,
+    pub stats: *mut u32,
+    pub hidden: *mut u32,
+}
+
 /// Outputs of mip_list_clusters_phase: mip_list_clusters' list in two phases. The list starts at entry *entry_base, read on
 /// the device (null: 0) — SECOND appends behind FIRST with entry_base = FIRST's entry_count; stats has four words (see the header).
 #[repr(C)]
@@ -404,6 +419,11 @@ extern "C" {
     /// the located work item and three of the four entry fields shared by all views; on the first stream.
     pub fn mip_list_clusters_views(ctx: *mut MipContext, frames: *const MipFrame, visible_bitmaps: *const *const u32,
                                    n_views: u32, policy: *const MipLodPolicy, out: *const MipClusterViewListOutputs) -> i32;
+    /// mip_list_clusters_views with a depth pyramid per view: `occs` is a host array of n_views host pointers, null for a view
+    /// that is tested against its planes alone; on the first stream, behind pyramids built for the next run.
+    pub fn mip_list_clusters_views_occluded(ctx: *mut MipContext, frames: *const MipFrame, visible_bitmaps: *const *const u32,
+                                            occs: *const *const MipOcclusion, n_views: u32, policy: *const MipLodPolicy,
+                                            out: *const MipClusterViewOccludedListOutputs) -> i32;
     /// mip_cull_clusters_phase with mip_list_clusters' entries in the commands' place: FIRST lists the survivors and writes the
     /// record, SECOND lists the recorded clusters visible under the new pyramid, from entry *out.entry_base on.
     pub fn mip_list_clusters_phase(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
@@ -433,6 +453,7 @@ const _: [u8; 16] = [0; std::mem::size_of::<MipClusterEntry>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipClusterListOutputs>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipClusterViewListOutputs>()];
 const _: [u8; 56] = [0; std::mem::size_of::<MipClusterPhaseListOutputs>()];
+const _: [u8; 56] = [0; std::mem::size_of::<MipClusterViewOccludedListOutputs>()];
 const _: [u8; 104] = [0; std::mem::size_of::<MipOcclusion>()];
 
 impl Pipeline {

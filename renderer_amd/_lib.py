@@ -61,6 +61,7 @@ EXPORTS = (
     "mip_cluster_record_bytes", "mip_cull_clusters_phase", "mip_cull_cluster_triangles",
     "mip_build_cluster_cones", "mip_read_cluster_cones", "mip_cone_from_pv", "mip_cull_clusters_cone", "mip_cull_cluster_triangles_cone",
     "mip_cull_clusters_views", "mip_list_clusters", "mip_list_clusters_views", "mip_list_clusters_phase",
+    "mip_list_clusters_views_occluded",
 )
 
 
@@ -242,6 +243,22 @@ class MipClusterViewListOutputs(C.Structure):
         ("entry_counts", C.c_void_p),
         ("draw_args", C.c_void_p),
         ("stats", C.c_void_p),
+    ]
+
+
+class MipClusterViewOccludedListOutputs(C.Structure):
+    """mip_list_clusters_views_occluded's outputs (include/mi_instance_pipeline.h): MipClusterViewListOutputs' fields and the
+    optional n_views words of `hidden`, 56 B."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("cluster_entries", C.c_void_p),
+        ("entry_stride", C.c_uint32),
+        ("work_capacity", C.c_uint32),
+        ("entry_counts", C.c_void_p),
+        ("draw_args", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("hidden", C.c_void_p),
     ]
 
 
@@ -446,6 +463,7 @@ def load_library():
     _declare_newer(lib, "mip_list_clusters", [vp, vp, vp, vp, vp, vp, vp])
     _declare_newer(lib, "mip_list_clusters_views", [vp, vp, vp, C.c_uint32, vp, vp])
     _declare_newer(lib, "mip_list_clusters_phase", [vp, vp, vp, vp, vp, vp, vp])
+    _declare_newer(lib, "mip_list_clusters_views_occluded", [vp, vp, vp, vp, C.c_uint32, vp, vp])
     lib.mip_instance_count.argtypes = [vp]
     lib.mip_instance_count.restype = C.c_uint32
     _lib = lib

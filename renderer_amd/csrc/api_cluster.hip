@@ -16,6 +16,8 @@
 // same stream, scratch and status words (cluster_views_list_kernel.hpp, cluster_views_list_plan.hpp: three new kernels).
 // mip_list_clusters_phase is mip_cull_clusters_phase with the list's entries in the commands' place, the list started at an entry
 // base read on the device (cluster_list_phase_kernel.hpp, cluster_list_phase_plan.hpp: the front and the list tail of its own).
+// mip_list_clusters_views_occluded is mip_list_clusters_views with a depth pyramid per view: one new kernel in the several-view
+// cull kernel's place (cluster_views_occluded_kernel.hpp), the same plan, stream, scratch and status words.
 // cluster_plan.hpp, cluster_triangle_plan.hpp and cluster_cone_plan.hpp hold the arithmetic and the launch plans; the kernels
 // (cluster_kernel.hpp, cluster_triangle_kernel.hpp, cluster_cone_kernel.hpp) are instantiated here and only here.
 #include "context.hpp"
@@ -26,6 +28,7 @@
 #include "cluster_list_kernel.hpp"
 #include "cluster_views_list_kernel.hpp"
 #include "cluster_list_phase_kernel.hpp"
+#include "cluster_views_occluded_kernel.hpp"
 
 static_assert(sizeof(MipClusterViewOutputs) == 40, "MipClusterViewOutputs is part of the ABI");
 static_assert(sizeof(MipClusterOutputs) == 40, "MipClusterOutputs is part of the ABI");
@@ -36,6 +39,7 @@ static_assert(sizeof(MipClusterEntry) == 16 && sizeof(MipClusterEntry) == sizeof
 static_assert(sizeof(MipClusterListOutputs) == 48, "MipClusterListOutputs is part of the ABI");
 static_assert(sizeof(MipClusterViewListOutputs) == 48, "MipClusterViewListOutputs is part of the ABI");
 static_assert(sizeof(MipClusterPhaseListOutputs) == 56, "MipClusterPhaseListOutputs is part of the ABI");
+static_assert(sizeof(MipClusterViewOccludedListOutputs) == 56, "MipClusterViewOccludedListOutputs is part of the ABI");
 static_assert(sizeof(mip::ClusterConeEntry) == 2 * sizeof(float4), "a cone is the two 16-byte words the kernels load");
 static_assert(mip::kClusterFirst == MIP_CLUSTER_PHASE_FIRST && mip::kClusterSecond == MIP_CLUSTER_PHASE_SECOND, "cluster_kernel.hpp restates the header");
 static_assert(MIP_CLUSTER_TRIANGLES == mip::kClusterTriangles, "cluster_plan.hpp restates the header");
@@ -904,6 +908,186 @@ int32_t list_clusters_phase(MipContext* ctx, const MipFrame* frame, const uint32
   return MIP_OK;
 }
 
+// ---- mip_list_clusters_views_occluded ----
+
+// Every check first (a refused call writes nothing), then the eight launches of mip_list_clusters_views' plan on the context's
+// first stream with mip_cluster_views_cull_occluded_packed_kernel (or, MIP_TUNE_VIEWS_OCCLUDED_PACKED=0, the simple loop of
+// mip_cluster_views_cull_occluded_kernel) in the cull kernel's place (with no pyramid in any view the plain
+// cull kernel stays: the same words, more waves per SIMD), behind a memset of `hidden`. The
+// argument block is filled here as list_clusters_views fills its own — duplicated, so that call stays as it is.
+int32_t list_clusters_views_occluded(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps, const MipOcclusion* const* occs,
+                                     uint32_t n_views, const MipLodPolicy* policy, const MipClusterViewOccludedListOutputs* out) {
+  if (!frames || !visible_bitmaps || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frames/visible_bitmaps/out is NULL");
+  if (!occs) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "occs is NULL (for no pyramid at all pass an array of NULLs, or call mip_list_clusters_views)");
+  if (out->struct_size != sizeof(MipClusterViewOccludedListOutputs))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterViewOccludedListOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipClusterViewOccludedListOutputs));
+  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipClusterViewOccludedListOutputs flags 0x%x", out->flags);
+  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_list_clusters_views_occluded needs MIP_OUT_DEVICE outputs");
+  if (!out->cluster_entries || !out->entry_counts) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cluster_entries/entry_counts is NULL");
+  if ((uintptr_t)out->cluster_entries % 16u != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cluster_entries is not 16-byte aligned");
+  if ((uintptr_t)out->entry_counts % 4u != 0u || (uintptr_t)out->draw_args % 4u != 0u || (uintptr_t)out->stats % 4u != 0u || (uintptr_t)out->hidden % 4u != 0u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "entry_counts, draw_args, stats or hidden is not 4-byte aligned");
+  if (n_views == 0 || n_views > MIP_MAX_VIEWS) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "n_views %u outside 1..%u", n_views, (unsigned)MIP_MAX_VIEWS);
+  if (!mip::cluster_views_list_fits(n_views, out->entry_stride))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "n_views %u x entry_stride %u >= 2^32: the last view's firstInstance would not fit", n_views, out->entry_stride);
+  if (out->hidden)  // either range's first word inside the other: the memset of one would clear words of the other
+    for (uint32_t k = 0; k < 3; ++k) {
+      const uint32_t* other = k == 0 ? out->stats : k == 1 ? out->draw_args : out->entry_counts;
+      const uint32_t words = k == 0 ? 2u + n_views : k == 1 ? 4u * n_views : n_views;
+      if (inside_words(out->hidden, other, words) || inside_words(other, out->hidden, n_views))
+        return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "hidden lies inside this call's stats, draw_args or entry_counts");
+    }
+  bool any_pyramid = false;
+  for (uint32_t v = 0; v < n_views; ++v) {
+    const MipOcclusion* occ = occs[v];
+    if (!occ) continue;
+    any_pyramid = true;
+    if (occ->struct_size != sizeof(MipOcclusion))
+      return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "view %u: MipOcclusion.struct_size %u != %zu", v, occ->struct_size, sizeof(MipOcclusion));
+    if (occ->width < 1u || occ->height < 1u || occ->width > MIP_MAX_DEPTH_EXTENT || occ->height > MIP_MAX_DEPTH_EXTENT)
+      return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "view %u: depth extent %ux%u outside 1..%u", v, occ->width, occ->height, (unsigned)MIP_MAX_DEPTH_EXTENT);
+    if (!occ->pyramid) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "view %u: pyramid is NULL", v);
+    if (occ->flags || occ->candidates || occ->occluded_bitmap)
+      return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "view %u: mip_list_clusters_views_occluded takes no MipOcclusion flags, candidates or occluded_bitmap", v);
+  }
+  if (!ctx->have_instances || !ctx->have_meshes) return fail(ctx, MIP_ERR_NOT_READY, "instances or mesh table not set");
+  if (!ctx->clusters.valid) return fail(ctx, MIP_ERR_NOT_READY, "no cluster table, or the mesh table / geometry changed since mip_build_clusters");
+  if (int32_t rc = bind_device(ctx)) return rc;
+
+  hipStream_t stream = ctx->stream;
+  const bool async = (out->flags & MIP_OUT_ASYNC) != 0;
+  const uint32_t n = ctx->n;
+  if (out->hidden) MIP_HIP(ctx, hipMemsetAsync(out->hidden, 0, (size_t)n_views * 4, stream));  // the cull kernel adds to it; N = 0 and a work overflow leave the zeros
+  if (n == 0) {  // nothing to test: zero counts, {192, 0, 0, v x entry_stride} per view, zero stats
+    MIP_HIP(ctx, hipMemsetAsync(out->entry_counts, 0, (size_t)n_views * 4, stream));
+    if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, (2 + (size_t)n_views) * 4, stream));
+    if (out->draw_args) {
+      MIP_HIP(ctx, hipMemsetAsync(out->draw_args, 0, (size_t)n_views * 16, stream));
+      for (uint32_t v = 0; v < n_views; ++v) {
+        MIP_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out->draw_args + 4u * v), (int)mip::kClusterListDrawVertices, 1, stream));
+        MIP_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out->draw_args + 4u * v + 3u),
+                                       (int)(uint32_t)mip::cluster_views_list_first(v, out->entry_stride), 1, stream));
+      }
+    }
+    return finish(ctx, stream, async);
+  }
+  if (!ctx->h_cluster_views_status) {  // the pair the several-view calls share
+    MIP_HIP(ctx, hipHostMalloc(&ctx->h_cluster_views_status, 2 * 4, hipHostMallocMapped));
+    std::memset(ctx->h_cluster_views_status, 0, 2 * 4);
+  }
+  const MipContext::ClusterTable& table = ctx->clusters;
+  const unsigned long long bound = mip::cluster_work_bound(n, table.max_clusters, out->work_capacity);
+  const mip::ClusterViewsListPlan plan = mip::plan_cluster_views_list(n, bound, n_views);
+  MipContext::ClusterViewScratch& vs = ctx->cluster_views;
+  if (int32_t rc = ensure_views_scratch(ctx, vs, plan.front)) return rc;
+  if (int32_t rc = ensure_views_list_scratch(ctx, vs, plan)) return rc;
+  if (any_pyramid && ctx->slots[ctx->next_slot].stream != stream) {
+    // a pyramid built for the next run sits on that slot's stream: this call goes behind what that stream holds now
+    if (!ctx->cluster_pyramid_ready) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_pyramid_ready, hipEventDisableTiming));
+    MIP_HIP(ctx, hipEventRecord(ctx->cluster_pyramid_ready, ctx->slots[ctx->next_slot].stream));
+    MIP_HIP(ctx, hipStreamWaitEvent(stream, ctx->cluster_pyramid_ready, 0));
+  }
+
+  mip::ClusterViewsListArgs la{};
+  mip::ClusterViewArgs& va = la.v;
+  mip::ClusterArgs& a = va.c;
+  a.lods.chain = ctx->d_mesh_chain;
+  a.lods.bucket_lod = ctx->d_bucket_lod;
+  std::memcpy(a.lods.switch_sq, policy->switch_sq, sizeof a.lods.switch_sq);
+  a.lods.pos = ctx->d_pos; a.lods.rot = ctx->d_rot; a.lods.scale = ctx->d_scale; a.lods.mesh_id = ctx->d_mesh_id;
+  a.lods.meshes = ctx->d_meshes; a.lods.mesh_draw = ctx->d_mesh_draw;
+  a.lods.n = n;
+  a.lods.n_tiles = plan.front.one.instance_tiles;
+  a.lods.n_buckets = (uint32_t)ctx->lod_buckets;
+  std::memcpy(a.lods.cam, frames[0].cam_pos, sizeof a.lods.cam);  // one level for all views
+  a.cluster_base = table.d_cluster_base;
+  a.boxes = table.d_boxes;
+  a.bound = bound;
+  const size_t cap = instance_cap(ctx);
+  a.items = vs.d_instances;
+  a.bucket = vs.d_instances + cap;
+  a.member_inst = vs.d_instances + 2 * cap;
+  a.member_first = vs.d_instances + 3 * cap;  // cap + 1 words
+  a.tile_items = vs.d_tile_items;
+  a.tile_members = vs.d_tile_members;
+  a.scalars = vs.d_scalars;
+  va.n_views = n_views;
+  va.head_tiles = plan.front.one.head_tiles;
+  va.words_stride = plan.front.one.survive_words;
+  va.view_words = vs.d_view_words;
+  va.view_mask = vs.d_view_mask;
+  for (uint32_t v = 0; v < n_views; ++v) {
+    va.view_bitmap[v] = visible_bitmaps[v];
+    va.view_base[v] = frames[v].first_instance_base;
+    std::memcpy(va.view_planes[v], frames[v].planes, sizeof va.view_planes[v]);
+  }
+  la.word_member = vs.d_word_member;
+  la.word_rank = vs.d_word_rank;
+  la.list_tiles = vs.d_list_tiles;
+  la.rank_stride = plan.list.words;
+  la.tile_stride = plan.list.list_tiles;
+  la.entries = static_cast<uint4*>(out->cluster_entries);
+  la.entry_stride = out->entry_stride;
+  la.entry_counts = out->entry_counts;
+  la.draw_args = out->draw_args;
+  la.list_stats = out->stats;
+  volatile uint32_t* status = ctx->h_cluster_views_status + (async ? 0u : 1u);
+  MIP_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&a.status), const_cast<uint32_t*>(status), 0));
+  if (!async) *status = 0;  // (no synchronous several-view call is in flight: each one drains the stream)
+#ifdef MIP_DEBUG_STAMPS
+  const DebugSwitches sw;
+  sw.tile_order(a.lods.n_tiles, a.lods.debug_tile_mult, a.lods.debug_tile_add);
+  a.debug_order = sw.reverse() ? mip::kClusterOrderReverse
+                  : (sw.order && std::strcmp(sw.order, "scramble") == 0) ? mip::kClusterOrderScramble : mip::kClusterOrderNone;
+#endif
+  mip::ClusterListArgs wa{};  // the word-member kernel's: it reads the leading block and writes word_member
+  wa.c = a;
+  wa.word_member = vs.d_word_member;
+  mip::ClusterViewOccludedArgs oa{};  // the cull kernel's: the front's block, then a pyramid per view
+  oa.v = va;
+  for (uint32_t v = 0; v < n_views; ++v)
+    if (const MipOcclusion* occ = occs[v]) {
+      std::memcpy(oa.occ[v].pv, occ->pv, sizeof oa.occ[v].pv);
+      oa.occ[v].pyramid = static_cast<const float*>(occ->pyramid);
+      oa.occ[v].width = occ->width;
+      oa.occ[v].height = occ->height;
+    }
+  oa.hidden = out->hidden;
+  const bool relative = policy->mode == MIP_LOD_RELATIVE;
+  const char* tune = std::getenv("MIP_TUNE_VIEWS_OCCLUDED_PACKED");  // A/B and tests: 0 = the simple loop; the packed cull kernel is the default
+  const bool packed = tune ? std::atoi(tune) != 0 : true;
+  const bool always = std::getenv("MIP_TUNE_VIEWS_OCCLUDED_ALWAYS") != nullptr;  // A/B and tests: the occluded kernel even when no view has a pyramid
+  for (const mip::ClusterViewsListLaunch& l : plan.launches) {
+    int32_t rc = MIP_OK;
+    switch (l.kernel) {
+      case mip::ClusterViewsListKernel::count:
+        rc = relative ? launch_grid(ctx, mip::mip_cluster_views_count_kernel<MIP_LOD_RELATIVE>, l.blocks_x, l.blocks_y, stream, va)
+                      : launch_grid(ctx, mip::mip_cluster_views_count_kernel<MIP_LOD_DISTANCE>, l.blocks_x, l.blocks_y, stream, va);
+        break;
+      case mip::ClusterViewsListKernel::scan: rc = launch(ctx, mip::mip_cluster_scan_kernel<mip::kClusterPlain>, l.blocks_x, stream, a); break;
+      case mip::ClusterViewsListKernel::members: rc = launch(ctx, mip::mip_cluster_members_kernel, l.blocks_x, stream, a); break;
+      // no pyramid in any view: the plain several-view cull writes the same words (hidden stays the memset's zeros) at five
+      // waves per SIMD where the packed kernel holds four and the simple loop three (DESIGN section 36 has the three measured)
+      case mip::ClusterViewsListKernel::cull:
+        rc = !any_pyramid && !always ? launch_grid(ctx, mip::mip_cluster_views_cull_kernel, l.blocks_x, l.blocks_y, stream, va)
+             : packed     ? launch_grid(ctx, mip::mip_cluster_views_cull_occluded_packed_kernel, l.blocks_x, l.blocks_y, stream, oa)
+                          : launch_grid(ctx, mip::mip_cluster_views_cull_occluded_kernel, l.blocks_x, l.blocks_y, stream, oa);
+        break;
+      case mip::ClusterViewsListKernel::word_members: rc = launch(ctx, mip::mip_cluster_list_word_members_kernel, l.blocks_x, stream, wa); break;
+      case mip::ClusterViewsListKernel::list_count: rc = launch_grid(ctx, mip::mip_cluster_views_list_count_kernel, l.blocks_x, l.blocks_y, stream, la); break;
+      case mip::ClusterViewsListKernel::list_epilogue: rc = launch_grid(ctx, mip::mip_cluster_views_list_epilogue_kernel, l.blocks_x, l.blocks_y, stream, la); break;
+      case mip::ClusterViewsListKernel::list_write: rc = launch_grid(ctx, mip::mip_cluster_views_list_write_kernel, l.blocks_x, l.blocks_y, stream, la); break;
+    }
+    if (rc) return rc;
+  }
+  if (int32_t rc = finish(ctx, stream, async)) return rc;
+  if (!async && *status) {  // this call's own word, and its stream has drained
+    *status = 0;
+    return fail(ctx, MIP_ERR_CAPACITY, "mip_list_clusters_views_occluded: a view has more surviving clusters than entry_stride (its first entry_stride entries are written, the other views are complete), or more work items than work_capacity / 2^32 - 1 (nothing is written); stats holds the counts");
+  }
+  return MIP_OK;
+}
+
 }  // namespace
 
 // mip_wait, after every stream has drained. An overflow of an asynchronous call is reported when nothing else is: while `rc`
@@ -916,13 +1100,13 @@ int32_t cluster_wait_status(MipContext* ctx, int32_t rc) {
       raised |= ((volatile uint32_t*)ctx->h_cluster_status)[k];
       ((volatile uint32_t*)ctx->h_cluster_status)[k] = 0;
     }
-  if (ctx->h_cluster_views_status) {  // mip_cull_clusters_views' and mip_list_clusters_views' asynchronous word
+  if (ctx->h_cluster_views_status) {  // the several-view calls' asynchronous word
     raised |= ((volatile uint32_t*)ctx->h_cluster_views_status)[0];
     ((volatile uint32_t*)ctx->h_cluster_views_status)[0] = 0;
   }
   if (!raised) return MIP_OK;
   if (raised & mip::kClusterStatusDevice) return fail(ctx, MIP_ERR_DEVICE, "asynchronous %s", kNotItsRecord);
-  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters, mip_list_clusters, mip_list_clusters_phase, mip_cull_clusters_views or mip_list_clusters_views had more runs than cmd_capacity (more surviving clusters than entry_capacity / entry_stride / the room behind entry_base), or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
+  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters, mip_list_clusters, mip_list_clusters_phase, mip_cull_clusters_views, mip_list_clusters_views or mip_list_clusters_views_occluded had more runs than cmd_capacity (more surviving clusters than entry_capacity / entry_stride / the room behind entry_base), or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
 }
 
 void cluster_release(MipContext* ctx) {
@@ -1064,6 +1248,14 @@ int32_t mip_list_clusters_views(MipContext* ctx, const MipFrame* frames, const u
   if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
   if (int32_t rc = check_policy(ctx, policy)) return rc;
   return list_clusters_views(ctx, frames, visible_bitmaps, n_views, policy, out);
+}
+
+int32_t mip_list_clusters_views_occluded(MipContext* ctx, const MipFrame* frames, const uint32_t* const* visible_bitmaps,
+                                         const MipOcclusion* const* occs, uint32_t n_views, const MipLodPolicy* policy,
+                                         const MipClusterViewOccludedListOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  return list_clusters_views_occluded(ctx, frames, visible_bitmaps, occs, n_views, policy, out);
 }
 
 // mip_list_clusters: the checks of its own fields, then the call it shares with mip_cull_clusters / mip_cull_clusters_cone

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterListOutputs, MipClusterOutputs, MipClusterPhaseListOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipClusterViewListOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterListOutputs, MipClusterOutputs, MipClusterPhaseListOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipClusterViewListOutputs, MipClusterViewOccludedListOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
                    MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
@@ -227,6 +227,23 @@ def make_cluster_view_list_outputs(cluster_entries, entry_stride, entry_counts, 
     o.entry_counts = entry_counts or None
     o.draw_args = draw_args or None
     o.stats = stats or None
+    return o
+
+
+def make_cluster_view_occluded_list_outputs(cluster_entries, entry_stride, entry_counts, draw_args=0, stats=0, hidden=0, work_capacity=0, async_=False):
+    """A MipClusterViewOccludedListOutputs for list_clusters_views_occluded: make_cluster_view_list_outputs' fields and
+    (optional) a device pointer to the n_views words of `hidden`: per view the work items that passed the view's planes and are
+    occluded under the view's pyramid."""
+    o = MipClusterViewOccludedListOutputs()
+    o.struct_size = C.sizeof(MipClusterViewOccludedListOutputs)
+    o.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+    o.cluster_entries = cluster_entries or None
+    o.entry_stride = int(entry_stride)
+    o.work_capacity = int(work_capacity)
+    o.entry_counts = entry_counts or None
+    o.draw_args = draw_args or None
+    o.stats = stats or None
+    o.hidden = hidden or None
     return o
 
 
@@ -851,6 +868,24 @@ class InstancePipeline:
             C.memmove(C.addressof(fr[v]), C.addressof(frames[v]), C.sizeof(MipFrame))
         bm = (C.c_void_p * max(k, 1))(*[int(b) if b else None for b in visible_bitmap_ptrs])
         self._check(self._lib.mip_list_clusters_views(self._ctx, C.addressof(fr), C.addressof(bm), k, C.addressof(policy), C.addressof(outputs)))
+
+    def list_clusters_views_occluded(self, frames, visible_bitmap_ptrs, occlusions, policy, outputs):
+        """mip_list_clusters_views_occluded: list_clusters_views with a depth pyramid per view. occlusions[v] is a
+        make_occlusion(...) (pyramid, extents and pv are read; no candidates, no occluded bitmap, no flags) or None: view v is
+        then tested against its planes alone. View v's list is what list_clusters(frames[v] with frames[0]'s cam_pos, ...,
+        occlusion=occlusions[v]) writes; `hidden` of `outputs` (make_cluster_view_occluded_list_outputs) counts per view the
+        work items that passed the planes and are occluded. Enqueued on the context's first stream, behind a run_views and
+        behind pyramids built for the next run: no wait is needed. MIP_ERR_CAPACITY as for list_clusters_views."""
+        k = len(frames)
+        if len(visible_bitmap_ptrs) != k or len(occlusions) != k:
+            raise ValueError("one bitmap pointer (or None) and one occlusion (or None) per frame")
+        fr = (MipFrame * max(k, 1))()
+        for v in range(k):
+            C.memmove(C.addressof(fr[v]), C.addressof(frames[v]), C.sizeof(MipFrame))
+        bm = (C.c_void_p * max(k, 1))(*[int(b) if b else None for b in visible_bitmap_ptrs])
+        oc = (C.c_void_p * max(k, 1))(*[C.addressof(o) if o is not None else None for o in occlusions])
+        self._check(self._lib.mip_list_clusters_views_occluded(self._ctx, C.addressof(fr), C.addressof(bm), C.addressof(oc), k, C.addressof(policy),
+                                                               C.addressof(outputs)))
 
     def list_clusters_phase(self, frame, visible_bitmap_ptr, policy, outputs, occlusion, record):
         """mip_list_clusters_phase: cull_clusters_phase with list_clusters' flat list in the commands' place. With a FIRST
