@@ -926,8 +926,8 @@ int32_t mip_cull_clusters_phase(MipContext* ctx, const MipFrame* frame, const ui
  * are MIP_ERR_INVALID_ARGUMENT.
  * ORDERING and scratch are mip_cull_clusters'; the scratch per frame slot is 12 bytes per work item of the bound larger (a
  * triangle word and a prefix per item) — 110 MB at 9.1 M items — so, again, a scene of large meshes should set work_capacity.
- * OUT OF SCOPE: the two-phase record; views, shards and skinned instances; mip_run_many and recorded graphs; dropping empty
- * commands; first_index_base. */
+ * OUT OF SCOPE: the two-phase record; views, shards and skinned instances; mip_run_many and recorded graphs; first_index_base.
+ * Dropping empty runs is mip_list_cluster_triangles' (below): the list form with a triangle mask per entry and no stream. */
 typedef struct MipClusterTriangleOutputs {
   uint32_t struct_size;      /* = sizeof(MipClusterTriangleOutputs) */
   uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
@@ -1053,7 +1053,7 @@ int32_t mip_cull_cluster_triangles_cone(MipContext* ctx, const MipFrame* frame, 
  * need no wait. Scratch is the call's own, allocated at first use and grown by a larger call: (1 + n_views) x 8 bytes per 64
  * work items of the bound plus 2 bytes per instance, beside the per-instance lists. No frame slot's cluster scratch is
  * touched: a cluster call behind a frame slot and this call do not disturb each other.
- * OUT OF SCOPE: a pyramid per view (mip_list_clusters_views_occluded below); the two phases; the per-triangle stream; cones; shards; skinned instances; mip_run_many
+ * OUT OF SCOPE: a pyramid per view (mip_list_clusters_views_occluded below); the two phases; the per-triangle test (one view: mip_list_cluster_triangles below); cones; shards; skinned instances; mip_run_many
  * and recorded graphs. */
 typedef struct MipClusterViewOutputs {
   uint32_t struct_size;      /* = sizeof(MipClusterViewOutputs) */
@@ -1107,8 +1107,8 @@ int32_t mip_cull_clusters_views(MipContext* ctx, const MipFrame* frames, const u
  *                                         model = models[e.instance - first_instance_base]; ... }   // (the subtraction wraps as the sum did)
  *   else gl_Position = vec4(0);   // a degenerate vertex: the triangles of a short last cluster's tail have no area
  * OUT OF SCOPE: the two-phase record and an entry base (mip_list_clusters_phase below); several views in THIS call (mip_list_clusters_views below;
- * commands per view: mip_cull_clusters_views); the per-triangle test
- * (mip_cull_cluster_triangles); shards, skinned instances, mip_run_many and recorded graphs. */
+ * commands per view: mip_cull_clusters_views); the per-triangle test (on this list: mip_list_cluster_triangles below; as an
+ * index stream with commands: mip_cull_cluster_triangles); shards, skinned instances, mip_run_many and recorded graphs. */
 typedef struct MipClusterEntry {
   uint32_t instance;         /* first_instance_base + i (wraps as firstInstance does) */
   uint32_t first_index;      /* index_offset[lod] + 192 x c: the source mesh's own range */
@@ -1169,7 +1169,7 @@ int32_t mip_list_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t
  * ORDERING: enqueued on the context's first stream, as mip_run_views and mip_cull_clusters_views are. Scratch is the
  * several-view call's own, grown by this call: on top of mip_cull_clusters_views' planes, (1 + n_views) x 4 bytes per 64 work
  * items of the bound. Both several-view calls run on the one stream, so sharing the scratch is ordered.
- * OUT OF SCOPE: a pyramid per view (mip_list_clusters_views_occluded below); cones; the two phases; the per-triangle stream; one list packed tightly over all views;
+ * OUT OF SCOPE: a pyramid per view (mip_list_clusters_views_occluded below); cones; the two phases; the per-triangle test (one view: mip_list_cluster_triangles below); one list packed tightly over all views;
  * shards; skinned instances; mip_run_many and recorded graphs. */
 typedef struct MipClusterViewListOutputs {
   uint32_t struct_size;      /* = sizeof(MipClusterViewListOutputs) */
@@ -1231,7 +1231,7 @@ int32_t mip_list_clusters_views(MipContext* ctx, const MipFrame* frames, const u
  * call goes behind what that stream holds now (an event recorded there, waited for on the device): V pyramids built with
  * mip_build_depth_pyramid (asynchronous) need no mip_wait in front of this call. Scratch is the several-view scratch,
  * unchanged in size: no new plane.
- * OUT OF SCOPE: commands per view under a pyramid; a two-phase record per view; cones; the per-triangle stream; shards;
+ * OUT OF SCOPE: commands per view under a pyramid; a two-phase record per view; cones; the per-triangle test (one view: mip_list_cluster_triangles below); shards;
  * skinned instances; mip_run_many and recorded graphs. */
 typedef struct MipClusterViewOccludedListOutputs {
   uint32_t struct_size;      /* = sizeof(MipClusterViewOccludedListOutputs) */
@@ -1294,8 +1294,8 @@ int32_t mip_list_clusters_views_occluded(MipContext* ctx, const MipFrame* frames
  * its bitmap with entry_base = NULL; (2) draw FIRST's list, rebuild the pyramid; (3) mip_run_occluded with the inverted
  * candidates, then plain mip_list_clusters over ITS bitmap under the new pyramid into a buffer of its own; (4) SECOND over
  * phase 1's bitmap with entry_base = FIRST's entry_count into FIRST's buffer: one more indirect draw from SECOND's draw_args.
- * OUT OF SCOPE: cones, several views, shards, skinned instances, the per-triangle stream, mip_run_many and recorded graphs, and
- * an entry_base for mip_list_clusters. */
+ * OUT OF SCOPE: cones, several views, shards, skinned instances, the per-triangle test (one phase: mip_list_cluster_triangles below), mip_run_many and
+ * recorded graphs, and an entry_base for mip_list_clusters. */
 typedef struct MipClusterPhaseListOutputs {
   uint32_t struct_size;       /* = sizeof(MipClusterPhaseListOutputs) */
   uint32_t flags;             /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
@@ -1311,11 +1311,69 @@ typedef struct MipClusterPhaseListOutputs {
 int32_t mip_list_clusters_phase(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
                                 const MipOcclusion* occ, const MipClusterPhaseListOutputs* out, const MipClusterRecord* rec);
 
+/* ---- Extension: per-triangle masks on the visible-cluster list -------------------------------------------------------------
+ * mip_cull_cluster_triangles ends in a dense index stream and commands into it; a consumer of mip_list_clusters' list draws
+ * with entries[gl_InstanceIndex] and pulls its own indices, so it wants no stream: it wants, per entry, the 64 bits that say
+ * which of the cluster's triangles to emit, and no entry for a cluster that keeps none. mip_list_cluster_triangles is
+ * mip_list_clusters with the per-triangle stage's test behind SURVIVES: one MipClusterEntry per surviving work item that keeps a
+ * triangle, and beside it one 64-bit TRIANGLE MASK. NOT a reference behaviour; checked against this repository's restatement
+ * (tests/cluster_triangle_list_restatement.py) only. Every entry point above is unchanged.
+ *
+ * MEMBERS, WORK ITEMS, W and SURVIVES are mip_list_clusters' for the same frame, visible_bitmap, policy, occ and cone: the
+ * planes, and the pyramid when occ is given; the cone test in front when cone is given.
+ * TRI_SURVIVES(i, c, t) is that of mip_cull_cluster_triangles above, unchanged: formed on the matrix mip_run writes for instance
+ * i, which the call builds from the instance columns, under frame->pv, the chain with no FMA contraction.
+ * MASKS: MASK(i, c) has bit t set iff t is below the triangle count of cluster c (64, or fewer in the last cluster of a level)
+ * and TRI_SURVIVES(i, c, t). Bits at or above the triangle count are zero.
+ * ENTRIES: one per work item with SURVIVES and MASK != 0, in (i, c) order, packed from entry 0. The four fields are exactly
+ * mip_list_clusters' fields, so the entries are a subsequence of that call's list for the same arguments. triangle_masks[k] is
+ * the MASK of entry k. entry_count = min(entries, entry_capacity); nothing at or behind entry_count is touched in either array.
+ * draw_args (optional, 4 words): VkDrawIndirectCommand {vertexCount = 192, instanceCount = entry_count, 0, 0}.
+ * stats (optional, 6 words): {entries, surviving clusters, W, members, surviving triangles, triangles tested}; words 1 to 5 are
+ * those of mip_cull_cluster_triangles (with a cone: mip_cull_cluster_triangles_cone) for the same arguments — tested = the
+ * triangles of the surviving clusters; the last two mod 2^32.
+ * ENTRY OVERFLOW (entries > entry_capacity): the first entry_capacity entries and masks are written exactly as they would be
+ * with room, entry_count = entry_capacity and draw_args[1] holds the same value, stats holds the true six values, and the status
+ * is MIP_ERR_CAPACITY.
+ * WORK OVERFLOW, as mip_list_clusters: MIP_ERR_CAPACITY, entry_count = 0, draw_args = {192, 0, 0, 0},
+ * stats = {0, 0, W mod 2^32, members, 0, 0}; nothing else is written and the context stays usable.
+ * There is no index overflow: there is no stream. N = 0 writes a zero count, {192, 0, 0, 0} and six zero stats.
+ * Both overflows are reported as mip_cull_clusters reports (WHO REPORTS AN OVERFLOW above): the same status words, the same
+ * mip_wait route.
+ * REFUSED, nothing written: everything mip_list_clusters refuses, what it refuses about a non-NULL cone included; a NULL
+ * triangle_masks or one that is not 8-byte aligned; triangle_masks' entry_capacity x 8 bytes overlapping cluster_entries,
+ * entry_count, draw_args or stats; a wrong struct_size: MIP_ERR_INVALID_ARGUMENT. MIP_ERR_NOT_READY as for mip_list_clusters.
+ * The geometry must be resident (mip_set_geometry), as for mip_cull_cluster_triangles: the cluster table is stale without it.
+ * ORDERING and scratch are mip_cull_clusters': the stream of the frame issued last, scratch per frame slot that grows lazily —
+ * mip_list_clusters' 8 bytes per 64 work items of the bound, 8 bytes per work item (the triangle word), 8 per 64 work items
+ * (which of them are not zero) and a few words per tile — and is freed with the rest.
+ *
+ * THE CONSUMER: mip_list_clusters' draw and shader, with
+ *   uint64_t mask = triangle_masks[gl_InstanceIndex];
+ *   if (gl_VertexIndex >= e.index_count || ((mask >> (gl_VertexIndex / 3)) & 1) == 0) gl_Position = vec4(0);   // degenerate
+ * in a vertex shader; a mesh shader with one workgroup per entry emits popcount(mask) primitives, the set bits in order.
+ * OUT OF SCOPE: a per-entry triangle prefix (a dense stream reconstructed on the device: mip_cull_cluster_triangles writes the
+ * stream); the two-phase record; several views; shards; skinned instances; mip_run_many and recorded graphs. */
+typedef struct MipClusterTriangleListOutputs {
+  uint32_t struct_size;      /* = sizeof(MipClusterTriangleListOutputs) */
+  uint32_t flags;            /* MIP_OUT_DEVICE (required) | MIP_OUT_ASYNC */
+  void* cluster_entries;     /* DEVICE, 16-byte aligned: room for entry_capacity MipClusterEntry */
+  void* triangle_masks;      /* DEVICE, 8-byte aligned: room for entry_capacity uint64_t, mask k beside entry k */
+  uint32_t entry_capacity;   /* entries (and masks) that fit */
+  uint32_t work_capacity;    /* the caller's bound on W; 0 = N x the largest C of the table */
+  uint32_t* entry_count;     /* DEVICE: entries written = min(entries, entry_capacity) */
+  uint32_t* draw_args;       /* DEVICE, optional, 4 words: VkDrawIndirectCommand {192, entry_count, 0, 0} */
+  uint32_t* stats;           /* DEVICE, optional, 6 words */
+} MipClusterTriangleListOutputs; /* 56 B */
+int32_t mip_list_cluster_triangles(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                   const MipOcclusion* occ /* or NULL */, const MipClusterCone* cone /* or NULL */,
+                                   const MipClusterTriangleListOutputs* out);
+
 /* Block until everything enqueued by this context has finished; reports a
  * deferred error of an async run (MIP_ERR_CAPACITY, MIP_ERR_DEVICE, MIP_ERR_TIMEOUT of an external semaphore).
  * Frames ordered by external semaphores still need this call at a bounded cadence (e.g. every
  * frames_in_flight frames): it is where their errors surface. The MIP_ERR_CAPACITY of an asynchronous
- * mip_cull_clusters, mip_list_clusters, mip_list_clusters_phase, mip_cull_clusters_views, mip_list_clusters_views or mip_list_clusters_views_occluded (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase or mip_list_clusters_phase) is returned
+ * mip_cull_clusters, mip_list_clusters, mip_list_cluster_triangles, mip_list_clusters_phase, mip_cull_clusters_views, mip_list_clusters_views or mip_list_clusters_views_occluded (and the MIP_ERR_DEVICE of an asynchronous SECOND call of mip_cull_clusters_phase or mip_list_clusters_phase) is returned
  * when there is no other error to return; otherwise by the mip_wait after. */
 int32_t mip_wait(MipContext* ctx);
 

@@ -153,6 +153,23 @@ int main(void) {
   list_occluded.entry_counts = &count;
   ok = ok && mip_list_clusters_views_occluded(ctx, &frame, view_bitmaps, view_occs, 1, &policy, &list_occluded) == MIP_ERR_INVALID_ARGUMENT &&
        mip_instance_count(ctx) == N;
+  /* Per-triangle masks on the visible-cluster list (extension): behind a run that wrote `visible_bitmap_dev`, with no wait,
+   *     MipClusterTriangleListOutputs tl = { sizeof tl, MIP_OUT_DEVICE | MIP_OUT_ASYNC, entries, masks, entry_capacity, 0, entry_count, draw_args, NULL };
+   *     mip_list_cluster_triangles(ctx, &frame, visible_bitmap_dev, &policy, NULL, NULL, &tl);
+   * and ONE vkCmdDrawIndirect(cb, draw_args, 0, 1, 16): the shader reads entries[gl_InstanceIndex] and masks[gl_InstanceIndex]
+   * and emits the triangles whose bit is set. Here: the struct and the entry point link from C, and host pointers are refused
+   * without harming the context. */
+  MipClusterTriangleListOutputs triangle_list;
+  uint64_t mask_word = 0;
+  memset(&triangle_list, 0, sizeof triangle_list);
+  triangle_list.struct_size = sizeof triangle_list;
+  triangle_list.flags = MIP_OUT_HOST;
+  triangle_list.cluster_entries = cmds;
+  triangle_list.triangle_masks = &mask_word;
+  triangle_list.entry_capacity = 1;
+  triangle_list.entry_count = &count;
+  ok = ok && mip_list_cluster_triangles(ctx, &frame, bitmap, &policy, NULL, NULL, &triangle_list) == MIP_ERR_INVALID_ARGUMENT &&
+       mip_instance_count(ctx) == N;
   printf("C_SMOKE %s instances=%d visible=%u commands=%u index_total=%u checksum=%08x\n", ok ? "OK" : "BAD", N, visible, count,
          index_total, sum);
   mip_destroy(ctx);

@@ -255,6 +255,21 @@ pub struct MipClusterListOutputs {
     pub stats: *mut u32,
 }
 
+/// Outputs of mip_list_cluster_triangles: mip_list_clusters' list restricted to the clusters that keep a triangle, and beside
+/// entry k the 64-bit mask of its cluster's surviving triangles; six stats words (see the header).
+#[repr(C)]
+pub struct MipClusterTriangleListOutputs {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub cluster_entries: *mut c_void,
+    pub triangle_masks: *mut c_void,
+    pub entry_capacity: u32,
+    pub work_capacity: u32,
+    pub entry_count: *mut u32,
+    pub draw_args: *mut u32,
+    pub stats: *mut u32,
+}
+
 /// Outputs of mip_list_clusters_views: one list of surviving clusters and one VkDrawIndirectCommand per view, device pointers;
 /// view v's entries start at entry v x entry_stride, which is also firstInstance of its draw (see the header).
 #[repr(C)]
@@ -428,6 +443,10 @@ extern "C" {
     /// record, SECOND lists the recorded clusters visible under the new pyramid, from entry *out.entry_base on.
     pub fn mip_list_clusters_phase(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
                                    occ: *const MipOcclusion, out: *const MipClusterPhaseListOutputs, rec: *const MipClusterRecord) -> i32;
+    /// mip_list_clusters with the per-triangle test behind the cluster cull: an entry per surviving cluster that keeps a
+    /// triangle, its triangle mask beside it; no index stream, no commands, no entry for an empty cluster.
+    pub fn mip_list_cluster_triangles(ctx: *mut MipContext, frame: *const MipFrame, visible_bitmap: *const u32, policy: *const MipLodPolicy,
+                                      occ: *const MipOcclusion, cone: *const MipClusterCone, out: *const MipClusterTriangleListOutputs) -> i32;
     pub fn mip_last_error(ctx: *const MipContext) -> *const c_char;
     pub fn mip_instance_count(ctx: *const MipContext) -> u32;
 }
@@ -454,6 +473,7 @@ const _: [u8; 48] = [0; std::mem::size_of::<MipClusterListOutputs>()];
 const _: [u8; 48] = [0; std::mem::size_of::<MipClusterViewListOutputs>()];
 const _: [u8; 56] = [0; std::mem::size_of::<MipClusterPhaseListOutputs>()];
 const _: [u8; 56] = [0; std::mem::size_of::<MipClusterViewOccludedListOutputs>()];
+const _: [u8; 56] = [0; std::mem::size_of::<MipClusterTriangleListOutputs>()];
 const _: [u8; 104] = [0; std::mem::size_of::<MipOcclusion>()];
 
 impl Pipeline {

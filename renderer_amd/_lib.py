@@ -61,7 +61,7 @@ EXPORTS = (
     "mip_cluster_record_bytes", "mip_cull_clusters_phase", "mip_cull_cluster_triangles",
     "mip_build_cluster_cones", "mip_read_cluster_cones", "mip_cone_from_pv", "mip_cull_clusters_cone", "mip_cull_cluster_triangles_cone",
     "mip_cull_clusters_views", "mip_list_clusters", "mip_list_clusters_views", "mip_list_clusters_phase",
-    "mip_list_clusters_views_occluded",
+    "mip_list_clusters_views_occluded", "mip_list_cluster_triangles",
 )
 
 
@@ -223,6 +223,22 @@ class MipClusterListOutputs(C.Structure):
         ("struct_size", C.c_uint32),
         ("flags", C.c_uint32),
         ("cluster_entries", C.c_void_p),
+        ("entry_capacity", C.c_uint32),
+        ("work_capacity", C.c_uint32),
+        ("entry_count", C.c_void_p),
+        ("draw_args", C.c_void_p),
+        ("stats", C.c_void_p),
+    ]
+
+
+class MipClusterTriangleListOutputs(C.Structure):
+    """mip_list_cluster_triangles' outputs (include/mi_instance_pipeline.h): mip_list_clusters' fields with the triangle masks
+    behind the entries, six stats words, 56 B."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("cluster_entries", C.c_void_p),
+        ("triangle_masks", C.c_void_p),
         ("entry_capacity", C.c_uint32),
         ("work_capacity", C.c_uint32),
         ("entry_count", C.c_void_p),
@@ -464,6 +480,7 @@ def load_library():
     _declare_newer(lib, "mip_list_clusters_views", [vp, vp, vp, C.c_uint32, vp, vp])
     _declare_newer(lib, "mip_list_clusters_phase", [vp, vp, vp, vp, vp, vp, vp])
     _declare_newer(lib, "mip_list_clusters_views_occluded", [vp, vp, vp, vp, C.c_uint32, vp, vp])
+    _declare_newer(lib, "mip_list_cluster_triangles", [vp, vp, vp, vp, vp, vp, vp])
     lib.mip_instance_count.argtypes = [vp]
     lib.mip_instance_count.restype = C.c_uint32
     _lib = lib

@@ -18,6 +18,9 @@
 // base read on the device (cluster_list_phase_kernel.hpp, cluster_list_phase_plan.hpp: the front and the list tail of its own).
 // mip_list_clusters_views_occluded is mip_list_clusters_views with a depth pyramid per view: one new kernel in the several-view
 // cull kernel's place (cluster_views_occluded_kernel.hpp), the same plan, stream, scratch and status words.
+// mip_list_cluster_triangles is mip_list_clusters with the per-triangle test behind the cull: an entry per surviving cluster that
+// keeps a triangle and its 64-bit triangle mask beside it (cluster_triangle_list_kernel.hpp, cluster_triangle_list_plan.hpp: the
+// list's front and word members, then four new kernels).
 // cluster_plan.hpp, cluster_triangle_plan.hpp and cluster_cone_plan.hpp hold the arithmetic and the launch plans; the kernels
 // (cluster_kernel.hpp, cluster_triangle_kernel.hpp, cluster_cone_kernel.hpp) are instantiated here and only here.
 #include "context.hpp"
@@ -29,6 +32,7 @@
 #include "cluster_views_list_kernel.hpp"
 #include "cluster_list_phase_kernel.hpp"
 #include "cluster_views_occluded_kernel.hpp"
+#include "cluster_triangle_list_kernel.hpp"
 
 static_assert(sizeof(MipClusterViewOutputs) == 40, "MipClusterViewOutputs is part of the ABI");
 static_assert(sizeof(MipClusterOutputs) == 40, "MipClusterOutputs is part of the ABI");
@@ -40,6 +44,8 @@ static_assert(sizeof(MipClusterListOutputs) == 48, "MipClusterListOutputs is par
 static_assert(sizeof(MipClusterViewListOutputs) == 48, "MipClusterViewListOutputs is part of the ABI");
 static_assert(sizeof(MipClusterPhaseListOutputs) == 56, "MipClusterPhaseListOutputs is part of the ABI");
 static_assert(sizeof(MipClusterViewOccludedListOutputs) == 56, "MipClusterViewOccludedListOutputs is part of the ABI");
+static_assert(sizeof(MipClusterTriangleListOutputs) == 56, "MipClusterTriangleListOutputs is part of the ABI");
+static_assert(mip::kClusterTriangleListStats == mip::kClusterTriangleStats, "words 1 to 5 are mip_cull_cluster_triangles'");
 static_assert(sizeof(mip::ClusterConeEntry) == 2 * sizeof(float4), "a cone is the two 16-byte words the kernels load");
 static_assert(mip::kClusterFirst == MIP_CLUSTER_PHASE_FIRST && mip::kClusterSecond == MIP_CLUSTER_PHASE_SECOND, "cluster_kernel.hpp restates the header");
 static_assert(MIP_CLUSTER_TRIANGLES == mip::kClusterTriangles, "cluster_plan.hpp restates the header");
@@ -196,6 +202,17 @@ int32_t ensure_list_scratch(MipContext* ctx, MipContext::ClusterScratch& cs, con
   return MIP_OK;
 }
 
+// What mip_list_cluster_triangles takes on top of the list's (cluster_triangle_list_plan.hpp): 8 bytes per work item and 8 per
+// 64 work items of the bound, and the tile sums. The triangle words and the item tiles' sums are mip_cull_cluster_triangles'.
+int32_t ensure_triangle_list_scratch(MipContext* ctx, MipContext::ClusterScratch& cs, const mip::ClusterTriangleListPlan& plan) {
+  if (int32_t rc = ensure_list_scratch(ctx, cs, plan.list)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_triangle_words, &cs.triangle_words_cap, (size_t)plan.triangle_words, 8)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_nonempty_words, &cs.nonempty_words_cap, (size_t)plan.nonempty_words, 8)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_tile_triangles, &cs.tile_triangles_cap, (size_t)plan.item_tiles, 8)) return rc;
+  if (int32_t rc = grow(ctx, &cs.d_tile_clusters, &cs.tile_clusters_cap, (size_t)plan.cluster_tiles, 4)) return rc;
+  return MIP_OK;
+}
+
 // The event a SECOND call waits for: behind everything the FIRST call enqueued.
 int32_t record_written(MipContext* ctx, hipStream_t stream) {
   if (!ctx->cluster_record_written) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_record_written, hipEventDisableTiming));
@@ -218,9 +235,12 @@ int32_t launch(MipContext* ctx, Kernel kernel, uint32_t blocks, hipStream_t stre
 // cull kernel's place, nothing else differs.
 // list != null: mip_list_clusters — `out` holds its fields under mip_cull_clusters' names; the word members, the count, the
 // list's epilogue and the write take the place of heads, epilogue and commands (eight launches). cone may be null or not.
+// tlist != null (with `list`, which then holds the fields the two structs share): mip_list_cluster_triangles — the triangle
+// test between the word members and the count, and the count, epilogue and write of cluster_triangle_list_kernel.hpp (nine launches).
 int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy, const MipOcclusion* occ,
                       const MipClusterOutputs* out, const MipClusterRecord* rec, bool phased, const MipClusterTriangleOutputs* tri = nullptr,
-                      const MipClusterCone* cone = nullptr, bool coned = false, const MipClusterListOutputs* list = nullptr) {
+                      const MipClusterCone* cone = nullptr, bool coned = false, const MipClusterListOutputs* list = nullptr,
+                      const MipClusterTriangleListOutputs* tlist = nullptr) {
   if (!frame || !visible_bitmap || !out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
   if (coned)
     if (int32_t rc = check_cone(ctx, cone)) return rc;
@@ -263,7 +283,7 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   const uint32_t n = ctx->n;
   if (n == 0) {  // nothing to test: zeros
     MIP_HIP(ctx, hipMemsetAsync(out->cmd_count, 0, 4, stream));
-    if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, tri ? 4 * mip::kClusterTriangleStats : list ? 12 : 16, stream));
+    if (out->stats) MIP_HIP(ctx, hipMemsetAsync(out->stats, 0, tri || tlist ? 4 * mip::kClusterTriangleStats : list ? 12 : 16, stream));
     if (list && list->draw_args) {  // {192, 0, 0, 0}
       MIP_HIP(ctx, hipMemsetAsync(list->draw_args, 0, 16, stream));
       MIP_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(list->draw_args), (int)mip::kClusterListDrawVertices, 1, stream));
@@ -292,8 +312,12 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
   if (tri)
     if (int32_t rc = ensure_triangle_scratch(ctx, cs, tri_plan)) return rc;
   const mip::ClusterListPlan list_plan = mip::plan_cluster_list(bound);
-  if (list)
+  const mip::ClusterTriangleListPlan tlist_plan = mip::plan_cluster_triangle_list(bound);
+  if (tlist) {
+    if (int32_t rc = ensure_triangle_list_scratch(ctx, cs, tlist_plan)) return rc;
+  } else if (list) {
     if (int32_t rc = ensure_list_scratch(ctx, cs, list_plan)) return rc;
+  }
   if (occ && ctx->next_slot != slot) {
     // a pyramid built for the next run sits on that slot's stream: this call goes behind what that stream holds now
     if (!ctx->cluster_pyramid_ready) MIP_HIP(ctx, hipEventCreateWithFlags(&ctx->cluster_pyramid_ready, hipEventDisableTiming));
@@ -390,9 +414,29 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
     la.draw_args = list->draw_args;
     la.list_stats = list->stats;
     if (int32_t rc = launch(ctx, mip::mip_cluster_list_word_members_kernel, list_plan.word_blocks, stream, la)) return rc;
-    if (int32_t rc = launch(ctx, mip::mip_cluster_list_count_kernel, list_plan.word_blocks, stream, la)) return rc;
-    if (int32_t rc = launch(ctx, mip::mip_cluster_list_epilogue_kernel, 1, stream, la)) return rc;
-    if (int32_t rc = launch(ctx, mip::mip_cluster_list_write_kernel, list_plan.write_blocks, stream, la)) return rc;
+    if (tlist) {
+      mip::ClusterTriangleListArgs ta{};
+      ta.l = la;
+      ta.vertices = ctx->d_vertices;
+      ta.indices = ctx->d_indices;
+      ta.vertex_bytes = (unsigned long long)ctx->n_vertices * 12ull;
+      ta.geometry_finite = ctx->geometry_finite ? 1u : 0u;
+      std::memcpy(ta.pv, frame->pv, sizeof ta.pv);
+      ta.triangle_words = cs.d_triangle_words;
+      ta.nonempty = cs.d_nonempty_words;
+      ta.tile_kept = cs.d_tile_triangles;
+      ta.tile_tested = cs.d_tile_triangles + tlist_plan.item_tiles;
+      ta.tile_clusters = cs.d_tile_clusters;
+      ta.masks = static_cast<unsigned long long*>(tlist->triangle_masks);
+      if (int32_t rc = launch(ctx, mip::mip_cluster_triangle_list_test_kernel, tlist_plan.test_blocks, stream, ta)) return rc;
+      if (int32_t rc = launch(ctx, mip::mip_cluster_triangle_list_count_kernel, tlist_plan.count_blocks, stream, ta)) return rc;
+      if (int32_t rc = launch(ctx, mip::mip_cluster_triangle_list_epilogue_kernel, 1, stream, ta)) return rc;
+      if (int32_t rc = launch(ctx, mip::mip_cluster_triangle_list_write_kernel, tlist_plan.write_blocks, stream, ta)) return rc;
+    } else {
+      if (int32_t rc = launch(ctx, mip::mip_cluster_list_count_kernel, list_plan.word_blocks, stream, la)) return rc;
+      if (int32_t rc = launch(ctx, mip::mip_cluster_list_epilogue_kernel, 1, stream, la)) return rc;
+      if (int32_t rc = launch(ctx, mip::mip_cluster_list_write_kernel, list_plan.write_blocks, stream, la)) return rc;
+    }
   } else if (tri) {
     mip::ClusterTriangleArgs ta{};
     ta.c = a;
@@ -426,6 +470,8 @@ int32_t cull_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t* vi
     const uint32_t code = *status;
     *status = 0;
     if (code & mip::kClusterStatusDevice) return fail(ctx, MIP_ERR_DEVICE, "%s", kNotItsRecord);
+    if (tlist)
+      return fail(ctx, MIP_ERR_CAPACITY, "mip_list_cluster_triangles: more entries than entry_capacity (the first entry_capacity entries and masks are written), or more work items than work_capacity / 2^32 - 1 (nothing is written); stats holds the counts");
     if (list)
       return fail(ctx, MIP_ERR_CAPACITY, "mip_list_clusters: more surviving clusters than entry_capacity (the first entry_capacity entries are written), or more work items than work_capacity / 2^32 - 1 (nothing is written); stats holds the counts");
     if (tri)
@@ -1106,7 +1152,7 @@ int32_t cluster_wait_status(MipContext* ctx, int32_t rc) {
   }
   if (!raised) return MIP_OK;
   if (raised & mip::kClusterStatusDevice) return fail(ctx, MIP_ERR_DEVICE, "asynchronous %s", kNotItsRecord);
-  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters, mip_list_clusters, mip_list_clusters_phase, mip_cull_clusters_views, mip_list_clusters_views or mip_list_clusters_views_occluded had more runs than cmd_capacity (more surviving clusters than entry_capacity / entry_stride / the room behind entry_base), or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
+  return fail(ctx, MIP_ERR_CAPACITY, "an asynchronous mip_cull_clusters, mip_list_clusters, mip_list_cluster_triangles, mip_list_clusters_phase, mip_cull_clusters_views, mip_list_clusters_views or mip_list_clusters_views_occluded had more runs than cmd_capacity (more surviving clusters than entry_capacity / entry_stride / the room behind entry_base), or more work items than work_capacity / 2^32 - 1; its stats hold the counts");
 }
 
 void cluster_release(MipContext* ctx) {
@@ -1133,6 +1179,8 @@ void cluster_release(MipContext* ctx) {
     (void)hipFree(cs.d_list_tiles);
     (void)hipFree(cs.d_list_candidates);
     (void)hipFree(cs.d_list_phase_scalars);
+    (void)hipFree(cs.d_nonempty_words);
+    (void)hipFree(cs.d_tile_clusters);
   }
   ctx->cluster_scratch.clear();
   {
@@ -1282,6 +1330,54 @@ int32_t mip_list_clusters(MipContext* ctx, const MipFrame* frame, const uint32_t
   shared.cmd_count = out->entry_count;
   shared.stats = out->stats;
   return cull_clusters(ctx, frame, visible_bitmap, policy, occ, &shared, nullptr, false, nullptr, cone, cone != nullptr, out);
+}
+
+// Whether [p, p + bytes) and [q, q + qbytes) share a byte (q may be null: no).
+static bool ranges_overlap(const void* p, unsigned long long bytes, const void* q, unsigned long long qbytes) {
+  if (!q || !bytes || !qbytes) return false;
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b ? bytes > b - a : qbytes > a - b;
+}
+
+// mip_list_cluster_triangles: the checks of its own fields, then the call it shares with mip_list_clusters
+int32_t mip_list_cluster_triangles(MipContext* ctx, const MipFrame* frame, const uint32_t* visible_bitmap, const MipLodPolicy* policy,
+                                   const MipOcclusion* occ, const MipClusterCone* cone, const MipClusterTriangleListOutputs* out) {
+  if (!ctx) return MIP_ERR_INVALID_ARGUMENT;
+  if (int32_t rc = check_policy(ctx, policy)) return rc;
+  if (!out) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "frame/visible_bitmap/out is NULL");
+  if (out->struct_size != sizeof(MipClusterTriangleListOutputs))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "MipClusterTriangleListOutputs.struct_size %u != %zu", out->struct_size, sizeof(MipClusterTriangleListOutputs));
+  if (!out->cluster_entries || !out->entry_count) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cluster_entries/entry_count is NULL");
+  if ((uintptr_t)out->cluster_entries % 16u != 0u) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "cluster_entries is not 16-byte aligned");
+  if (!out->triangle_masks || (uintptr_t)out->triangle_masks % 8u != 0u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "triangle_masks is NULL or not 8-byte aligned");
+  if (out->flags & ~(MIP_OUT_DEVICE | MIP_OUT_ASYNC)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "unknown MipClusterTriangleListOutputs flags 0x%x", out->flags);
+  if (!(out->flags & MIP_OUT_DEVICE)) return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "mip_list_cluster_triangles needs MIP_OUT_DEVICE outputs");
+  if ((uintptr_t)out->entry_count % 4u != 0u || (uintptr_t)out->draw_args % 4u != 0u || (uintptr_t)out->stats % 4u != 0u)
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "entry_count, draw_args or stats is not 4-byte aligned");
+  const unsigned long long mask_bytes = 8ull * out->entry_capacity;
+  if (ranges_overlap(out->triangle_masks, mask_bytes, out->cluster_entries, 16ull * out->entry_capacity) ||
+      ranges_overlap(out->triangle_masks, mask_bytes, out->entry_count, 4) || ranges_overlap(out->triangle_masks, mask_bytes, out->draw_args, 16) ||
+      ranges_overlap(out->triangle_masks, mask_bytes, out->stats, 4ull * mip::kClusterTriangleListStats))
+    return fail(ctx, MIP_ERR_INVALID_ARGUMENT, "triangle_masks overlaps another output");
+  MipClusterListOutputs list{};  // the fields it shares with mip_list_clusters, and under them those of mip_cull_clusters
+  list.struct_size = sizeof(MipClusterListOutputs);
+  list.flags = out->flags;
+  list.cluster_entries = out->cluster_entries;
+  list.entry_capacity = out->entry_capacity;
+  list.work_capacity = out->work_capacity;
+  list.entry_count = out->entry_count;
+  list.draw_args = out->draw_args;
+  list.stats = out->stats;
+  MipClusterOutputs shared{};
+  shared.struct_size = sizeof(MipClusterOutputs);
+  shared.flags = out->flags;
+  shared.cluster_cmds = out->cluster_entries;
+  shared.cmd_capacity = out->entry_capacity;
+  shared.work_capacity = out->work_capacity;
+  shared.cmd_count = out->entry_count;
+  shared.stats = out->stats;
+  return cull_clusters(ctx, frame, visible_bitmap, policy, occ, &shared, nullptr, false, nullptr, cone, cone != nullptr, &list, out);
 }
 
 uint64_t mip_cluster_record_bytes(uint64_t work_items) { return mip::cluster_record_bytes(work_items); }

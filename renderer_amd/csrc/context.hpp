@@ -161,6 +161,11 @@ struct MipContext {
     uint32_t* d_list_candidates = nullptr;  // per list tile: the candidates of its record words (FIRST)
     uint32_t* d_list_phase_scalars = nullptr;  // the entry base and the room, from the epilogue to the write kernel
     size_t list_candidates_cap = 0;
+    // mip_list_cluster_triangles (cluster_triangle_list_plan.hpp) on top of the list's; d_triangle_words and d_tile_triangles
+    // above are shared with mip_cull_cluster_triangles (one stream per slot: the calls follow each other)
+    unsigned long long* d_nonempty_words = nullptr;  // per 64 work items: the surviving items that keep a triangle
+    uint32_t* d_tile_clusters = nullptr;  // per list tile: surviving clusters
+    size_t nonempty_words_cap = 0, tile_clusters_cap = 0;
   };
   std::vector<ClusterScratch> cluster_scratch;
   // mip_cull_clusters_views (cluster_views_plan.hpp): its own scratch on the first stream, as view_batch is — no frame slot's

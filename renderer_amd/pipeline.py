@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterListOutputs, MipClusterOutputs, MipClusterPhaseListOutputs, MipClusterRecord, MipClusterTriangleOutputs, MipClusterViewListOutputs, MipClusterViewOccludedListOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
+from ._lib import (MipBatchOutputs, MipClusterCone, MipClusterListOutputs, MipClusterOutputs, MipClusterPhaseListOutputs, MipClusterRecord, MipClusterTriangleListOutputs, MipClusterTriangleOutputs, MipClusterViewListOutputs, MipClusterViewOccludedListOutputs, MipClusterViewOutputs, MipConfig, MipError, MipFrame, MipLodPolicy, MipOcclusion, MipOutputs, MipShardedOutputs, MipSortPolicy,
                    MipTimings, MipViewBatchOutputs)
 
 MESH_DTYPE = np.dtype(
@@ -171,6 +171,23 @@ def make_cluster_list_outputs(cluster_entries, entry_capacity, entry_count, draw
     o.struct_size = C.sizeof(MipClusterListOutputs)
     o.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
     o.cluster_entries = cluster_entries or None
+    o.entry_capacity = int(entry_capacity)
+    o.work_capacity = int(work_capacity)
+    o.entry_count = entry_count or None
+    o.draw_args = draw_args or None
+    o.stats = stats or None
+    return o
+
+
+def make_cluster_triangle_list_outputs(cluster_entries, triangle_masks, entry_capacity, entry_count, draw_args=0, stats=0, work_capacity=0, async_=False):
+    """A MipClusterTriangleListOutputs for list_cluster_triangles: make_cluster_list_outputs' fields, a device pointer to room for
+    entry_capacity 64-bit triangle masks (8-byte aligned; mask k goes with entry k) and SIX stats words {entries, surviving
+    clusters, W, members, surviving triangles, triangles tested}."""
+    o = MipClusterTriangleListOutputs()
+    o.struct_size = C.sizeof(MipClusterTriangleListOutputs)
+    o.flags = _lib.MIP_OUT_DEVICE | (_lib.MIP_OUT_ASYNC if async_ else 0)
+    o.cluster_entries = cluster_entries or None
+    o.triangle_masks = triangle_masks or None
     o.entry_capacity = int(entry_capacity)
     o.work_capacity = int(work_capacity)
     o.entry_count = entry_count or None
@@ -852,6 +869,16 @@ class InstancePipeline:
         self._check(self._lib.mip_list_clusters(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
                                                 C.addressof(occlusion) if occlusion is not None else None,
                                                 C.addressof(cone) if cone is not None else None, C.addressof(outputs)))
+
+    def list_cluster_triangles(self, frame, visible_bitmap_ptr, policy, outputs, occlusion=None, cone=None):
+        """mip_list_cluster_triangles: list_clusters with the per-triangle stage's test (frame's pv) behind the cluster cull.
+        `outputs` (make_cluster_triangle_list_outputs) receives one entry per surviving cluster that keeps at least one triangle —
+        a subsequence of list_clusters' list — and beside entry k the 64-bit mask of the cluster's surviving triangles: no index
+        stream, no commands, and no entry for a cluster whose triangles are all culled. MIP_ERR_CAPACITY (from wait() for an
+        asynchronous call) when the entries do not fit entry_capacity or the work items exceed work_capacity."""
+        self._check(self._lib.mip_list_cluster_triangles(self._ctx, C.addressof(frame), visible_bitmap_ptr or None, C.addressof(policy),
+                                                         C.addressof(occlusion) if occlusion is not None else None,
+                                                         C.addressof(cone) if cone is not None else None, C.addressof(outputs)))
 
     def list_clusters_views(self, frames, visible_bitmap_ptrs, policy, outputs):
         """mip_list_clusters_views: cull_clusters_views with list_clusters' flat list in the commands' place, one list and one
